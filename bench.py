@@ -18,6 +18,12 @@ Rank 0 prints ONE JSON line.  Besides the contract keys it carries
   cpu_baseline  - the oracle (CPU restatement of the reference, numpy/scipy + C/OpenMP BCD) timed on this box's host
                   cores on the headline's own rows (--cpu-sample, default all 1M: ~30 s of CPU; N=1 only)
   count_like    - the same measurement on the count-like / log_cpm family, which runs all 100 iterations
+
+Every family record runs --steps timed fits after --warmup untimed ones.  The inputs depend only on the arguments (seeded
+generators), so runs with the same arguments fit the same data.  --dump-outputs DIR (one GPU) writes, after the timed steps,
+what the last timed fit of each family returned to its caller (beta_, proportions_, gene_idx_, info_) as DIR/<family>_<name>.npy
+in float64, at most DUMP_BYTES in all: beta_ and proportions_ on a fixed, seeded sample of rows (DIR/sample_rows.npy) when the
+whole arrays would not fit.
 """
 import argparse
 import json
@@ -68,7 +74,15 @@ def parse():
                     help="skip the host_arrays record (numpy / scipy in, numpy out: the literal drop-in, PCIe included)")
     ap.add_argument("--cpu-sample", type=int, default=1_000_000,
                     help="rows of the headline matrix the CPU baseline is timed on (default: all of configs[2]: ~30 s of CPU)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what each family's last timed fit returned as DIR/<family>_<name>.npy "
+                         "(float64, at most 64 MB in all: a fixed, seeded sample of rows when the whole arrays do not fit)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and (a.gpus > 1 or a.virtual_ranks > 0 or os.environ.get("FDX_BENCH_FORCE_DIST")):
+        ap.error("--dump-outputs covers the one-GPU families only (not --gpus N > 1, --virtual-ranks or FDX_BENCH_FORCE_DIST)")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------ synthetic inputs
@@ -109,8 +123,9 @@ def gen_counts(torch, n, G, K, device, seed):
         dist = torch.cdist(coords[r0:r1], centres)
         B = torch.exp(-dist / (side / 2))
         B /= B.sum(dim=1, keepdim=True)
-        depth = torch.distributions.Gamma(torch.tensor(5.0, device=device, dtype=torch.float64),
-                                          torch.tensor(1.0 / 1000.0, device=device, dtype=torch.float64)).sample((r1 - r0,))
+        # depth ~ Gamma(5, scale 1000) as the sum of five exponentials, drawn from the seeded generator (a
+        # torch.distributions.Gamma sample would come from the device's global stream and change from run to run)
+        depth = torch.empty(5, r1 - r0, device=device, dtype=torch.float64).exponential_(generator=g).sum(dim=0) * 1000.0
         lam = (B @ X) * depth[:, None]
         lam *= 1 + 0.1 * torch.rand(r1 - r0, G, generator=g, device=device, dtype=torch.float64)
         Y[r0:r1] = torch.poisson(lam, generator=g).to(torch.float32)
@@ -277,11 +292,45 @@ def sketch_kernel_name(mode, K, d=512, dtype="float"):
         "true" if (wg and os.environ.get("FDX_TILE_FLAT")) else "false")
 
 
-def aux_steps(a):
-    """Timed steps of the families beside the headline (count-like, CSR, lattice): the driver's --steps, at most 10; they get
-    the same --warmup as the headline (a family's first two or three fits in a process still pay for pooled buffers changing
-    hands: with two warm-up fits and two timed ones the driver's figure was the tail of the warm-up)."""
-    return max(1, min(a.steps, 10))
+DUMP_BYTES = 64_000_000                          # --dump-outputs: all files together (64 MB)
+
+
+def dump_plan(a, n_records):
+    """--dump-outputs: the rows of beta_ / proportions_ that are written - all n when n_records families' arrays fit in
+    DUMP_BYTES beside the small ones (gene_idx_, info_, the row list), else a fixed, seeded, sorted sample that does."""
+    n, K = a.spots, a.types
+    small = n_records * 8 * (8 + max(a.genes, a.sparse_genes)) + (64 << 10)      # gene_idx_ + info_ + npy headers
+    rows = min(n, (DUMP_BYTES - small) // (n_records * 2 * K * 8 + 8))
+    if rows < 1:
+        raise SystemExit("bench.py: --dump-outputs: not one row of the outputs fits in %d bytes" % DUMP_BYTES)
+    if rows == n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(0).choice(n, size=rows, replace=False))
+
+
+def fit_outputs(torch, model, rows):
+    """What FlashDeconv.fit handed its caller (output="torch"), as float64 host arrays: beta_ and proportions_ at `rows`,
+    gene_idx_, and info_ as [n_iterations, converged, final_objective, final_change, lambda_used_]."""
+    idx = torch.from_numpy(rows).to(model.proportions_.device)
+    out = {"beta": model.beta_.index_select(0, idx).cpu().numpy().astype(np.float64),
+           "proportions": model.proportions_.index_select(0, idx).cpu().numpy().astype(np.float64)}
+    if model.gene_idx_ is not None:
+        out["gene_idx"] = np.asarray(model.gene_idx_, dtype=np.float64)
+    i = model.info_
+    out["info"] = np.array([i["n_iterations"], float(i["converged"]), i["final_objective"], i["final_change"], model.lambda_used_],
+                           dtype=np.float64)
+    return out
+
+
+def write_dump(path, rows, dumped):
+    os.makedirs(path, exist_ok=True)
+    arrays = {"sample_rows": rows.astype(np.float64)}
+    for fam, out in dumped.items():
+        arrays.update({f"{fam}_{name}": v for name, v in out.items()})
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_BYTES, total
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def run_family(torch, model_kw, Y, X, coords, steps, warmup, barrier):
@@ -446,7 +495,8 @@ def spawn_ranks(n_ranks, rendezvous_timeout_s=None):
     them all, relay rank 0's output and exit with the worst return code.  The first rank that exits non-zero ends the job: the
     others are terminated (they would sit in a collective until the driver's timeout) and the parent returns that code within
     seconds.  Every rank's stderr goes to a file named by rank (gpurun_out/bench_rank<r>.err, else the temp dir); a rank that
-    produces no result within --rendezvous-timeout seconds of the start (default 900; FDX_BENCH_RDZV_TIMEOUT) ends the job too."""
+    produces no result within --rendezvous-timeout seconds of the start (default 900; FDX_BENCH_RDZV_TIMEOUT) ends the job too.
+    In the temp dir the files go to a directory of the job's own, removed when the job succeeds."""
     import socket
     import subprocess
     import tempfile
@@ -455,8 +505,10 @@ def spawn_ranks(n_ranks, rendezvous_timeout_s=None):
         port = sk.getsockname()[1]
     timeout_s = float(rendezvous_timeout_s or os.environ.get("FDX_BENCH_RDZV_TIMEOUT", "900"))
     logdir = os.path.join(ROOT, "gpurun_out")
+    own_logdir = False
     if not os.path.isdir(logdir) or not os.access(logdir, os.W_OK):
-        logdir = tempfile.gettempdir()
+        # a directory of this job's own: fixed names in the shared temp dir collide with another user's or job's files
+        logdir, own_logdir = tempfile.mkdtemp(prefix="fdx_bench_ranks_"), True
     procs, errs = [], []
     out0 = tempfile.TemporaryFile()
     for r in range(n_ranks):
@@ -513,6 +565,9 @@ def spawn_ranks(n_ranks, rendezvous_timeout_s=None):
                 sys.stderr.write(f.read().decode(errors="replace"))
         except OSError:
             pass
+        if own_logdir:                                # relayed, and no failure message points at it
+            import shutil
+            shutil.rmtree(logdir, ignore_errors=True)
     sys.exit(rc)
 
 
@@ -642,6 +697,10 @@ def main():
     cpu_inputs = None
     y_f64 = None
     fams = {"both": ["gaussian", "counts"], "all": ["gaussian", "counts", "sparse", "lattice"]}.get(a.family, [a.family])
+    dumped, dump_rows = {}, None
+    if a.dump_outputs:
+        with_f64 = "gaussian" in fams and a.config == 3 and a.family == "all"      # the y_f64 record below
+        dump_rows = dump_plan(a, len(fams) + int(with_f64))
     for fam in fams:
         if fam == "lattice":
             # Visium-HD bins sit on a regular lattice: with k = 6 every spot's k-th neighbour is tied (four at distance 1, four at
@@ -652,11 +711,13 @@ def main():
             ii = torch.arange(n, device=device)
             coords = torch.stack([(ii % side).double(), (ii // side).double()], dim=1)
             kw = dict(sketch_dim=d, preprocess="log_cpm", n_hvg=G)
-            lsteps = aux_steps(a)
+            lsteps = a.steps
             import warnings
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore")
                 model, dt, stage = run_family(torch, kw, Y, X, coords, lsteps, a.warmup, barrier)
+            if dump_rows is not None:
+                dumped[fam] = fit_outputs(torch, model, dump_rows)
             ms_step = dt / lsteps * 1e3
             results[fam] = {
                 "value": n * lsteps / dt, "unit": "spots/s", "ms_per_step": ms_step, "steps": lsteps, "warmup": a.warmup,
@@ -673,8 +734,10 @@ def main():
         if fam == "sparse":
             Y, X, coords = gen_sparse(torch, n, a.sparse_genes, K, device, seed=0)
             kw = dict(sketch_dim=d, preprocess="log_cpm", n_hvg=G, max_iter=20)
-            ssteps = aux_steps(a)
+            ssteps = a.steps
             model, dt, stage = run_family(torch, kw, Y, X, coords, ssteps, a.warmup, barrier)
+            if dump_rows is not None:
+                dumped[fam] = fit_outputs(torch, model, dump_rows)
             nnz_y = int(Y.values().numel())
             # fused CSR sketch -> H (gram_ms == 0): reads the stored entries (4 B value + 4 B column each) and the row extents, writes
             # H; the two-kernel path also writes and re-reads Y_sketch (n x d x 8 B)
@@ -707,8 +770,10 @@ def main():
         else:
             Y, X, coords = gen_counts(torch, n, G, K, device, seed=0)
             kw = dict(sketch_dim=d, preprocess="log_cpm", n_hvg=G)
-        steps = a.steps if fam == "gaussian" else aux_steps(a)
+        steps = a.steps
         model, dt, stage = run_family(torch, kw, Y, X, coords, steps, a.warmup, barrier)
+        if dump_rows is not None:
+            dumped[fam] = fit_outputs(torch, model, dump_rows)
         T = model.info_["n_iterations"]
         nnz = int(model._graph.info()[1])
         sk_bytes, sw_bytes = alg_bytes(n, G, K, 4, nnz, 0, T)
@@ -741,10 +806,12 @@ def main():
         if fam == "gaussian" and a.config == 3 and a.family == "all":
             # the same job with Y stored float64 in HBM - the reference's own dtype (core/deconv.py:229): twice the one-off read
             Y64 = Y.double()
-            m64, dt64, st64 = run_family(torch, kw, Y64, X, coords, aux_steps(a), a.warmup, barrier)
-            ms64 = dt64 / aux_steps(a) * 1e3
+            m64, dt64, st64 = run_family(torch, kw, Y64, X, coords, a.steps, a.warmup, barrier)
+            if dump_rows is not None:
+                dumped["gaussian_y_f64"] = fit_outputs(torch, m64, dump_rows)
+            ms64 = dt64 / a.steps * 1e3
             g64 = n * G * 8 / (st64["sketch_ms"] * 1e-3) / 1e9
-            y_f64 = {"value": n / (ms64 * 1e-3), "unit": "spots/s", "ms_per_step": ms64, "steps": aux_steps(a),
+            y_f64 = {"value": n / (ms64 * 1e-3), "unit": "spots/s", "ms_per_step": ms64, "steps": a.steps,
                      "step_ms_min_max": st64.pop("step_ms_min_max"), "cold_ms": round(st64["cold_ms"], 3),
                      "n_iterations": m64.info_["n_iterations"], "converged": m64.info_["converged"], "workload": "same job, Y float64 in HBM (16 GB)",
                      "roofline": {"bound": "hbm", "kernel": "fdx::tile_sketch_kernel<double, ...>", "achieved": round(g64, 1), "peak": HBM_PEAK_GBS,
@@ -760,6 +827,8 @@ def main():
             cpu_inputs = True
         del Y, coords, model
         torch.cuda.empty_cache()
+    if dump_rows is not None:
+        write_dump(a.dump_outputs, dump_rows, dumped)
 
     main_fam = "gaussian" if "gaussian" in results else ("counts" if "counts" in results else ("sparse" if "sparse" in results else "lattice"))
     if main_fam in ("sparse", "lattice"):

@@ -4,7 +4,7 @@ oracle/fdx_oracle.py -- TEST INFRASTRUCTURE, NOT PRODUCT CODE.
 CPU restatement (NumPy float64; pure-Python loops for tiny cases; C via
 oracle/bcd_ref.c for the BCD sweep and the MT19937 hash stream) of the reference's
 sketched graph-regularised NNLS path, stage by stage.  Every function cites the
-reference lines (under /root/reference/flashdeconv/) it follows.
+reference lines (under flashdeconv/ of cafferychen777/flashdeconv v0.1.6) it follows.
 
 Who may import this: tests/, __graft_entry__.smoke(), bench.py's cpu_baseline leg.
 The product package (flashdeconv_amd/) never imports it and has no CPU fallback.

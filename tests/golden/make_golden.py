@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Capture golden vectors from the reference implementation (this container only).
+"""Capture golden vectors from the reference implementation (needs a checkout of it).
 
-The reference (``/root/reference``, pure Python) cannot travel to the GPU box and
+The reference (cafferychen777/flashdeconv v0.1.6, pure Python; the checkout's root is
+given by ``FDX_REFERENCE``) cannot travel to the GPU box and
 imports ``numba``, which is absent here.  Its three ``@jit`` functions are plain
 Python compiled without fastmath, so running them un-jitted has the same float64
 semantics.  This script therefore puts a no-op stand-in module
@@ -10,7 +11,7 @@ named ``numba`` on ``sys.path`` (``jit`` = identity decorator, ``prange`` =
 seeded inputs of ``tests/datagen.py`` and stores inputs' SHA-256 + outputs as
 small ``.npz`` files next to this script.  Only data (arrays) is stored.
 
-Run:  python tests/golden/make_golden.py        (takes a few minutes; pure-Python BCD)
+Run:  FDX_REFERENCE=<checkout> python tests/golden/make_golden.py        (takes a few minutes; pure-Python BCD)
 """
 import os
 import sys
@@ -24,10 +25,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 import datagen  # noqa: E402
 
-REF = os.environ.get("FDX_REFERENCE", "/root/reference")
+REF = os.environ.get("FDX_REFERENCE")
 
 
 def _import_reference():
+    if not REF or not os.path.isdir(os.path.join(REF, "flashdeconv")):
+        raise SystemExit("make_golden.py: set FDX_REFERENCE to a checkout of the reference (the directory holding flashdeconv/)")
     shim_dir = tempfile.mkdtemp(prefix="numba_standin_")
     with open(os.path.join(shim_dir, "numba.py"), "w") as f:
         f.write(

@@ -242,3 +242,59 @@ def test_config4_ten_million_spots_eight_virtual_ranks():
     assert info4["n_iterations"][0] == its[0] and info4["nnz"] == info8["nnz"]
     np.testing.assert_allclose(info4["lambda_used"], info8["lambda_used"], rtol=1e-14)
     assert torch.equal(beta4, beta8)
+
+
+def test_bench_inputs_repeat_and_dump_outputs_of_the_timed_fits(tmp_path, monkeypatch, capsys):
+    """bench.py's generators give the same inputs for the same seed (every draw from the seeded generator), and --dump-outputs
+    writes what each family's last timed fit returned: float64 files within bench.DUMP_BYTES, taken from the model that ran
+    exactly --warmup + --steps fits (not the cold fit's own model) after its last fit."""
+    import json
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from flashdeconv_amd import FlashDeconv
+    dev = torch.device("cuda", 0)
+    for gen, G in ((bench.gen_gaussian, 300), (bench.gen_counts, 300), (bench.gen_sparse, 2000)):
+        (Y1, X1, c1), (Y2, X2, c2) = gen(torch, 20000, G, 8, dev, 5), gen(torch, 20000, G, 8, dev, 5)
+        parts = (lambda Y: (Y.crow_indices(), Y.col_indices(), Y.values())) if Y1.layout == torch.sparse_csr else (lambda Y: (Y,))
+        assert all(torch.equal(u, v) for u, v in zip(parts(Y1), parts(Y2))), gen.__name__
+        assert np.array_equal(X1, X2) and torch.equal(c1, c2), gen.__name__
+    fits, models, dumped_from = {}, [], []       # fit calls per model (models kept alive so that ids stay unique); per dump:
+    fit0, outputs0 = FlashDeconv.fit, bench.fit_outputs    # (model id, its fit calls when the dump was taken)
+
+    def counting_fit(self, *args, **kwargs):
+        if id(self) not in fits:
+            models.append(self)
+        fits[id(self)] = fits.get(id(self), 0) + 1
+        return fit0(self, *args, **kwargs)
+
+    def recording_outputs(torch_, model, rows):
+        dumped_from.append((id(model), fits.get(id(model))))
+        return outputs0(torch_, model, rows)
+
+    monkeypatch.setattr(FlashDeconv, "fit", counting_fit)
+    monkeypatch.setattr(bench, "fit_outputs", recording_outputs)
+    out = tmp_path / "dump"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--family", "all", "--spots", "20000", "--genes", "300", "--types", "8",
+                                      "--sketch-dim", "64", "--sparse-genes", "2000", "--steps", "3", "--warmup", "1",
+                                      "--no-cpu-baseline", "--no-live-pmc", "--no-host-arrays", "--dump-outputs", str(out)])
+    bench.main()
+    line = json.loads([ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")][-1])
+    # five dumps (gaussian, its float64-Y twin, counts, sparse, lattice), each of a model with 1 warm-up + 3 timed fits and none after
+    assert len(dumped_from) == 5 and all(n == 4 and fits[m] == 4 for m, n in dumped_from), (dumped_from, fits)
+    assert len({m for m, _ in dumped_from}) == 5
+    models.clear()
+    recs = {"gaussian": dict(line["config"], steps=line["steps"]), "gaussian_y_f64": line["y_f64"], "counts": line["count_like"],
+            "sparse": line["sparse_csr"], "lattice": line["lattice"]}
+    files = {p.name: np.load(p) for p in out.iterdir()}
+    assert sum(p.stat().st_size for p in out.iterdir()) <= bench.DUMP_BYTES
+    assert all(v.dtype == np.float64 for v in files.values())
+    assert np.array_equal(files["sample_rows.npy"], np.arange(20000))
+    for fam, rec in recs.items():
+        assert rec["steps"] == 3, fam
+        beta, prop, info = files[f"{fam}_beta.npy"], files[f"{fam}_proportions.npy"], files[f"{fam}_info.npy"]
+        assert beta.shape == prop.shape == (20000, 8) and bool((beta >= 0).all()), fam
+        np.testing.assert_allclose(prop.sum(axis=1), 1.0, atol=1e-12)
+        assert info[0] == rec["n_iterations"] and info[1] == float(rec["converged"]), fam
+        assert files[f"{fam}_gene_idx.npy"].ndim == 1
+    assert set(files) == {"sample_rows.npy"} | {f"{f}_{k}.npy" for f in recs for k in ("beta", "proportions", "info", "gene_idx")}

@@ -280,25 +280,58 @@ def test_bench_spawns_its_own_ranks():
     assert line["gpus"] == 3 and line["scaling"] == "weak" and int(line["MASTER_PORT"]) > 0
     # one rank dies at start-up (exit code 3), the others sit as in a collective: the parent ends them and returns non-zero
     # within seconds, naming the rank and where its stderr went
+    import shutil
     import time
+
+    def remove_job_logs(stderr):          # a failed job keeps its own log directory in the temp dir for the user
+        logdir = re.search(r"Per-rank stderr: (\S+)/bench_rank<r>\.err", stderr).group(1)
+        if os.path.basename(logdir).startswith("fdx_bench_ranks_"):
+            shutil.rmtree(logdir)
     env3 = dict(env, FDX_BENCH_SPAWN_FAIL_RANK="1", FDX_BENCH_SPAWN_HANG="120")
     t0 = time.monotonic()
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3"], env=env3, capture_output=True, text=True,
                          timeout=100)
     assert out.returncode == 3 and time.monotonic() - t0 < 30, (out.returncode, out.stderr)
     assert "rank 1 of 3 exited with code 3" in out.stderr and "rank asked to fail" in out.stderr
+    remove_job_logs(out.stderr)
     # ... and a job whose ranks never produce a result ends at the rendezvous timeout
     env4 = dict(env, FDX_BENCH_SPAWN_HANG="120")
     t0 = time.monotonic()
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rendezvous-timeout", "2"], env=env4,
                          capture_output=True, text=True, timeout=100)
     assert out.returncode == 124 and time.monotonic() - t0 < 30 and "produced no result in time" in out.stderr
+    remove_job_logs(out.stderr)
     # under torch.distributed.run the environment is already there: no second level of processes
     env2 = dict(env, RANK="1", LOCAL_RANK="1", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT="29999")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env2, capture_output=True, text=True,
                          timeout=120)
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["RANK"] == "1" and line["WORLD_SIZE"] == "2" and line["scaling"] == "strong"
+
+
+def test_bench_rejects_steps_it_cannot_time_and_dumps_it_cannot_write():
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    for args in (["--steps", "0"], ["--warmup", "-1"], ["--gpus", "2", "--dump-outputs", "d"], ["--virtual-ranks", "4", "--dump-outputs", "d"]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, capture_output=True, text=True, timeout=60)
+        assert out.returncode == 2 and ("--steps" in out.stderr or "--dump-outputs" in out.stderr), (args, out.stderr)
+
+
+def test_bench_dump_sample_is_fixed_and_within_budget():
+    """--dump-outputs: the rows written of beta_ / proportions_ - a seeded sample that is the same from run to run, and with the
+    small arrays every family writes stays within bench.DUMP_BYTES; all rows when they fit."""
+    import types
+    import bench
+    for n, K, n_rec, genes, sparse_genes in ((1_000_000, 30, 5, 2000, 20000), (1_250_000, 50, 1, 5000, 20000), (10_000_000, 96, 5, 2000, 50000)):
+        a = types.SimpleNamespace(spots=n, types=K, genes=genes, sparse_genes=sparse_genes)
+        rows = bench.dump_plan(a, n_rec)
+        assert np.array_equal(rows, bench.dump_plan(a, n_rec))
+        assert 0 < len(rows) < n and rows[0] >= 0 and rows[-1] < n and bool((np.diff(rows) > 0).all())
+        worst = len(rows) * 8 + n_rec * (2 * len(rows) * K * 8 + 8 * (5 + max(genes, sparse_genes)) + 4 * 128)
+        assert worst <= bench.DUMP_BYTES, (n, K, worst)
+    a = types.SimpleNamespace(spots=20000, types=8, genes=300, sparse_genes=2000)
+    assert np.array_equal(bench.dump_plan(a, 5), np.arange(20000))
 
 
 def test_schedule_builders_under_address_and_ub_sanitizers():

@@ -1,6 +1,6 @@
 import os, sys, time
 os.environ["FDX_TRACE_HOST"] = "1"
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, bench
 from flashdeconv_amd import FlashDeconv
 dev = torch.device("cuda:0")

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """One rank's whole share of the sharded fit (tools/virtual_ranks.py: alone_pipelined), repeated, for a kernel trace:
 
-    cd /tmp && rocprofv3 --kernel-trace --output-format csv -d out -- python3 /root/repo/tools/rank_probe.py 8 3
-    python3 tools/timeline.py out            # launch-order timeline of the last repetition (marker: normalize_export)
+    rocprofv3 --kernel-trace --output-format csv -d /tmp/rank_trace -- python3 tools/rank_probe.py 8 3
+    python3 tools/timeline.py /tmp/rank_trace            # launch-order timeline of the last repetition (marker: normalize_export)
 
 usage: rank_probe.py [W = 8] [rank = W // 2] [n = 1_000_000] [config5 = 0]"""
 import os
