@@ -351,6 +351,54 @@ int fdx_type_sums_dev(const void* Y_dev, int32_t dtype, int64_t n, int32_t G, in
 int fdx_type_sums_csr_dev(const fdx_csr_view* Y, const int32_t* rows_dev, const int32_t* type_off_dev, int32_t K, int32_t mean,
                           double* X_out_dev, void* stream);
 
+/* ---- evaluation metrics (replaces utils/metrics.py:12-266; csrc/metrics_kernels.cpp) --------------------------------------- *
+ * pred_dev / true_dev: (n, K) row-major device matrices of the same `dtype` (FDX_F32 / FDX_F64), row strides ld_pred / ld_true
+ * in elements; arithmetic is float64.  1 <= n, 1 <= K, n * K <= 2^31 - 1.  The results come back to host arrays, so these
+ * entries return after the device work is done (one device-to-host copy at the end).  Workspace comes from the library's
+ * caching pool (about 1.2 GB at 1M x 30 float64 when Spearman is asked for); fdx_trim() returns it to the driver.
+ *
+ * stats_host: (K + 1) rows of FDX_METRICS_FIELDS doubles; row k < K is column k, row K is all n * K entries.  Fields: */
+#define FDX_MX_SSE 0        /* sum of (pred - true)^2 (metrics.py:36-41) */
+#define FDX_MX_SAE 1        /* sum of |pred - true| (metrics.py:63-68) */
+#define FDX_MX_SUM_P 2      /* sums of pred / true (the means of metrics.py:208-209) */
+#define FDX_MX_SUM_T 3
+#define FDX_MX_MIN_P 4      /* min / max ignoring NaN: ptp of _safe_corr (metrics.py:100-103) is max - min unless a NaN ... */
+#define FDX_MX_MAX_P 5
+#define FDX_MX_MIN_T 6
+#define FDX_MX_MAX_T 7
+#define FDX_MX_NAN_P 8      /* ... which these flags (1.0 / 0.0) report */
+#define FDX_MX_NAN_T 9
+#define FDX_MX_N_RARE 10    /* rare-cell counts as exact integers (metrics.py:245-257); also in rare_host */
+#define FDX_MX_TP 11
+#define FDX_MX_FP 12
+#define FDX_MX_FN 13
+#define FDX_MX_JSD_SUM 14   /* row K only: sum of the per-spot JSD when jsd_out_dev was given (metrics.py:141-157) */
+#define FDX_MX_C_PT 15      /* centred sums of np.corrcoef (metrics.py:110): about the column means (rows < K) or the overall */
+#define FDX_MX_C_PP 16      /* means (row K): sum (p - mp)(t - mt), sum (p - mp)^2, sum (t - mt)^2 */
+#define FDX_MX_C_TT 17
+#define FDX_METRICS_FIELDS 18
+/* Spearman selection (metrics.py:104-106, 112-122): per column and / or over pred.flatten() vs true.flatten() */
+#define FDX_SPEARMAN_OVERALL 1
+#define FDX_SPEARMAN_PER_TYPE 2
+
+/* Moments of a pred / true pair (metrics.py:36-41 compute_rmse, :63-68 compute_mae, :107-122 Pearson compute_correlation,
+ * :141-157 compute_jsd, :245-257 compute_rare_cell_detection): stats_host as above; rare_host (may be NULL): int64
+ * {n_rare, TP, FP, FN} for `threshold` (rare: 0 < true < threshold; present: pred > threshold / 2); jsd_out_dev (n doubles on
+ * the device, NULL = skip the JSD) receives the per-spot JSD with clipping bound `epsilon`. */
+int fdx_metrics_moments_dev(const void* pred_dev, const void* true_dev, int32_t dtype, int64_t n, int32_t K, int64_t ld_pred,
+                            int64_t ld_true, double threshold, double epsilon, double* jsd_out_dev, double* stats_host,
+                            int64_t* rare_host, void* stream);
+/* Spearman correlation (metrics.py:104-106 scipy.stats.spearmanr: Pearson of average ranks, ties averaged, -0.0 == +0.0):
+ * rho_host[k] for column k (flags & FDX_SPEARMAN_PER_TYPE), rho_host[K] over all entries (flags & FDX_SPEARMAN_OVERALL), NaN
+ * where not asked for; clipped to [-1, 1].  The constant / NaN rules of _safe_corr (metrics.py:100-103) are the caller's: a
+ * constant column gives NaN here. */
+int fdx_metrics_spearman_dev(const void* pred_dev, const void* true_dev, int32_t dtype, int64_t n, int32_t K, int64_t ld_pred,
+                             int64_t ld_true, int32_t flags, double* rho_host, void* stream);
+/* Both in one device sequence and one copy back (metrics.py:160-217 evaluate_deconvolution). */
+int fdx_metrics_evaluate_dev(const void* pred_dev, const void* true_dev, int32_t dtype, int64_t n, int32_t K, int64_t ld_pred,
+                             int64_t ld_true, double threshold, double epsilon, int32_t flags, double* jsd_out_dev,
+                             double* stats_host, int64_t* rare_host, double* rho_host, void* stream);
+
 /* ---- device-pointer building blocks (spot-sharded multi-GPU driver, flashdeconv_amd/distributed.py) ------- *
  * One process per GPU; the host side (torch.distributed over RCCL) owns the buffers and the halo exchange, these
  * entry points only enqueue kernels on `stream`.  Same reference lines as the single-GPU entries above.           */
