@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: spots/sec to convergence of FlashDeconv.fit_transform on synthetic N x G x K data.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak]
+    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--full]
 
 One rank per GPU.  Under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the environment) this process is one of
 the N ranks; started from a bare shell with --gpus N > 1 it spawns the N ranks itself (fresh child processes, before
@@ -15,15 +15,25 @@ the N ranks.  --scaling weak: N x 1M spots, 1M per rank.
 
 Rank 0 prints ONE JSON line.  Besides the contract keys it carries
   roofline      - dominant kernel of the step vs the HBM roofline (algorithmic bytes / hipEvent-measured duration)
-  cpu_baseline  - the oracle (CPU restatement of the reference, numpy/scipy + C/OpenMP BCD) timed on this box's host
-                  cores on the headline's own rows (--cpu-sample, default all 1M: ~30 s of CPU; N=1 only)
+  stage_ms      - stage times of one step as they tile its wall time
+
+A plain run does only what the headline needs: one GPU, the gaussian/raw family, --warmup untimed fits, --steps timed ones,
+the result line (and the files of --dump-outputs).  --full adds everything else, each outside every timed region:
   count_like    - the same measurement on the count-like / log_cpm family, which runs all 100 iterations
+  y_f64, sparse_csr, lattice - the headline job with Y float64 in HBM, the CSR family, the square-lattice family
+  cold_ms       - per family, one more fit with the library's plan caches bypassed
+  roofline.traffic of this run - two child runs of this script under rocprofv3 --pmc (--no-live-pmc: the committed profile's)
+  host_arrays   - numpy / scipy in, numpy out (--no-host-arrays skips it)
+  cpu_baseline  - the oracle (CPU restatement of the reference, numpy/scipy + C/OpenMP BCD) timed on this box's host
+                  cores on the headline's own rows (--cpu-sample, default all 1M: ~30 s of CPU; N=1 only; --no-cpu-baseline)
+--family picks the families itself, with or without --full.
 
 Every family record runs --steps timed fits after --warmup untimed ones.  The inputs depend only on the arguments (seeded
 generators), so runs with the same arguments fit the same data.  --dump-outputs DIR (one GPU) writes, after the timed steps,
 what the last timed fit of each family returned to its caller (beta_, proportions_, gene_idx_, info_) as DIR/<family>_<name>.npy
 in float64, at most DUMP_BYTES in all: beta_ and proportions_ on a fixed, seeded sample of rows (DIR/sample_rows.npy) when the
-whole arrays would not fit.
+whole arrays would not fit.  Without --family it covers every family, --full or not, so a plain run with --dump-outputs fits
+them all (their records go into the line as well).
 """
 import argparse
 import json
@@ -49,7 +59,11 @@ def parse():
     ap.add_argument("--genes", type=int, default=2000)
     ap.add_argument("--types", type=int, default=30)
     ap.add_argument("--sketch-dim", type=int, default=512)
-    ap.add_argument("--family", choices=["gaussian", "counts", "both", "sparse", "lattice", "all"], default="all")
+    ap.add_argument("--family", choices=["gaussian", "counts", "both", "sparse", "lattice", "all"], default=None,
+                    help="families to run (default: gaussian alone in a plain run; all with --full or --dump-outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every other measurement: all families (count-like, Y float64, CSR, lattice), "
+                         "cold fits, live PMC traffic, host_arrays and the CPU baseline")
     ap.add_argument("--sparse-genes", type=int, default=20000, help="columns of the CSR family's matrix (HVG picks ~--genes of them)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                     help="N > 1: strong = the --spots job sharded over N ranks (configs[3]); weak = N x --spots")
@@ -82,6 +96,8 @@ def parse():
         ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.dump_outputs and (a.gpus > 1 or a.virtual_ranks > 0 or os.environ.get("FDX_BENCH_FORCE_DIST")):
         ap.error("--dump-outputs covers the one-GPU families only (not --gpus N > 1, --virtual-ranks or FDX_BENCH_FORCE_DIST)")
+    if a.family is None:
+        a.family = "all" if (a.full or a.dump_outputs) else "gaussian"
     return a
 
 
@@ -218,7 +234,7 @@ def live_pmc_traffic(a, timeout_s=240):
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(work, ctr)
             cmd = [exe, "--pmc", ctr, "--kernel-trace", "--output-format", "csv", "-d", out, "--", sys.executable, os.path.abspath(__file__),
-                   "--family", a.family, "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-host-arrays", "--no-live-pmc",
+                   "--family", a.family, "--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-host-arrays", "--no-live-pmc",
                    "--spots", str(a.spots), "--genes", str(a.genes), "--types", str(a.types), "--sketch-dim", str(a.sketch_dim),
                    "--sparse-genes", str(a.sparse_genes)]
             try:
@@ -333,7 +349,7 @@ def write_dump(path, rows, dumped):
         np.save(os.path.join(path, name + ".npy"), v)
 
 
-def run_family(torch, model_kw, Y, X, coords, steps, warmup, barrier):
+def run_family(torch, model_kw, Y, X, coords, steps, warmup, barrier, cold=False):
     from flashdeconv_amd import FlashDeconv
     model = FlashDeconv(**model_kw)
     for _ in range(warmup):
@@ -356,8 +372,10 @@ def run_family(torch, model_kw, Y, X, coords, steps, warmup, barrier):
     for k in stage:
         stage[k] /= steps
     stage["step_ms_min_max"] = [round(min(walls), 3), round(max(walls), 3)]
-    # cold fit: the same call with the library's content-keyed caches (sketch plans, tile schedules) bypassed - what a user who
-    # calls fit_transform ONCE pays (the GPU context itself is warm); outside the timed region
+    if not cold:
+        return model, dt, stage
+    # cold fit (--full): the same call with the library's content-keyed caches (sketch plans, tile schedules) bypassed - what a
+    # user who calls fit_transform ONCE pays (the GPU context itself is warm); outside the timed region
     from flashdeconv_amd import _lib as _fdx_lib
     os.environ["FDX_NO_PLAN_CACHE"] = "1"
     _fdx_lib.env_reload()                          # (the library caches its switches: no fit is running here)
@@ -379,6 +397,11 @@ def stage_record(stage, ms_per_step):
     out = {k: round(v, 3) for k, v in stage.items() if k not in ("cold_ms", "step_ms_min_max")}
     out["unaccounted_ms"] = round(ms_per_step - (stage["host_pre_ms"] + stage["span_ms"] + stage["host_post_ms"]), 3)
     return out
+
+
+def cold_record(stage):
+    """{"cold_ms": ...} of a family's stage times (or record) when run_family timed its cold fit (--full), else {}."""
+    return {"cold_ms": round(stage["cold_ms"], 3)} if "cold_ms" in stage else {}
 
 
 def host_cpu_budget():
@@ -715,13 +738,13 @@ def main():
             import warnings
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore")
-                model, dt, stage = run_family(torch, kw, Y, X, coords, lsteps, a.warmup, barrier)
+                model, dt, stage = run_family(torch, kw, Y, X, coords, lsteps, a.warmup, barrier, cold=a.full)
             if dump_rows is not None:
                 dumped[fam] = fit_outputs(torch, model, dump_rows)
             ms_step = dt / lsteps * 1e3
             results[fam] = {
                 "value": n * lsteps / dt, "unit": "spots/s", "ms_per_step": ms_step, "steps": lsteps, "warmup": a.warmup,
-                "step_ms_min_max": stage.pop("step_ms_min_max"), "cold_ms": round(stage["cold_ms"], 3),
+                "step_ms_min_max": stage.pop("step_ms_min_max"), **cold_record(stage),
                 "workload": f"{n} spots on a {side} x {side} square lattice (every k-th neighbour tied), {G} genes x {K} types, count-like / "
                             f"log_cpm, knn_ties='auto' (default): the reference's cKDTree tie order",
                 "n_iterations": model.info_["n_iterations"], "converged": model.info_["converged"],
@@ -735,7 +758,7 @@ def main():
             Y, X, coords = gen_sparse(torch, n, a.sparse_genes, K, device, seed=0)
             kw = dict(sketch_dim=d, preprocess="log_cpm", n_hvg=G, max_iter=20)
             ssteps = a.steps
-            model, dt, stage = run_family(torch, kw, Y, X, coords, ssteps, a.warmup, barrier)
+            model, dt, stage = run_family(torch, kw, Y, X, coords, ssteps, a.warmup, barrier, cold=a.full)
             if dump_rows is not None:
                 dumped[fam] = fit_outputs(torch, model, dump_rows)
             nnz_y = int(Y.values().numel())
@@ -747,7 +770,7 @@ def main():
             ms_step = dt / ssteps * 1e3
             results[fam] = {
                 "value": n * ssteps / dt, "unit": "spots/s", "ms_per_step": ms_step, "steps": ssteps, "warmup": a.warmup,
-                "step_ms_min_max": stage.pop("step_ms_min_max"), "cold_ms": round(stage["cold_ms"], 3),
+                "step_ms_min_max": stage.pop("step_ms_min_max"), **cold_record(stage),
                 "workload": f"CSR input: {n} spots x {a.sparse_genes} genes, {nnz_y} stored entries ({nnz_y / n / a.sparse_genes:.3f} dense, "
                             f"{nnz_y / n:.0f} per spot), float32 values + int32 columns in HBM; HVG+markers select "
                             f"{len(model.gene_idx_)} genes, log_cpm, max_iter 20 (the solve is not the subject here)",
@@ -771,7 +794,7 @@ def main():
             Y, X, coords = gen_counts(torch, n, G, K, device, seed=0)
             kw = dict(sketch_dim=d, preprocess="log_cpm", n_hvg=G)
         steps = a.steps
-        model, dt, stage = run_family(torch, kw, Y, X, coords, steps, a.warmup, barrier)
+        model, dt, stage = run_family(torch, kw, Y, X, coords, steps, a.warmup, barrier, cold=a.full)
         if dump_rows is not None:
             dumped[fam] = fit_outputs(torch, model, dump_rows)
         T = model.info_["n_iterations"]
@@ -794,7 +817,7 @@ def main():
         ach = bytes_launch / (ms_launch * 1e-3) / 1e9
         results[fam] = {
             "value": n * steps / dt, "ms_per_step": dt / steps * 1e3, "step_ms_min_max": stage.pop("step_ms_min_max"),
-            "cold_ms": round(stage["cold_ms"], 3), "n_iterations": T,
+            **cold_record(stage), "n_iterations": T,
             "converged": model.info_["converged"], "stage_ms": stage_record(stage, dt / steps * 1e3),
             "roofline": {"bound": "hbm", "kernel": kname, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": pmc_traffic(kname, (n, G, K, d)),
@@ -806,13 +829,13 @@ def main():
         if fam == "gaussian" and a.config == 3 and a.family == "all":
             # the same job with Y stored float64 in HBM - the reference's own dtype (core/deconv.py:229): twice the one-off read
             Y64 = Y.double()
-            m64, dt64, st64 = run_family(torch, kw, Y64, X, coords, a.steps, a.warmup, barrier)
+            m64, dt64, st64 = run_family(torch, kw, Y64, X, coords, a.steps, a.warmup, barrier, cold=a.full)
             if dump_rows is not None:
                 dumped["gaussian_y_f64"] = fit_outputs(torch, m64, dump_rows)
             ms64 = dt64 / a.steps * 1e3
             g64 = n * G * 8 / (st64["sketch_ms"] * 1e-3) / 1e9
             y_f64 = {"value": n / (ms64 * 1e-3), "unit": "spots/s", "ms_per_step": ms64, "steps": a.steps,
-                     "step_ms_min_max": st64.pop("step_ms_min_max"), "cold_ms": round(st64["cold_ms"], 3),
+                     "step_ms_min_max": st64.pop("step_ms_min_max"), **cold_record(st64),
                      "n_iterations": m64.info_["n_iterations"], "converged": m64.info_["converged"], "workload": "same job, Y float64 in HBM (16 GB)",
                      "roofline": {"bound": "hbm", "kernel": "fdx::tile_sketch_kernel<double, ...>", "achieved": round(g64, 1), "peak": HBM_PEAK_GBS,
                                   "unit": "GB/s", "frac": round(g64 / HBM_PEAK_GBS, 4), "traffic": None,
@@ -820,7 +843,7 @@ def main():
                      "stage_ms": stage_record(st64, ms64)}
             del Y64, m64
             torch.cuda.empty_cache()
-        if fam == "gaussian" and not a.no_cpu_baseline and a.config == 3:
+        if fam == "gaussian" and a.full and not a.no_cpu_baseline and a.config == 3:
             # the CPU baseline runs on these very rows, at the end (outside every timed region): they are generated again there
             # from the same seed - an 8 GB host copy held through the other families' timed steps is host memory the kernel may
             # compact or migrate under them
@@ -843,12 +866,12 @@ def main():
         "config": {"workload": f"{n} spots x {G} genes x {K} types, sketch_dim {d}, k_neighbors 6, "
                                f"{'gaussian/raw' if main_fam == 'gaussian' else 'count-like/log_cpm'} family, Y float32 in HBM, "
                                f"tol 1e-4, max_iter 100", "n_iterations": r["n_iterations"], "converged": r["converged"]},
-        "roofline": r["roofline"], "stage_ms": r["stage_ms"], "cold_ms": r["cold_ms"], "step_ms_min_max": r["step_ms_min_max"],
+        "roofline": r["roofline"], "stage_ms": r["stage_ms"], **cold_record(r), "step_ms_min_max": r["step_ms_min_max"],
     }
     if "counts" in results and main_fam != "counts":
         c = results["counts"]
         line["count_like"] = {"value": c["value"], "unit": "spots/s", "ms_per_step": c["ms_per_step"], "steps": c["steps"],
-                              "step_ms_min_max": c["step_ms_min_max"], "cold_ms": c["cold_ms"],
+                              "step_ms_min_max": c["step_ms_min_max"], **cold_record(c),
                               "n_iterations": c["n_iterations"], "converged": c["converged"], "roofline": c["roofline"],
                               "stage_ms": c["stage_ms"], "workload": "same shape, count-like / log_cpm family (runs max_iter)"}
     if y_f64 is not None:
@@ -857,13 +880,13 @@ def main():
         line["sparse_csr"] = results["sparse"]
     if "lattice" in results:
         line["lattice"] = results["lattice"]
-    if not a.no_live_pmc and a.config == 3:
+    if a.full and not a.no_live_pmc and a.config == 3:
         live = live_pmc_traffic(a)
         apply_live_traffic(line.get("roofline"), live)
         for key in ("count_like", "sparse_csr"):
             if key in line:
                 apply_live_traffic(line[key].get("roofline"), live)
-    if not a.no_host_arrays and a.config == 3 and a.family == "all":
+    if a.full and not a.no_host_arrays and a.config == 3 and a.family == "all":
         line["host_arrays"] = host_arrays_record(torch, n, G, K, d, a.sparse_genes, device)
     if cpu_inputs is not None:
         from flashdeconv_amd import _lib as _fdx_lib

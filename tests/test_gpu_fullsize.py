@@ -298,3 +298,48 @@ def test_bench_inputs_repeat_and_dump_outputs_of_the_timed_fits(tmp_path, monkey
         assert info[0] == rec["n_iterations"] and info[1] == float(rec["converged"]), fam
         assert files[f"{fam}_gene_idx.npy"].ndim == 1
     assert set(files) == {"sample_rows.npy"} | {f"{f}_{k}.npy" for f in recs for k in ("beta", "proportions", "info", "gene_idx")}
+
+
+def test_bench_plain_run_times_the_headline_alone_and_full_adds_the_rest(monkeypatch, capsys):
+    """A plain run fits the gaussian/raw family alone - one model, exactly --warmup + --steps fits - and starts no CPU baseline,
+    host_arrays record or PMC child runs; its line carries the contract keys and nothing of another family.  --full at the same
+    size: every family's record, one cold fit per family, and the three extra measurements (stubbed here: they are the slow part)."""
+    import json
+    sys.path.insert(0, ROOT)
+    import bench
+    from flashdeconv_amd import FlashDeconv
+    fits, models, called = {}, [], []
+    fit0 = FlashDeconv.fit
+
+    def counting_fit(self, *args, **kwargs):
+        if id(self) not in fits:
+            models.append(self)                  # kept alive so that ids stay unique
+        fits[id(self)] = fits.get(id(self), 0) + 1
+        return fit0(self, *args, **kwargs)
+
+    monkeypatch.setattr(FlashDeconv, "fit", counting_fit)
+    for name, stub in (("cpu_baseline", {"value": 1.0}), ("host_arrays_record", {}), ("live_pmc_traffic", {})):
+        monkeypatch.setattr(bench, name, lambda *a, _name=name, _stub=stub, **k: called.append(_name) or _stub)
+    small = ["--spots", "20000", "--genes", "300", "--types", "8", "--sketch-dim", "64", "--sparse-genes", "2000",
+             "--steps", "3", "--warmup", "1"]
+
+    def run(extra):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + small + extra)
+        bench.main()
+        return json.loads([ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")][-1])
+
+    line = run([])
+    assert list(fits.values()) == [4] and called == [], (fits, called)
+    assert line["metric"] == bench.METRIC and line["unit"] == "spots/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["config"]["n_iterations"] >= 1 and line["roofline"]["ms_per_launch"] > 0
+    assert not set(line) & {"count_like", "y_f64", "sparse_csr", "lattice", "cold_ms", "host_arrays", "cpu_baseline"}, sorted(line)
+    fits.clear()
+    models.clear()
+    line = run(["--full"])
+    assert sorted(called) == ["cpu_baseline", "host_arrays_record", "live_pmc_traffic"], called
+    # five families (gaussian, its float64-Y twin, counts, sparse, lattice): 1 warm-up + 3 timed fits each, then one cold fit each
+    assert sorted(fits.values()) == [1] * 5 + [4] * 5, fits
+    recs = [line, line["y_f64"], line["count_like"], line["sparse_csr"], line["lattice"]]
+    assert all(r["cold_ms"] > 0 and r["steps"] == 3 for r in recs)
+    assert line["cpu_baseline"] == {"value": 1.0} and line["host_arrays"] == {}

@@ -318,6 +318,18 @@ def test_bench_rejects_steps_it_cannot_time_and_dumps_it_cannot_write():
         assert out.returncode == 2 and ("--steps" in out.stderr or "--dump-outputs" in out.stderr), (args, out.stderr)
 
 
+def test_bench_plain_run_picks_the_headline_family_alone(monkeypatch):
+    """A plain `bench.py` run fits the gaussian/raw family alone; --full (every other measurement) and --dump-outputs (files of
+    every family) take all families; an explicit --family holds either way."""
+    import sys
+    import bench
+    for args, family, full in (([], "gaussian", False), (["--full"], "all", True), (["--dump-outputs", "d"], "all", False),
+                               (["--family", "counts"], "counts", False), (["--full", "--family", "sparse"], "sparse", True)):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "2", "--warmup", "1"] + args)
+        a = bench.parse()
+        assert (a.family, a.full, a.steps, a.warmup) == (family, full, 2, 1), args
+
+
 def test_bench_dump_sample_is_fixed_and_within_budget():
     """--dump-outputs: the rows written of beta_ / proportions_ - a seeded sample that is the same from run to run, and with the
     small arrays every family writes stays within bench.DUMP_BYTES; all rows when they fit."""

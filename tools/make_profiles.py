@@ -26,7 +26,7 @@ bench_line = open(os.path.join(src, "bench_trace.json")).read().strip().split("\
 with open(os.path.join(dst, f"{tag}_kernel_stats.md"), "w") as f:
     f.write(f"# {tag} - rocprofv3 kernel stats of the bench command\n\n")
     f.write("Command on the MI355X box: `rocprofv3 --kernel-trace --stats --output-format csv -d ... -- python3 bench.py --steps 3 "
-            f"--warmup 1 --no-cpu-baseline{' ' + extra if extra else ''}` (tools/profile_round.sh).\n\n")
+            f"--warmup 1 --full --no-cpu-baseline{' ' + extra if extra else ''}` (tools/profile_round.sh).\n\n")
     if extra:
         f.write(f"Workload: `bench.py {extra}` (see the bench line below).  torch kernels (at::, Cijk_) are the synthetic data "
                 "generators, outside the timed region.\n\n")
@@ -72,7 +72,7 @@ json.dump({"note": "per-launch means over non no-op launches; hbm_bytes_correcte
 with open(os.path.join(dst, f"{tag}_pmc_traffic.md"), "w") as f:
     f.write(f"# {tag} - HBM traffic per launch from PMC counters (FETCH_SIZE, WRITE_SIZE)\n\n")
     f.write("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in two separate passes of `python3 bench.py --steps 1 --warmup 0 "
-            f"--no-cpu-baseline {extra if extra else '--family all'}` (tools/profile_round.sh); per-launch means over the real (non no-op) launches; "
+            f"--full --no-cpu-baseline {extra if extra else '--family all'}` (tools/profile_round.sh); per-launch means over the real (non no-op) launches; "
             "hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024: on gfx950 FETCH_SIZE reports half the bytes of a wide coalesced read "
             "(MI355X_MICROARCH.md, HBM section).\n\n")
     f.write("| kernel | launches | 2 x FETCH_SIZE (MB) | WRITE_SIZE (MB) | HBM bytes per launch (MB) |\n|---|---|---|---|---|\n")

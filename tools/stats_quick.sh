@@ -3,8 +3,9 @@
 tag=$1; shift
 out=/root/repo/gpurun_out/${tag}
 rm -rf "$out"; mkdir -p "$out"
+bench="$(cd "$(dirname "$0")/.." && pwd)/bench.py"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python3 /root/repo/bench.py --no-cpu-baseline "$@" > "$out/bench.json" 2> "$out/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python3 "$bench" --full --no-cpu-baseline "$@" > "$out/bench.json" 2> "$out/bench.err"
 f=$(find "$out" -name "*kernel_stats.csv" | head -1)
 python3 - "$f" <<'PY' > "$out/top.txt"
 import csv,sys
