@@ -301,10 +301,8 @@ int fdx_bcd_solve(const fdx_graph* g, const double* Y_sketch, const double* X_sk
     FDX_REQUIRE(d > 0, "fdx_bcd_solve: sketch_dim must be positive");
     FDX_REQUIRE(Y_sketch && X_sketch && beta_out, "fdx_bcd_solve: null array");
     hipStream_t st = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    FDX_HIP(hipEventCreate(&e0));
-    FDX_HIP(hipEventCreate(&e1));
-    FDX_HIP(hipEventRecord(e0, st));
+    Event e0(true), e1(true);
+    FDX_TRY(e0.record(st));
 
     const long long ld = round_up(n + 1, 64);
     DevBuf dY, dX, dH, dG, dB0, dB1, dPart, dSum, dOut;
@@ -331,9 +329,7 @@ int fdx_bcd_solve(const fdx_graph* g, const double* Y_sketch, const double* X_sk
     FDX_TRY(copy_d2h(G.data(), dG.p, G.size() * sizeof(double), st));
     FDX_TRY(copy_d2h(&YtY, dSum.p, sizeof(double), st));
     FDX_HIP(hipStreamSynchronize(st));
-    double diag_mean = 0.0;  // rho <- rho * mean(diag XtX)   (solver.py:359-360)
-    for (int k = 0; k < K; ++k) diag_mean += G[(size_t)k * K + k];
-    diag_mean /= (double)K;
+    const double diag_mean = xtx_diag_mean(G.data(), K);  // rho <- rho * mean(diag XtX)   (solver.py:359-360)
 
     if (KP != K) {
         FDX_TRY(dGp.alloc((size_t)KP * KP * sizeof(double)));
@@ -348,12 +344,10 @@ int fdx_bcd_solve(const fdx_graph* g, const double* Y_sketch, const double* X_sk
     FDX_TRY(launch_normalize_export(p.beta[r.result_buffer], ld, g->identity_order ? nullptr : g->perm.as<int>(), (int)n,
                                     g->n_slices, K, dOut.as<double>(), nullptr, st));
     FDX_TRY(copy_d2h(beta_out, dOut.p, (size_t)n * K * sizeof(double), st));
-    FDX_HIP(hipEventRecord(e1, st));
+    FDX_TRY(e1.record(st));
     FDX_HIP(hipStreamSynchronize(st));
     float ms = 0.f;
-    FDX_HIP(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    FDX_HIP(hipEventElapsedTime(&ms, e0.e, e1.e));
     info->converged = r.converged;
     info->n_iterations = r.n_iterations;
     info->final_objective = r.final_objective;
@@ -423,8 +417,6 @@ extern "C" int fdx_objective(const fdx_graph* g, const double* beta, const doubl
     FDX_TRY(copy_h2d(dB.p, bt.data(), bt.size() * sizeof(double), st));
     FDX_TRY(copy_h2d(dH.p, ht.data(), ht.size() * sizeof(double), st));
     FDX_TRY(copy_h2d(dG.p, XtX, (size_t)K * K * sizeof(double), st));
-    if (K <= FDX_MAX_K_FAST || true)
-        FDX_TRY(solver_objective(*g, dB.as<double>(), ld, dH.as<double>(), ld, dG.as<double>(), K, YtY, lambda, rho, dPart.as<double>(),
-                                 dOut.as<double>(), obj_out, st));
-    return 0;
+    return solver_objective(*g, dB.as<double>(), ld, dH.as<double>(), ld, dG.as<double>(), K, YtY, lambda, rho, dPart.as<double>(),
+                            dOut.as<double>(), obj_out, st);
 }

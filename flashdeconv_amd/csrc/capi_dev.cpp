@@ -43,13 +43,9 @@ int fdx_side_stream(void** stream_out) {
 }
 
 int fdx_stream_wait_stream(void* waiter, void* producer) {
-    hipEvent_t ev = nullptr;
-    FDX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    hipError_t e = hipEventRecord(ev, (hipStream_t)producer);
-    if (e == hipSuccess) e = hipStreamWaitEvent((hipStream_t)waiter, ev, 0);
-    (void)hipEventDestroy(ev);                      // released when the wait has been satisfied
-    if (e != hipSuccess) return fail(FDX_ERR_HIP, hipGetErrorString(e));
-    return 0;
+    Event ev;                                       // released once the wait has consumed it
+    FDX_TRY(ev.record((hipStream_t)producer));
+    return ev.wait_on((hipStream_t)waiter);
 }
 
 int fdx_graph_build_radius_rows_dev(const double* coords_dev, int64_t n, int32_t dim, double radius, int64_t lo, int64_t hi,
@@ -249,102 +245,15 @@ int fdx_prepare_dev(const void* Y_dev, int32_t y_dtype, int64_t n, int32_t G, in
     FDX_TRY(prepare_queue(&job, Y_dev, y_dtype, n, G, ldy, row_map_dev, X, K, bucket, weight_y, weight_x, d, mode_y_in, mode_x,
                           H_out_dev, ldh, XtX_out_host, st));
     // the caller's XtX buffer belongs to the caller's stream: filled there (the stream already waits for the X side)
-    FDX_HIP(hipMemcpyAsync(XtX_out_dev, job.dG.p, (size_t)K * K * sizeof(double), hipMemcpyDeviceToDevice, st));
+    FDX_HIP(hipMemcpyAsync(XtX_out_dev, job.x.dG.p, (size_t)K * K * sizeof(double), hipMemcpyDeviceToDevice, st));
     double yty = 0.0;
-    if (n > 0 && job.evSum) FDX_HIP(hipStreamWaitEvent(st, job.evSum, 0));
+    if (n > 0 && job.evSum) FDX_TRY(job.evSum.wait_on(st));
     if (n > 0) FDX_HIP(hipMemcpyAsync(&yty, job.dSum.p, sizeof(double), hipMemcpyDeviceToHost, st));
     FDX_HIP(hipStreamSynchronize(st));
     if (job.side) FDX_HIP(hipStreamSynchronize(job.side));
     if (YtY_partial_out) *YtY_partial_out = yty;
     return 0;
 }
-
-}  // extern "C"
-
-namespace fdx {
-int prepare_queue(PrepareJob* job, const void* Y_dev, int y_dtype, long long n, int G, long long ldy, const int* row_map_dev,
-                  const double* X, int K, const int* bucket, const double* weight_y, const double* weight_x, int d, int mode_y_in,
-                  int mode_x, double* H_out_dev, long long ldh, double* XtX_host, hipStream_t st, const double* X_dev) {
-    const int32_t mode_y = mode_y_in & 0xff;
-    TileF64Math f64_math((mode_y_in & FDX_PRE_F64_MATH) != 0);
-    FDX_REQUIRE(y_dtype == FDX_F32 || y_dtype == FDX_F64, "fdx_prepare_dev: Y dtype must be FDX_F32 or FDX_F64");
-    FDX_REQUIRE(n >= 0 && G > 0 && K > 0 && d > 0, "fdx_prepare_dev: bad shape");
-    FDX_REQUIRE(X && bucket && weight_y && weight_x && H_out_dev, "fdx_prepare_dev: null array");
-    FDX_REQUIRE(ldh >= n && ldy >= G, "fdx_prepare_dev: leading dimension too small");
-    // The X side (upload of the signatures - a pageable copy: the host waits for it -, X_sketch, XtX and its copy to the host) runs
-    // on the library's side stream: queued on the caller's stream behind a shard plan that is still executing, the upload made
-    // the host wait for the whole plan and the launches behind it arrived on an idle device (70 us of a 125k-spot rank's 1.6 ms).
-    // The schedules of an Omega are built once per content and device (sketch_plan.cpp: the cache the single-GPU fit uses).
-    hipStream_t side = fdx::env("FDX_NO_SIDE_STREAM") ? nullptr : library_side_stream();
-    if (side == st) side = nullptr;
-    job->side = side;
-    const hipStream_t xs = side ? side : st;
-    {
-        PoolStream pool_xs(xs);
-        // a new Omega's tables are uploaded on xs as well (the caller's stream waits for the event below before the sketch)
-        FDX_TRY(sketch_plan_cached(bucket, weight_y, G, d, xs, &job->plan_y));
-        if (weight_x == weight_y) job->plan_x = job->plan_y;
-        else FDX_TRY(sketch_plan_cached(bucket, weight_x, G, d, xs, &job->plan_x));
-        FDX_TRY(job->dXs.alloc((size_t)K * d * sizeof(double)));
-        FDX_TRY(job->dG.alloc((size_t)K * K * sizeof(double)));
-        const void* Xd = X_dev;                                            // already there (the leverage job's copy, complete)
-        if (!Xd) {
-            FDX_TRY(job->dX.alloc((size_t)K * G * sizeof(double)));
-            FDX_TRY(copy_h2d(job->dX.p, X, (size_t)K * G * sizeof(double), xs));
-            Xd = job->dX.p;
-        }
-        FDX_TRY(launch_sketch_rows(Xd, FDX_F64, G, nullptr, K, G, d, mode_x, job->plan_x->dev(), job->dXs.as<double>(), d, nullptr, xs));
-        FDX_TRY(launch_xyt(job->dXs.as<double>(), job->dXs.as<double>(), d, K, d, K, job->dG.as<double>(), K, nullptr, xs));
-        if (XtX_host)
-            FDX_HIP(hipMemcpyAsync(XtX_host, job->dG.p, (size_t)K * K * sizeof(double), hipMemcpyDeviceToHost, xs));
-        FDX_HIP(hipEventCreateWithFlags(&job->evX, hipEventDisableTiming));
-        FDX_HIP(hipEventRecord(job->evX, xs));
-        if (side) FDX_HIP(hipStreamWaitEvent(st, job->evX, 0));
-    }
-    SketchPlan& plan_y = *job->plan_y;
-    if (n > 0) {
-        FDX_REQUIRE(Y_dev != nullptr, "fdx_prepare_dev: null Y");
-        const long long chunk = std::min<long long>(n, 1LL << 18);
-        FDX_TRY(job->dRowSq.alloc((size_t)n * sizeof(double)));
-        FDX_TRY(job->dSum.alloc(sizeof(double)));
-        // same choice as the single-GPU fit (fit.cpp): shards start on multiples of 256, so the fused kernel's groups of 16
-        // spots coincide with those of an unsharded run and H keeps the same bits
-        const bool fused = fused_sketch_contract_ok(y_dtype, ldy, Y_dev, G, d, K, mode_y, plan_y.dev());
-        if (fused)
-            FDX_TRY(launch_sketch_contract(Y_dev, y_dtype, ldy, row_map_dev, n, G, d, mode_y, plan_y.dev(), job->dXs.as<double>(), K,
-                                           H_out_dev, ldh, job->dRowSq.as<double>(), st));
-        else
-            FDX_TRY(job->dYs.alloc((size_t)chunk * d * sizeof(double)));
-        for (long long r0 = 0; r0 < n && !fused; r0 += chunk) {
-            const long long nr = std::min(chunk, n - r0);
-            const unsigned char* ybase = static_cast<const unsigned char*>(Y_dev);
-            if (!row_map_dev) ybase += (size_t)r0 * (size_t)ldy * (y_dtype == FDX_F32 ? 4 : 8);
-            FDX_TRY(launch_sketch_rows(ybase, y_dtype, ldy, row_map_dev ? row_map_dev + r0 : nullptr, nr, G, d, mode_y,
-                                       plan_y.dev(), job->dYs.as<double>(), d, job->dRowSq.as<double>() + r0, st));
-            FDX_TRY(launch_xyt(job->dXs.as<double>(), job->dYs.as<double>(), d, nr, d, K, H_out_dev + r0, ldh, nullptr, st));
-        }
-        // the shard's partial YtY only enters the objective: its reduction goes to the side stream (behind the sketch, beside the
-        // first sweep) instead of standing between the sketch and the sweeps
-        hipStream_t ys = side ? side : st;
-        if (ys != st) {
-            hipEvent_t evSk = nullptr;
-            FDX_HIP(hipEventCreateWithFlags(&evSk, hipEventDisableTiming));
-            const hipError_t e1 = hipEventRecord(evSk, st);
-            const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(ys, evSk, 0) : e1;
-            (void)hipEventDestroy(evSk);                              // released once the wait has consumed it
-            FDX_HIP(e2);
-        }
-        FDX_TRY(launch_sum_partials(job->dRowSq.as<double>(), n, job->dSum.as<double>(), 1, 1, ys));
-        if (ys != st) {
-            FDX_HIP(hipEventCreateWithFlags(&job->evSum, hipEventDisableTiming));
-            FDX_HIP(hipEventRecord(job->evSum, ys));
-        }
-    }
-    return 0;
-}
-}  // namespace fdx
-
-extern "C" {
 
 // The same for a CSR shard (core/deconv.py:181-188 sparse log-CPM rule, core/sketching.py:194-199): the own rows stay
 // sparse in HBM; gene_idx selects G of the matrix's columns (NULL = all, in order).
@@ -361,35 +270,21 @@ int fdx_prepare_csr_dev(const fdx_csr_view* Y, const int32_t* gene_idx, int32_t 
     FDX_REQUIRE(ldh >= n, "fdx_prepare_csr_dev: leading dimension too small");
     hipStream_t st = (hipStream_t)stream;
     PoolStream pool_stream(st);
-    const int G_all = Y->G;
-    const bool csr_fused = csr_contract_ok(d, K, (G_all + 31) / 32);       // the same choice as fit_impl: sharded = unsharded bits
-    CsrSelection sel;
-    FDX_TRY(sel.build(gene_idx, G, G_all, bucket, weight_y, d, csr_fused, st, "fdx_prepare_csr_dev"));
-    DevBuf dX, dXs, dYs, dRowSq, dSum;
-    std::shared_ptr<SketchPlan> plan_x;
-    FDX_TRY(sketch_plan_cached(bucket, weight_x, G, d, st, &plan_x));
-    FDX_TRY(dX.alloc((size_t)K * G * sizeof(double)));
-    FDX_TRY(dXs.alloc((size_t)K * d * sizeof(double)));
-    FDX_TRY(copy_h2d(dX.p, X, (size_t)K * G * sizeof(double), st));
-    FDX_TRY(launch_sketch_rows(dX.p, FDX_F64, G, nullptr, K, G, d, mode_x, plan_x->dev(), dXs.as<double>(), d, nullptr, st));
-    FDX_TRY(launch_xyt(dXs.as<double>(), dXs.as<double>(), d, K, d, K, XtX_out_dev, K, nullptr, st));
+    YSource ysrc;
+    ysrc.csr = Y;
+    ysrc.gene_idx = gene_idx;
+    YTables tables;
+    XSide x;
+    RowsToH rows;
+    DevBuf dSum;
+    // everything on the caller's stream; XtX straight into the caller's buffer
+    FDX_TRY(tables.build(ysrc, G, d, K, bucket, weight_y, st, "fdx_prepare_csr_dev"));
+    FDX_TRY(queue_x_side(&x, X, nullptr, K, K, G, d, mode_x, bucket, weight_x, XtX_out_dev, nullptr, nullptr, st));
     double yty = 0.0;
     if (n > 0) {
-        const long long chunk = std::min<long long>(n, 1LL << 18);
-        if (!csr_fused) FDX_TRY(dYs.alloc((size_t)chunk * d * sizeof(double)));
-        FDX_TRY(dRowSq.alloc((size_t)n * sizeof(double)));
         FDX_TRY(dSum.alloc(sizeof(double)));
-        if (csr_fused)
-            FDX_TRY(launch_sketch_csr_contract((const long long*)Y->indptr, Y->indices, Y->data, Y->dtype, nullptr, n, d, mode_y, sel,
-                                               dXs.as<double>(), K, H_out_dev, ldh, dRowSq.as<double>(), st));
-        for (long long r0 = 0; r0 < n && !csr_fused; r0 += chunk) {
-            const long long nr = std::min(chunk, n - r0);
-            FDX_TRY(launch_sketch_csr((const long long*)Y->indptr, Y->indices, Y->data, Y->dtype, nullptr, r0, nr, d, mode_y, sel.slots.p,
-                                      sel.bits.as<unsigned>(), sel.sel_words, dYs.as<double>(), d, dRowSq.as<double>() + r0, st));
-            FDX_TRY(launch_xyt(dXs.as<double>(), dYs.as<double>(), d, nr, d, K, H_out_dev + r0, ldh, nullptr, st));
-        }
-        FDX_TRY(launch_sum_partials(dRowSq.as<double>(), n, dSum.as<double>(), 1, 1, st));
-        FDX_HIP(hipMemcpyAsync(&yty, dSum.p, sizeof(double), hipMemcpyDeviceToHost, st));
+        FDX_TRY(queue_rows_to_h(ysrc, tables, n, G, d, K, mode_y, nullptr, x.dXs.as<double>(), H_out_dev, ldh, false, &rows, st));
+        FDX_TRY(queue_yty(rows.dRowSq.as<double>(), n, dSum.as<double>(), &yty, nullptr, st, st));
     }
     if (XtX_out_host)
         FDX_HIP(hipMemcpyAsync(XtX_out_host, XtX_out_dev, (size_t)K * K * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -412,30 +307,17 @@ int fdx_bcd_sweep_dev(const fdx_graph* g, const double* H_dev, int64_t ldh, cons
     FDX_REQUIRE(K >= 1 && (sweep_instantiated(K) || K > FDX_MAX_K_PAD),
                 "fdx_bcd_sweep_dev: K must be in 1..64, fdx_solver_padded_k of 65..96 cell types, or above 96");
     if (g->n == 0) return 0;
-    // above 96 types: the LDS-resident sweep (XtX with its rows padded to 16, prepared per call) or the generic one (per-call
-    // scratch) takes the whole shard in one launch, as in fdx_sharded_solve_padded_dev
+    // above 96 types the whole shard goes in one launch of the LDS-resident or the generic sweep, its scratch prepared per call
     DevBuf scratch;
     size_t scratch_ld = 0;
-    if (!sweep_instantiated(K)) {
+    {
         PoolStream pool_stream((hipStream_t)stream);
-        if (sweep_uses_lds(K)) {
-            FDX_TRY(scratch.alloc(sweep_lds_pad_doubles(K) * sizeof(double)));
-            FDX_TRY(sweep_lds_prepare(XtX_dev, K, scratch.as<double>(), (hipStream_t)stream));
-        } else {
-            scratch_ld = (size_t)g->n_slices * 64;
-            FDX_TRY(scratch.alloc(scratch_ld * 2 * K * sizeof(double)));
-        }
+        FDX_TRY(sweep_scratch_prepare(XtX_dev, K, g->n_slices, &scratch, &scratch_ld, (hipStream_t)stream));
     }
-    BcdSweepArgs a{};
+    BcdSweepArgs a = sweep_args_for_graph(*g, false);   // (this entry does not look at FDX_NO_TILED)
     a.H = H_dev; a.XtX = XtX_dev; a.beta_in = beta_in; a.beta_out = beta_out;
-    a.ell = g->ell.as<int>(); a.slice_off = g->slice_off.as<int>(); a.deg = g->deg.as<int>();
     a.stats = (unsigned long long*)stats_dev; a.rel_change = rel_change_dev;
-    a.lambda = lambda; a.rho = rho_eff; a.tol = tol; a.ldh = (int)ldh; a.ld = (int)ld; a.n = (int)g->n;
-    a.n_slices = g->n_slices; a.K = K; a.it = it;
-    if (g->tiled) {
-        a.tiled = 1; a.ell_local = g->ell_local.as<unsigned short>(); a.tile_halo = g->tile_halo.as<int>();
-        a.tile_hcnt = g->tile_hcnt.as<int>(); a.n_tiles = g->n_tiles; a.halo_max = g->halo_max;
-    }
+    a.lambda = lambda; a.rho = rho_eff; a.tol = tol; a.ldh = (int)ldh; a.ld = (int)ld; a.K = K; a.it = it;
     return launch_bcd_sweep(a, scratch.as<double>(), scratch_ld, (hipStream_t)stream);
 }
 

@@ -18,7 +18,6 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <condition_variable>
 #include <cstdio>
@@ -448,15 +447,7 @@ int fdx_sharded_solve_padded_dev(fdx_comm* c, const fdx_graph* g, const double* 
 // lambda, the iteration loop, objective and export - one call, the device never waiting for the host between its stages
 // (the separate calls cost a 125k-spot rank ~0.35 ms of idle device: 1.25 -> 1.6 ms).  Reference: core/deconv.py:326-398 for the
 // stages, core/solver.py:157-166 for the sharding.
-// FDX_TRACE_HOST=1: host clock at the steps of a shard's fit (stderr)
-static void shard_trace(const char* what) {
-    static const bool on = fdx::env("FDX_TRACE_HOST") != nullptr;
-    if (!on) return;
-    static auto t_prev = std::chrono::steady_clock::now();
-    const auto t = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[fdx-host] +%7.1f us  shard fit: %s\n", std::chrono::duration<double, std::micro>(t - t_prev).count(), what);
-    t_prev = t;
-}
+static void shard_trace(const char* what) { fdx::trace_host("shard fit", what); }
 
 int fdx_shard_fit_dev(fdx_comm* c, const fdx_graph* g, const void* Y_dev, int32_t y_dtype, int64_t n_own, int32_t G, int64_t ldy,
                       const double* X, int32_t K, const int32_t* bucket, const double* weight_y, const double* weight_x,
@@ -497,11 +488,11 @@ int fdx_shard_fit_dev(fdx_comm* c, const fdx_graph* g, const void* Y_dev, int32_
     shard_trace("X side + sketch queued");
     FDX_TRY(graph_shard_join(g));
     shard_trace("rest of the plan queued");
-    const double* XtX_dev = job.dG.as<double>();
+    const double* XtX_dev = job.x.dG.as<double>();
     if (KP != K) {
         PoolStream pool_xs(job.side ? job.side : st);
         FDX_TRY(dGp.alloc((size_t)KP * KP * sizeof(double)));
-        FDX_TRY(solver_pad_square(job.dG.as<double>(), K, dGp.as<double>(), KP, job.side ? job.side : st));
+        FDX_TRY(solver_pad_square(XtX_dev, K, dGp.as<double>(), KP, job.side ? job.side : st));
         if (job.side) {                                                     // behind the first event: the sweeps wait for this one too
             FDX_HIP(hipEventRecord(c->ev_packed, job.side));
             FDX_HIP(hipStreamWaitEvent(st, c->ev_packed, 0));
@@ -553,14 +544,11 @@ int fdx_shard_fit_dev(fdx_comm* c, const fdx_graph* g, const void* Y_dev, int32_
     FDX_REQUIRE(g->send_off.size() == (size_t)W + 1, "fdx_shard_fit_dev: the graph was built for a different number of ranks");
 
     // ---- lambda, scaled rho (host scalars of the sweeps): XtX has long arrived
-    FDX_HIP(hipEventSynchronize(job.evX));
+    FDX_TRY(job.evX.sync());
     shard_trace("XtX on the host");
-    double diag_mean = 0.0;
-    for (int k = 0; k < K; ++k) diag_mean += Gh[(size_t)k * K + k];
-    diag_mean /= (double)K;
-    double lambda = prm->lambda_spatial;
-    if (prm->lambda_auto) lambda = 0.005 * diag_mean / std::max(tot[0] / (double)prm->n_total_spots, 1.0);   // core/spatial.py:181-190
-    const double rho_eff = prm->rho_sparsity * diag_mean;                                                       // core/solver.py:359-360
+    const double diag_mean = xtx_diag_mean(Gh, K);
+    const double lambda = prm->lambda_auto ? auto_lambda(diag_mean, tot[0] / (double)prm->n_total_spots) : prm->lambda_spatial;
+    const double rho_eff = prm->rho_sparsity * diag_mean;
     info->lambda_used = lambda;
     info->rho_effective = rho_eff;
 
@@ -584,7 +572,7 @@ int fdx_shard_fit_dev(fdx_comm* c, const fdx_graph* g, const void* Y_dev, int32_
         FDX_HIP(hipEventRecord(c->ev_halo, c->side));
     }
     FDX_TRY(solver_objective_partials(*g, beta, ld, dH.as<double>(), ldh, XtX_dev, KP, objp.as<double>(), dFin.as<double>(), st));
-    if (job.evSum) FDX_HIP(hipStreamWaitEvent(st, job.evSum, 0));
+    if (job.evSum) FDX_TRY(job.evSum.wait_on(st));
     FDX_HIP(hipMemcpyAsync(dFin.as<double>() + 4, job.dSum.p, sizeof(double), hipMemcpyDeviceToDevice, st));
     FDX_TRY(allreduce(c, dFin.p, 5, false, st));
     FDX_HIP(hipMemcpyAsync(cnt_h, dFin.p, 5 * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -592,7 +580,7 @@ int fdx_shard_fit_dev(fdx_comm* c, const fdx_graph* g, const void* Y_dev, int32_
     FDX_HIP(hipStreamSynchronize(st));
     shard_trace("objective on the host");
     info->YtY = cnt_h[4];
-    info->solve.final_objective = 0.5 * (cnt_h[4] - 2.0 * cnt_h[0] + cnt_h[1]) + 0.5 * lambda * cnt_h[2] + rho_eff * cnt_h[3];   // core/solver.py:272-284
+    info->solve.final_objective = objective_from_sums(cnt_h, cnt_h[4], lambda, rho_eff);
     return 0;
 }
 
@@ -619,24 +607,14 @@ static int sharded_solve_impl(fdx_comm* c, const fdx_graph* g, const double* H_d
     const int total_send = g->send_off.back(), total_recv = g->recv_off.back();
     FDX_TRY(comm_streams(c));
 
-    DevBuf stats, send_buf, recv_buf, soff, roff, sweep_scratch, stat_recv;
+    SweepStats stats;
+    DevBuf send_buf, recv_buf, soff, roff, sweep_scratch, stat_recv;
     size_t scratch_ld = 0;
-    if (sweep_uses_lds(K)) {                          // as in solver_run: XtX with its rows padded to 16 for the LDS-resident sweep
-        FDX_TRY(sweep_scratch.alloc(sweep_lds_pad_doubles(K) * sizeof(double)));
-        FDX_TRY(sweep_lds_prepare(XtX_dev, K, sweep_scratch.as<double>(), (hipStream_t)stream));
-    } else if (!sweep_instantiated(K)) {
-        scratch_ld = (size_t)g->n_slices * 64;
-        FDX_TRY(sweep_scratch.alloc(scratch_ld * 2 * K * sizeof(double)));
-    }
-    const int iters = std::max<int>(max_iter, 1);
-    // the max slots of every iteration and, behind them, the rel_change trace: one block, one fill
-    const size_t stats_bytes = (size_t)iters * 128 * 8;
-    FDX_TRY(stats.alloc(stats_bytes + (size_t)iters * 8));
-    double* const relchg_p = reinterpret_cast<double*>(static_cast<char*>(stats.p) + stats_bytes);
+    FDX_TRY(sweep_scratch_prepare(XtX_dev, K, g->n_slices, &sweep_scratch, &scratch_ld, st));
     FDX_TRY(send_buf.alloc((size_t)std::max(total_send, 1) * K * 8));
     FDX_TRY(recv_buf.alloc((size_t)std::max(total_recv, 1) * K * 8));
     FDX_TRY(stat_recv.alloc((size_t)W * 128 * 8));
-    FDX_HIP(hipMemsetAsync(stats.p, 0, stats.bytes, st));
+    FDX_TRY(stats.init(max_iter, st));
     if (c->loopback) FDX_HIP(hipMemsetAsync(recv_buf.p, 0, recv_buf.bytes, st));   // part of it is never written by the self-copy
     // per-peer offsets of the staging blocks: a graph from the queued shard build (fdx_graph_shard_knn_dev) has them on the device
     const int* soff_p = g->send_off_dev.as<int>();
@@ -655,16 +633,10 @@ static int sharded_solve_impl(fdx_comm* c, const fdx_graph* g, const double* H_d
     FDX_HIP(hipMemsetAsync(beta1_dev, 0, (size_t)K * ld * 8, st));
     if (upload_offsets) FDX_HIP(hipStreamSynchronize(st));                    // the offset vectors are host objects of g
 
-    BcdSweepArgs a{};
-    a.H = H_dev; a.XtX = XtX_dev; a.ell = g->ell.as<int>(); a.slice_off = g->slice_off.as<int>(); a.deg = g->deg.as<int>();
-    a.stats = stats.as<unsigned long long>(); a.rel_change = relchg_p;
-    a.lambda = lambda; a.rho = rho_eff; a.tol = tol; a.ldh = (int)ldh; a.ld = (int)ld; a.n = (int)g->n;
-    a.n_slices = g->n_slices; a.K = K;
-    const bool tiled = g->tiled && !fdx::env("FDX_NO_TILED");
-    if (tiled) {
-        a.tiled = 1; a.ell_local = g->ell_local.as<unsigned short>(); a.tile_halo = g->tile_halo.as<int>();
-        a.tile_hcnt = g->tile_hcnt.as<int>(); a.n_tiles = g->n_tiles; a.halo_max = g->halo_max;
-    }
+    BcdSweepArgs a = sweep_args_for_graph(*g, true);
+    a.H = H_dev; a.XtX = XtX_dev; a.stats = stats.stats; a.rel_change = stats.rel_change;
+    a.lambda = lambda; a.rho = rho_eff; a.tol = tol; a.ldh = (int)ldh; a.ld = (int)ld; a.K = K;
+    const bool tiled = a.tiled != 0;
     a.beta_in = beta0_dev;
     a.beta_out = beta1_dev;
     // boundary-first ordering needs the tiled sweep (tile lists) and somebody to talk to
@@ -717,24 +689,7 @@ static int sharded_solve_impl(fdx_comm* c, const fdx_graph* g, const double* H_d
         a.send_buf = send_buf.as<double>();
     }
 
-    // the trace lands in pinned host memory behind an event; while the host waits for it the first iterations of the NEXT chunk
-    // are already queued (no-ops if this chunk converged: device-side stopping rule), as in solver_run
-    double* rc_host = (double*)pinned_scratch(2, (size_t)iters * sizeof(double));
-    FDX_REQUIRE(rc_host != nullptr, "sharded solve: pinned host buffer");
-    for (int j = 0; j < iters; ++j) rc_host[j] = 0.0;
-    int done = 0, n_iter = 0, chunk = 4;
-    bool converged = false;
-    hipEvent_t ev0[2] = {nullptr, nullptr}, ev1[2] = {nullptr, nullptr}, evCopy = nullptr;
-    struct EvGuard { hipEvent_t* e[5]; ~EvGuard() { for (auto* q : e) if (*q) (void)hipEventDestroy(*q); } } ev_guard{{&ev0[0], &ev0[1], &ev1[0], &ev1[1], &evCopy}};
-    for (int j = 0; j < 2; ++j) {
-        FDX_HIP(hipEventCreate(&ev0[j]));
-        FDX_HIP(hipEventCreate(&ev1[j]));
-    }
-    FDX_HIP(hipEventCreateWithFlags(&evCopy, hipEventDisableTiming));
-    double sweep_ms = 0.0;
     double* beta[2] = {beta0_dev, beta1_dev};
-    // the in-process transport meets at host barriers: nothing is gained by queueing ahead there
-    const int n_ahead = (c->local || fdx::exp_env("FDX_NO_SWEEP_AHEAD")) ? 0 : 2;
     auto iterate = [&](int it, bool last_of_chunk) -> int {
         a.it = it;
         a.beta_in = beta[it & 1];
@@ -786,51 +741,21 @@ static int sharded_solve_impl(fdx_comm* c, const fdx_graph* g, const double* H_d
         if (g->n == 0 && !last_of_chunk) FDX_TRY(launch_bcd_fold_last(a.stats, a.rel_change, it, st));
         return 0;
     };
-    auto run = [&]() -> int {
-        int queued_ahead = 0, ci = 0;
-        while (done < max_iter && !converged) {
-            const int end = std::min<int>(max_iter, done + chunk);
-            const int pair = ci & 1;
-            if (queued_ahead == 0) FDX_HIP(hipEventRecord(ev0[pair], st));
-            for (int it = done + queued_ahead; it < end; ++it) FDX_TRY(iterate(it, it + 1 == end));
-            FDX_TRY(launch_bcd_fold_last(a.stats, a.rel_change, end - 1, st));
-            FDX_HIP(hipEventRecord(ev1[pair], st));
-            FDX_HIP(hipMemcpyAsync(rc_host + done, relchg_p + done, (size_t)(end - done) * 8, hipMemcpyDeviceToHost, st));
-            FDX_HIP(hipEventRecord(evCopy, st));
-            int ahead = 0;
-            if (end < max_iter && n_ahead > 0) {
-                ahead = std::min(n_ahead, max_iter - end);
-                FDX_HIP(hipEventRecord(ev0[pair ^ 1], st));
-                // a rank without rows folds sweep it in iteration it itself unless it is the last of its chunk: these are not
-                for (int it = end; it < end + ahead; ++it) FDX_TRY(iterate(it, false));
-            }
-            FDX_HIP(hipEventSynchronize(evCopy));
-            float ms = 0.f;
-            FDX_HIP(hipEventElapsedTime(&ms, ev0[pair], ev1[pair]));
-            sweep_ms += ms;
-            for (int it = done; it < end; ++it) {
-                n_iter = it + 1;
-                if (rc_host[(size_t)it] < tol) { converged = true; break; }   // solver.py:409-413
-            }
-            done = end;
-            queued_ahead = ahead;
-            chunk = std::max(std::min(ci == 0 ? chunk : chunk * 2, 32), ahead);
-            ++ci;
-        }
-        return 0;
-    };
-    const int rc = run();
+    // the in-process transport meets at host barriers: nothing is gained by queueing ahead there
+    const int n_ahead = (c->local || fdx::exp_env("FDX_NO_SWEEP_AHEAD")) ? 0 : 2;
+    LoopResult loop;
+    const int rc = solver_loop(stats, max_iter, tol, 4, n_ahead, iterate, &loop, st);
     if (rc && c->local) c->local->abort();     // the other thread ranks leave their barriers with an error instead of hanging
     (void)hipStreamSynchronize(st);
     if (c->side) (void)hipStreamSynchronize(c->side);
     if (rc) return rc;
-    info->n_iterations = n_iter;
-    info->converged = converged ? 1 : 0;
-    info->final_change = n_iter > 0 ? rc_host[(size_t)n_iter - 1] : 0.0;
-    info->sweep_ms = sweep_ms;
-    *result_buffer = n_iter & 1;
+    info->n_iterations = loop.n_iter;
+    info->converged = loop.converged ? 1 : 0;
+    info->final_change = loop.n_iter > 0 ? loop.rel_changes[loop.n_iter - 1] : 0.0;
+    info->sweep_ms = loop.sweep_ms;
+    *result_buffer = loop.n_iter & 1;
     if (rel_changes_out)
-        for (int i = 0; i < n_iter; ++i) rel_changes_out[i] = rc_host[(size_t)i];
+        for (int i = 0; i < loop.n_iter; ++i) rel_changes_out[i] = loop.rel_changes[i];
     return 0;
 }
 

@@ -2,6 +2,9 @@
 // is a CPU fallback (the reference has no switches).
 #include "fdx_env.h"
 
+#include <atomic>
+#include <chrono>
+#include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -48,6 +51,13 @@ Switch g_switches[] = {
 constexpr int kSwitches = sizeof(g_switches) / sizeof(g_switches[0]);
 std::once_flag g_once;
 std::mutex g_mu;
+std::atomic<bool> g_trace_host{false};   // FDX_TRACE_HOST as load_all() last saw it: a trace point that is off costs this load, not a walk of the registry
+
+const char* lookup(const char* name) {
+    for (const Switch& s : g_switches)
+        if (std::strcmp(s.name, name) == 0) return s.set ? s.value.c_str() : nullptr;
+    return nullptr;          // not a runtime switch (tests/test_host.py checks the sources against the registry)
+}
 
 void load_all() {
     for (Switch& s : g_switches) {
@@ -55,15 +65,24 @@ void load_all() {
         s.set = v != nullptr;
         s.value = v ? v : "";
     }
+    g_trace_host.store(lookup("FDX_TRACE_HOST") != nullptr, std::memory_order_relaxed);
 }
 
 }  // namespace
 
 const char* env(const char* name) {
     std::call_once(g_once, load_all);
-    for (const Switch& s : g_switches)
-        if (std::strcmp(s.name, name) == 0) return s.set ? s.value.c_str() : nullptr;
-    return nullptr;          // not a runtime switch (tests/test_host.py checks the sources against the registry)
+    return lookup(name);
+}
+
+void trace_host(const char* scope, const char* what) {
+    std::call_once(g_once, load_all);
+    if (!g_trace_host.load(std::memory_order_relaxed)) return;
+    thread_local auto t_prev = std::chrono::steady_clock::now();
+    const auto t = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "[fdx-host] +%7.1f us  %s%s%s\n", std::chrono::duration<double, std::micro>(t - t_prev).count(),
+                 scope ? scope : "", scope ? ": " : "", what);
+    t_prev = t;
 }
 
 void env_reload() {

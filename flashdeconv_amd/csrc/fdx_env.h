@@ -15,6 +15,9 @@ namespace fdx {
 
 const char* env(const char* name);
 void env_reload();
+// FDX_TRACE_HOST=1: host time since this thread's previous traced point (stderr, "scope: what"; scope may be NULL) - which calls
+// the host spends its time in, and whether it keeps ahead of the device
+void trace_host(const char* scope, const char* what);
 
 #ifdef FDX_EXPERIMENT
 inline const char* exp_env(const char* name) { return getenv(name); }

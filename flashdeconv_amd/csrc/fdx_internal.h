@@ -97,6 +97,8 @@ struct DevBuf {
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept { take(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept { take(o); return *this; }
     ~DevBuf() { release(); }
     int alloc(size_t n) {
         release();
@@ -121,6 +123,45 @@ struct DevBuf {
         o.p = nullptr;
         o.bytes = 0;
         o.cap = 0;
+    }
+};
+
+// An owned HIP event: created by its first record() (with timing only when asked for), destroyed with the object.
+struct Event {
+    hipEvent_t e = nullptr;
+    bool timing = false;
+    explicit Event(bool with_timing = false) : timing(with_timing) {}
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    Event(Event&& o) noexcept : e(o.e), timing(o.timing) { o.e = nullptr; }
+    Event& operator=(Event&& o) noexcept {
+        if (this != &o) { reset(); e = o.e; timing = o.timing; o.e = nullptr; }
+        return *this;
+    }
+    ~Event() { reset(); }
+    void reset() {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    explicit operator bool() const { return e != nullptr; }
+    int record(hipStream_t st) {
+        if (!e) FDX_HIP(hipEventCreateWithFlags(&e, timing ? hipEventDefault : hipEventDisableTiming));
+        FDX_HIP(hipEventRecord(e, st));
+        return 0;
+    }
+    int wait_on(hipStream_t st) const {   // st waits for the recorded point
+        FDX_HIP(hipStreamWaitEvent(st, e, 0));
+        return 0;
+    }
+    int sync() const {
+        FDX_HIP(hipEventSynchronize(e));
+        return 0;
+    }
+    // milliseconds from `from` to this event; 0 when one of them was never recorded (both: timing events, completed)
+    float ms_since(hipEvent_t from) const {
+        float t = 0.f;
+        if (e && from) (void)hipEventElapsedTime(&t, from, e);
+        return t;
     }
 };
 

@@ -17,7 +17,6 @@
 //      by original index + unique.
 //   5. sliced ELL (slice = 64 consecutive sorted points = one wavefront of the BCD sweep).
 #include "fdx_env.h"
-#include <chrono>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -1205,15 +1204,7 @@ __global__ __launch_bounds__(256) void tile_ell_kernel(const int* __restrict__ w
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-// FDX_TRACE_HOST=1: host clock at the steps of a graph build (stderr), to see which calls the host spends its time in
-static void trace_host(const char* what) {
-    static const bool on = fdx::env("FDX_TRACE_HOST") != nullptr;
-    if (!on) return;
-    static auto t_prev = std::chrono::steady_clock::now();
-    const auto t = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[fdx-host] +%7.1f us  %s\n", std::chrono::duration<double, std::micro>(t - t_prev).count(), what);
-    t_prev = t;
-}
+static void trace_host(const char* what) { fdx::trace_host(nullptr, what); }   // the steps of a graph build
 
 static int exclusive_scan_int(const int* in, int* out, long long count, hipStream_t st, DevBuf& tmp) {
     size_t bytes = 0;

@@ -1,5 +1,5 @@
-// Queued form of a shard's "prepare" step (capi_dev.cpp): X_sketch / XtX on the library's side stream, sketch -> H of the own
-// rows and the partial ||Y_s||^2 on the caller's stream - nothing waited for.  Internal.
+// The sketch -> H stage (prepare.cpp), one copy for the single-GPU fit (fit.cpp) and for a shard's prepare (capi_dev.cpp, comm.cpp):
+// a sharded run is bit-identical to one GPU because both queue the same kernels through these routines.  Internal.
 #pragma once
 #include <memory>
 
@@ -8,13 +8,63 @@
 
 namespace fdx {
 
+// Where the spot rows come from: a dense (n, G) device matrix, or a CSR matrix over csr->G columns of which gene_idx
+// (host, G entries; NULL = all columns in order) are the selected genes.
+struct YSource {
+    const void* dense = nullptr;
+    int32_t dtype = FDX_F32;
+    int64_t ldy = 0;
+    const fdx_csr_view* csr = nullptr;
+    const int32_t* gene_idx = nullptr;
+    int32_t row_dtype() const { return csr ? csr->dtype : dtype; }
+    const void* id() const { return csr ? (const void*)csr->data : dense; }   // whose rows these are (the carry of a stopped fit)
+};
+
+// The CountSketch of the Y side on the device: the cached plan of a dense source, or a CSR source's column selection (in the form
+// of the fused kernel when that one serves the shape)
+struct YTables {
+    std::shared_ptr<SketchPlan> plan;
+    CsrSelection sel;
+    bool csr_fused = false;
+    int build(const YSource& y, int G, int d, int K, const int32_t* bucket, const double* weight_y, hipStream_t xs, const char* who);
+};
+
+// X side: plan for weight_x (x->plan when the caller has set it: the Y side's plan for equal weights), upload of the signatures
+// unless X_dev has them, X_sketch (K, d), XtX (K, K) into XtX_dev (NULL: x->dG), bordered with zeros to (KP, KP) in x->dGp when
+// KP != K, copied to XtX_host when given, `done` recorded when given - all queued on xs, whose pool stream the buffers get.
+struct XSide {
+    DevBuf dX, dXs, dG, dGp;
+    std::shared_ptr<SketchPlan> plan;
+};
+int queue_x_side(XSide* x, const double* X, const double* X_dev, int K, int KP, int G, int d, int mode_x, const int32_t* bucket,
+                 const double* weight_x, double* XtX_dev, double* XtX_host, Event* done, hipStream_t xs);
+
+// Rows -> H: columns [0, n) of H (K, ldh) = X_sketch . sketch(row)^T and the rows' squared norms, queued on st.  One kernel where
+// the shape has a fused form, else Y_sketch in chunks (dYs) contracted as it is produced.  row_map: optional gather (the fit's
+// spot permutation).  time_chunks: the two-kernel path records events per chunk, WAITS for the stream and fills sketch_ms /
+// gram_ms (the fit's stage timing); without it nothing is waited for.
+struct RowsToH {
+    DevBuf dRowSq, dYs;
+    bool fused = false;
+    double sketch_ms = 0.0, gram_ms = 0.0;
+};
+int queue_rows_to_h(const YSource& y, const YTables& t, long long n, int G, int d, int K, int mode_y, const int* row_map,
+                    const double* Xs, double* H, long long ldh, bool time_chunks, RowsToH* out, hipStream_t st);
+
+// YtY = sum of the rows' squared norms into sum_dev, queued on ys behind the work of st (ys may be st), copied to yty_host and
+// `done` recorded on ys where given
+int queue_yty(const double* row_sq, long long n, double* sum_dev, double* yty_host, Event* done, hipStream_t st, hipStream_t ys);
+
+// Queued form of a dense shard's "prepare" step: X side on the library's side stream, sketch -> H of the own rows on the
+// caller's, the partial ||Y_s||^2 on the side stream again - nothing waited for.
 struct PrepareJob {
-    DevBuf dX, dXs, dG, dYs, dRowSq, dSum;         // dG: XtX (K, K); dSum: the shard's partial YtY (one double, valid behind the caller's stream)
-    std::shared_ptr<SketchPlan> plan_y, plan_x;
+    XSide x;                                       // x.dG: XtX (K, K)
+    YTables y;
+    RowsToH rows;
+    DevBuf dSum;                                   // the shard's partial YtY (one double, valid behind evSum)
     hipStream_t side = nullptr;                    // nullptr: everything on the caller's stream
-    hipEvent_t evX = nullptr;                      // X side done (XtX in dG, and on the host when asked for)
-    hipEvent_t evSum = nullptr;                    // dSum written (on the side stream when there is one: consumers on another stream wait for it)
-    ~PrepareJob() { if (evX) (void)hipEventDestroy(evX); if (evSum) (void)hipEventDestroy(evSum); }
+    Event evX;                                     // X side done (XtX in x.dG, and on the host when asked for)
+    Event evSum;                                   // dSum written (on the side stream when there is one: consumers on another stream wait for it)
 };
 
 // Y_dev: (n, G) rows of this shard in solver order (row_map_dev: optional gather).  XtX_host: pinned or pageable, K*K doubles or

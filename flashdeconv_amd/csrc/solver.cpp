@@ -55,18 +55,45 @@ int solver_pad_square(const double* A, int K, double* B, int KP, hipStream_t st)
     return 0;
 }
 
+BcdSweepArgs sweep_args_for_graph(const fdx_graph& g, bool honour_no_tiled) {
+    BcdSweepArgs a{};
+    a.ell = g.ell.as<int>(); a.slice_off = g.slice_off.as<int>(); a.deg = g.deg.as<int>();
+    a.n = (int)g.n; a.n_slices = g.n_slices;
+    if (g.tiled && !(honour_no_tiled && fdx::env("FDX_NO_TILED"))) {
+        a.tiled = 1; a.ell_local = g.ell_local.as<unsigned short>(); a.tile_halo = g.tile_halo.as<int>();
+        a.tile_hcnt = g.tile_hcnt.as<int>(); a.n_tiles = g.n_tiles; a.halo_max = g.halo_max;
+    }
+    return a;
+}
+
+int sweep_scratch_prepare(const double* XtX, int K, int n_slices, DevBuf* scratch, size_t* scratch_ld, hipStream_t st) {
+    *scratch_ld = 0;
+    if (sweep_uses_lds(K)) {
+        FDX_TRY(scratch->alloc(sweep_lds_pad_doubles(K) * sizeof(double)));
+        FDX_TRY(sweep_lds_prepare(XtX, K, scratch->as<double>(), st));
+    } else if (!sweep_instantiated(K)) {
+        *scratch_ld = (size_t)n_slices * 64;
+        FDX_TRY(scratch->alloc(*scratch_ld * 2 * K * sizeof(double)));
+    }
+    return 0;
+}
+
+double xtx_diag_mean(const double* XtX_host, int K) {
+    double diag_mean = 0.0;
+    for (int k = 0; k < K; ++k) diag_mean += XtX_host[(size_t)k * K + k];
+    return diag_mean / (double)K;
+}
+
+double auto_lambda(double diag_mean, double mean_degree) { return 0.005 * diag_mean / std::max(mean_degree, 1.0); }
+
 int solver_objective_partials(const fdx_graph& g, const double* beta, long long ld, const double* H, long long ldh,
                               const double* XtX, int K, double* scratch_partials, double* out4_dev, hipStream_t st) {
     // the four sums of compute_objective (core/solver.py:269-284): <H,beta>, beta' XtX beta, smoothness, |beta|_1
     int nblk = objective_partials_count(g.n_slices);
     int rc_t = 1;
-    if (g.tiled && !fdx::env("FDX_NO_TILED")) {          // same LDS-tiled traversal as the sweep (n_tiles <= nblk partial rows)
-        BcdSweepArgs a{};
-        a.H = H; a.XtX = XtX; a.beta_in = beta; a.beta_out = nullptr; a.ell = g.ell.as<int>();
-        a.slice_off = g.slice_off.as<int>(); a.deg = g.deg.as<int>(); a.stats = nullptr; a.rel_change = nullptr;
-        a.lambda = 0.0; a.rho = 0.0; a.tol = 0.0; a.ldh = (int)ldh; a.ld = (int)ld; a.n = (int)g.n;
-        a.n_slices = g.n_slices; a.K = K; a.tiled = 1; a.ell_local = g.ell_local.as<unsigned short>();
-        a.tile_halo = g.tile_halo.as<int>(); a.tile_hcnt = g.tile_hcnt.as<int>(); a.n_tiles = g.n_tiles; a.halo_max = g.halo_max;
+    BcdSweepArgs a = sweep_args_for_graph(g, true);
+    if (a.tiled) {          // same LDS-tiled traversal as the sweep (n_tiles <= nblk partial rows)
+        a.H = H; a.XtX = XtX; a.beta_in = beta; a.ldh = (int)ldh; a.ld = (int)ld; a.K = K;
         // the padded sizes above 64 types: the traversal without the K^2 products, the quadratic term as a Gram matrix by MFMA
         a.skip_quad = (K > FDX_MAX_K_FAST && sweep_instantiated(K)) ? 1 : 0;
         rc_t = launch_bcd_objective_tiled(a, scratch_partials, st);
@@ -94,22 +121,76 @@ int solver_objective(const fdx_graph& g, const double* beta, long long ld, const
     double r[4];
     FDX_HIP(hipMemcpyAsync(r, scratch_out4, sizeof(r), hipMemcpyDeviceToHost, st));
     FDX_HIP(hipStreamSynchronize(st));
-    *obj_host = 0.5 * (YtY - 2.0 * r[0] + r[1]) + 0.5 * lambda * r[2] + rho_eff * r[3];
+    *obj_host = objective_from_sums(r, YtY, lambda, rho_eff);
+    return 0;
+}
+
+int SweepStats::init(int max_iter, hipStream_t st) {
+    const size_t iters = (size_t)std::max(max_iter, 1);
+    const size_t stats_bytes = iters * 128 * sizeof(unsigned long long);
+    FDX_TRY(block.alloc(stats_bytes + iters * sizeof(double)));
+    FDX_HIP(hipMemsetAsync(block.p, 0, block.bytes, st));
+    stats = block.as<unsigned long long>();
+    rel_change = reinterpret_cast<double*>(static_cast<char*>(block.p) + stats_bytes);
+    return 0;
+}
+
+int solver_loop(const SweepStats& s, int max_iter, double tol, int first_chunk, int n_ahead,
+                const std::function<int(int, bool)>& queue_iteration, LoopResult* res, hipStream_t st) {
+    // per chunk: events around its iterations (alternating pairs: the next chunk's first iterations are queued before this chunk's
+    // timing is read) and one after the trace copy the host waits on
+    Event ev0[2] = {Event(true), Event(true)}, ev1[2] = {Event(true), Event(true)}, evCopy;
+    // the trace lands in pinned host memory: a copy into pageable memory returns only when it has been done, i.e. it would make
+    // the host wait for the chunk before it can queue anything behind it
+    const size_t rc_count = (size_t)std::max(max_iter, 1);
+    double* rc_host = (double*)pinned_scratch(2, rc_count * sizeof(double));
+    if (!rc_host) return fail(FDX_ERR_HIP, "solver: pinned host buffer");
+    for (size_t j = 0; j < rc_count; ++j) rc_host[j] = 0.0;
+    *res = LoopResult();
+    res->rel_changes = rc_host;
+    int done = 0;          // iterations whose rel_change is known on the host
+    int chunk = first_chunk > 0 ? first_chunk : 4;
+    // The host reads the rel_change trace once per chunk; so that the device does not idle during that round trip (~45 us,
+    // a quarter of a sweep, per chunk) the first iterations of the NEXT chunk are queued before the host waits: if this chunk
+    // converged they are no-ops like every sweep past convergence (device-side stopping rule), otherwise they are simply early.
+    int queued_ahead = 0;  // iterations of the current chunk that were queued during the previous chunk's read-back
+    int ci = 0;            // chunk counter (event pair = ci & 1)
+    while (done < max_iter && !res->converged) {
+        const int end = std::min(max_iter, done + chunk);
+        const int pair = ci & 1;
+        if (queued_ahead == 0) FDX_TRY(ev0[pair].record(st));          // otherwise recorded ahead of the early iterations
+        for (int it = done + queued_ahead; it < end; ++it) FDX_TRY(queue_iteration(it, it + 1 == end));
+        FDX_TRY(launch_bcd_fold_last(s.stats, s.rel_change, end - 1, st));
+        FDX_TRY(ev1[pair].record(st));
+        FDX_HIP(hipMemcpyAsync(rc_host + done, s.rel_change + done, (size_t)(end - done) * sizeof(double), hipMemcpyDeviceToHost, st));
+        FDX_TRY(evCopy.record(st));
+        int ahead = 0;
+        if (end < max_iter && n_ahead > 0) {
+            ahead = std::min(n_ahead, max_iter - end);
+            FDX_TRY(ev0[pair ^ 1].record(st));
+            for (int it = end; it < end + ahead; ++it) FDX_TRY(queue_iteration(it, false));   // (not the last of their chunk)
+        }
+        FDX_TRY(evCopy.sync());
+        float ms_chunk = 0.f;
+        FDX_HIP(hipEventElapsedTime(&ms_chunk, ev0[pair].e, ev1[pair].e));
+        res->sweep_ms += ms_chunk;
+        for (int it = done; it < end; ++it) {
+            res->n_iter = it + 1;
+            if (rc_host[it] < tol) { res->converged = true; break; }   // solver.py:409-413
+        }
+        done = end;
+        queued_ahead = ahead;
+        // 4, 4, 8, 16, 32, 32, ...: a solve that converges in 5-8 sweeps (the gaussian family: 7) retires one no-op sweep instead of five
+        chunk = std::max(std::min(ci == 0 ? chunk : chunk * 2, 32), ahead);
+        ++ci;
+    }
     return 0;
 }
 
 int solver_run(const SolveProblem& p, SolveResult* res, hipStream_t st) {
     const fdx_graph& g = *p.graph;
     const int K = p.K;
-    res->result_buffer = 0;
-    res->n_iterations = 0;
-    res->converged = 0;
-    res->final_change = 0.0;
-    res->final_objective = 0.0;
-    res->objective_iters.clear();
-    res->objectives.clear();
-    res->rel_changes.clear();
-    res->sweep_ms = 0.0;
+    *res = SolveResult();
     if (g.n == 0 || K == 0) {  // core/solver.py:334-343
         res->converged = 1;
         return 0;
@@ -118,22 +199,13 @@ int solver_run(const SolveProblem& p, SolveResult* res, hipStream_t st) {
     FDX_REQUIRE(p.max_iter >= 0, "solver: max_iter must be >= 0");
 
     const int max_iter = p.max_iter;
-    DevBuf stats, relchg, obj_partials, obj_out, generic_scratch, obj_trace;
-    // the max slots of every iteration and, behind them, the rel_change trace: one block, one fill
-    const size_t stats_bytes = (size_t)std::max(max_iter, 1) * 128 * sizeof(unsigned long long);
-    FDX_TRY(stats.alloc(stats_bytes + (size_t)std::max(max_iter, 1) * sizeof(double)));
+    SweepStats stats;
+    DevBuf obj_partials, obj_out, generic_scratch;
+    FDX_TRY(stats.init(max_iter, st));
     FDX_TRY(obj_partials.alloc((size_t)objective_partials_count(g.n_slices) * 4 * sizeof(double)));
     FDX_TRY(obj_out.alloc(4 * sizeof(double)));
-    FDX_HIP(hipMemsetAsync(stats.p, 0, stats.bytes, st));
-    double* const relchg_p = reinterpret_cast<double*>(static_cast<char*>(stats.p) + stats_bytes);
     size_t scratch_ld = 0;
-    if (sweep_uses_lds(K)) {                          // the LDS-resident sweep reads XtX with its rows padded to 16
-        FDX_TRY(generic_scratch.alloc(sweep_lds_pad_doubles(K) * sizeof(double)));
-        FDX_TRY(sweep_lds_prepare(p.XtX, K, generic_scratch.as<double>(), st));
-    } else if (!sweep_instantiated(K)) {
-        scratch_ld = (size_t)g.n_slices * 64;
-        FDX_TRY(generic_scratch.alloc(scratch_ld * 2 * K * sizeof(double)));
-    }
+    FDX_TRY(sweep_scratch_prepare(p.XtX, K, g.n_slices, &generic_scratch, &scratch_ld, st));
     const int K_real = p.K_real > 0 ? p.K_real : K;
     if (p.init_beta) FDX_TRY(solver_init_beta(p.beta[0], p.ld, g.n_total, K_real, st, K));   // beta0 = 1/K (solver.py:372)
     // the second buffer's pad rows must also read as zero
@@ -141,15 +213,9 @@ int solver_run(const SolveProblem& p, SolveResult* res, hipStream_t st) {
     // buffer was 30 us of a 6 ms fit)
     if (p.init_beta) FDX_TRY(solver_zero_pad(p.beta[1], p.ld, g.n_total, K, st));
 
-    BcdSweepArgs a{};
-    a.H = p.H; a.XtX = p.XtX; a.ell = g.ell.as<int>(); a.slice_off = g.slice_off.as<int>(); a.deg = g.deg.as<int>();
-    a.stats = stats.as<unsigned long long>(); a.rel_change = relchg_p;
-    a.lambda = p.lambda; a.rho = p.rho_eff; a.tol = p.tol; a.ldh = (int)p.ldh; a.ld = (int)p.ld; a.n = (int)g.n;
-    a.n_slices = g.n_slices; a.K = K;
-    if (g.tiled && !fdx::env("FDX_NO_TILED")) {
-        a.tiled = 1; a.ell_local = g.ell_local.as<unsigned short>(); a.tile_halo = g.tile_halo.as<int>();
-        a.tile_hcnt = g.tile_hcnt.as<int>(); a.n_tiles = g.n_tiles; a.halo_max = g.halo_max;
-    }
+    BcdSweepArgs a = sweep_args_for_graph(g, true);
+    a.H = p.H; a.XtX = p.XtX; a.stats = stats.stats; a.rel_change = stats.rel_change;
+    a.lambda = p.lambda; a.rho = p.rho_eff; a.tol = p.tol; a.ldh = (int)p.ldh; a.ld = (int)p.ld; a.K = K;
 
     // the start vector as a constant of the first sweep (bcd_sweep_inst.cpp, INIT) - or written now, where that kernel does not apply
     double init_uniform = 0.0;
@@ -163,36 +229,9 @@ int solver_run(const SolveProblem& p, SolveResult* res, hipStream_t st) {
             FDX_TRY(solver_init_beta(p.beta[0], p.ld, g.n_total, K_real, st, K));
     }
 
-    // per chunk: events around its sweeps (alternating pairs: the next chunk's first sweeps are queued before this chunk's
-    // timing is read) and one after the trace copy the host waits on
-    hipEvent_t ev0[2] = {nullptr, nullptr}, ev1[2] = {nullptr, nullptr}, evCopy = nullptr;
-    struct EvGuard { hipEvent_t* e[5]; ~EvGuard() { for (auto* q : e) if (*q) (void)hipEventDestroy(*q); } } ev_guard{{&ev0[0], &ev0[1], &ev1[0], &ev1[1], &evCopy}};
-    for (int j = 0; j < 2; ++j) {
-        FDX_HIP(hipEventCreate(&ev0[j]));
-        FDX_HIP(hipEventCreate(&ev1[j]));
-    }
-    FDX_HIP(hipEventCreateWithFlags(&evCopy, hipEventDisableTiming));
-    double sweep_ms_acc = 0.0;   // GPU time of the queued sweeps only (host read-back gaps between chunks excluded)
-
-    // the trace lands in pinned host memory: a copy into pageable memory returns only when it has been done, i.e. it would make
-    // the host wait for the chunk before it can queue anything behind it
-    const size_t rc_count = (size_t)std::max(max_iter, 1);
-    double* rc_host = (double*)pinned_scratch(2, rc_count * sizeof(double));
-    if (!rc_host) return fail(FDX_ERR_HIP, "solver: pinned host buffer");
-    for (size_t j = 0; j < rc_count; ++j) rc_host[j] = 0.0;
-    int done = 0;          // iterations whose rel_change is known on the host
-    int n_iter = 0;
-    bool converged = false;
-    int chunk = p.first_chunk > 0 ? p.first_chunk : 4;
-    // The host reads the rel_change trace once per chunk; so that the device does not idle during that round trip (~45 us,
-    // a quarter of a sweep, per chunk) the first sweeps of the NEXT chunk are queued before the host waits: if this chunk
-    // converged they are no-ops like every sweep past convergence (device-side stopping rule), otherwise they are simply early.
-    const int n_ahead = (p.verbose || fdx::exp_env("FDX_NO_SWEEP_AHEAD")) ? 0 : 2;
-    int queued_ahead = 0;  // sweeps of the current chunk that were queued during the previous chunk's read-back
-    int ci = 0;            // chunk counter (event pair = ci & 1)
     // verbose objective trace: evaluated on the NEW buffer at it % 10 == 0 or it == max_iter-1 (solver.py:399-404)
     std::vector<std::pair<int, double>> trace;
-    auto queue_sweep = [&](int it) -> int {
+    auto queue_sweep = [&](int it, bool) -> int {
         a.it = it;
         a.beta_in = p.beta[it & 1];
         a.beta_out = p.beta[(it + 1) & 1];
@@ -206,45 +245,17 @@ int solver_run(const SolveProblem& p, SolveResult* res, hipStream_t st) {
         }
         return 0;
     };
-    while (done < max_iter && !converged) {
-        const int end = std::min(max_iter, done + chunk);
-        const int pair = ci & 1;
-        if (queued_ahead == 0) FDX_HIP(hipEventRecord(ev0[pair], st));          // otherwise recorded ahead of the early sweeps
-        for (int it = done + queued_ahead; it < end; ++it) FDX_TRY(queue_sweep(it));
-        FDX_TRY(launch_bcd_fold_last(a.stats, a.rel_change, end - 1, st));
-        FDX_HIP(hipEventRecord(ev1[pair], st));
-        FDX_HIP(hipMemcpyAsync(rc_host + done, relchg_p + done, (size_t)(end - done) * sizeof(double),
-                               hipMemcpyDeviceToHost, st));
-        FDX_HIP(hipEventRecord(evCopy, st));
-        int ahead = 0;
-        if (end < max_iter && n_ahead > 0) {
-            ahead = std::min(n_ahead, max_iter - end);
-            FDX_HIP(hipEventRecord(ev0[pair ^ 1], st));
-            for (int it = end; it < end + ahead; ++it) FDX_TRY(queue_sweep(it));
-        }
-        FDX_HIP(hipEventSynchronize(evCopy));
-        {
-            float ms_chunk = 0.f;
-            FDX_HIP(hipEventElapsedTime(&ms_chunk, ev0[pair], ev1[pair]));
-            sweep_ms_acc += ms_chunk;
-        }
-        for (int it = done; it < end; ++it) {
-            n_iter = it + 1;
-            if (rc_host[it] < p.tol) { converged = true; break; }   // solver.py:409-413
-        }
-        done = end;
-        queued_ahead = ahead;
-        // 4, 4, 8, 16, 32, 32, ...: a solve that converges in 5-8 sweeps (the gaussian family: 7) retires one no-op sweep instead of five
-        chunk = std::max(std::min(ci == 0 ? chunk : chunk * 2, 32), ahead);
-        ++ci;
-    }
-    res->sweep_ms = sweep_ms_acc;
+    LoopResult loop;
+    const int n_ahead = (p.verbose || fdx::exp_env("FDX_NO_SWEEP_AHEAD")) ? 0 : 2;
+    FDX_TRY(solver_loop(stats, max_iter, p.tol, p.first_chunk, n_ahead, queue_sweep, &loop, st));
 
-    res->n_iterations = n_iter;                        // iteration + 1 (solver.py:422); 0 when max_iter == 0
-    res->converged = converged ? 1 : 0;
-    res->final_change = n_iter > 0 ? rc_host[n_iter - 1] : 0.0;
+    const int n_iter = loop.n_iter;
+    res->sweep_ms = loop.sweep_ms;
+    res->n_iterations = n_iter;
+    res->converged = loop.converged ? 1 : 0;
+    res->final_change = n_iter > 0 ? loop.rel_changes[n_iter - 1] : 0.0;
     res->result_buffer = n_iter & 1;                   // sweep `it` writes buffer (it+1)&1
-    res->rel_changes.assign(rc_host, rc_host + n_iter);
+    res->rel_changes.assign(loop.rel_changes, loop.rel_changes + n_iter);
     for (auto& t : trace)
         if (t.first < n_iter) { res->objective_iters.push_back(t.first); res->objectives.push_back(t.second); }
     if (p.compute_objective)

@@ -1,5 +1,6 @@
 // Internal interface of the BCD solve driver (solver.cpp).
 #pragma once
+#include <functional>
 #include <vector>
 
 #include "fdx_graph.h"
@@ -54,5 +55,40 @@ int solver_objective(const fdx_graph& g, const double* beta, long long ld, const
                      const double* XtX, int K, double YtY, double lambda, double rho_eff, double* scratch_partials,
                      double* scratch_out4, double* obj_host, hipStream_t st);
 int solver_run(const SolveProblem& p, SolveResult* res, hipStream_t st);
+
+// ---- pieces the single-GPU solve (solver_run) and the sharded one (comm.cpp) share
+// The graph's part of a sweep's arguments: ELL arrays, sizes and - for a tiled graph - the tile fields (honour_no_tiled: unless
+// FDX_NO_TILED asks for the global-gather sweep).  Everything else is left zero for the caller.
+BcdSweepArgs sweep_args_for_graph(const fdx_graph& g, bool honour_no_tiled);
+// Scratch of the sweeps that are not register-resident (more than 64 types outside 72 / 80 / 88 / 96): the LDS-resident sweep reads
+// XtX with its rows padded to 16 (queued on st; scratch_ld stays 0), the generic one keeps the abundances in 2 K planes of scratch_ld
+int sweep_scratch_prepare(const double* XtX, int K, int n_slices, DevBuf* scratch, size_t* scratch_ld, hipStream_t st);
+// diag_mean = mean(diag XtX): rho_eff = rho * diag_mean (core/solver.py:359-360); auto_tune_lambda (core/spatial.py:181-190):
+// alpha * diag_mean / max(mean degree, 1), alpha = 0.005
+double xtx_diag_mean(const double* XtX_host, int K);
+double auto_lambda(double diag_mean, double mean_degree);
+// compute_objective (core/solver.py:269-284) from its four sums <H,beta>, beta' XtX beta, smoothness, |beta|_1
+inline double objective_from_sums(const double* r4, double YtY, double lambda, double rho_eff) {
+    return 0.5 * (YtY - 2.0 * r4[0] + r4[1]) + 0.5 * lambda * r4[2] + rho_eff * r4[3];
+}
+
+// The max slots of every iteration and, behind them, the rel_change trace: one device block, one fill (queued by init)
+struct SweepStats {
+    DevBuf block;
+    unsigned long long* stats = nullptr;
+    double* rel_change = nullptr;
+    int init(int max_iter, hipStream_t st);
+};
+struct LoopResult {
+    int n_iter = 0;                       // iteration + 1 (solver.py:422); 0 when max_iter == 0
+    bool converged = false;
+    const double* rel_changes = nullptr;  // n_iter values, pinned scratch of this thread: valid until the next loop
+    double sweep_ms = 0.0;                // GPU time of the queued iterations only (host read-back gaps between chunks excluded)
+};
+// The chunked iteration driver: queue_iteration(it, last_of_chunk) queues iteration it on st; chunks of first_chunk, then
+// 4, 8, 16, 32, 32, ... iterations, the rel_change trace read back once per chunk with the first n_ahead iterations of the next
+// chunk queued before the host waits for it.  The stopping rule is solver.py:409-413 on the trace.
+int solver_loop(const SweepStats& s, int max_iter, double tol, int first_chunk, int n_ahead,
+                const std::function<int(int, bool)>& queue_iteration, LoopResult* res, hipStream_t st);
 
 }  // namespace fdx
