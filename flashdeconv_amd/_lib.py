@@ -39,6 +39,17 @@ class SolveInfo(ctypes.Structure):
         ("total_ms", c_double),
     ]
 
+    def as_dict(self, rel_changes=None, objective=True):
+        """The reference's info dict (core/solver.py:415-421).  rel_changes: the per-iteration array the call filled, when the
+        caller reports it; objective=False for a solve whose objective is evaluated afterwards."""
+        n_it = int(self.n_iterations)
+        d = {"converged": bool(self.converged), "n_iterations": n_it, "final_change": float(self.final_change)}
+        if objective:
+            d["final_objective"] = float(self.final_objective)
+        if rel_changes is not None:
+            d["rel_changes"] = [float(v) for v in rel_changes[:n_it]]
+        return d
+
 
 class FitParams(ctypes.Structure):
     _fields_ = [
@@ -305,18 +316,27 @@ def host_cpu_budget():
     return max(1, int(round(cpus)))
 
 
+def current_stream():
+    """torch's current stream of the current device, as the stream argument of the device-pointer calls."""
+    import torch
+    return c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def dtype_code(t):
+    """FDX_F32 / FDX_F64 of a torch tensor, a numpy array or a dtype of either."""
+    return FDX_F32 if str(getattr(t, "dtype", t)).rpartition(".")[2] == "float32" else FDX_F64
+
+
 def tensor_to_host(t):
     """A CUDA torch tensor as a numpy array, copied through the library's pinned staging (fdx_memcpy_d2h): ``t.cpu()`` hands the
     driver pageable memory to pin, and unmapping that memory later stalls the process's GPU queues (csrc/pool.cpp: copy_d2h)."""
-    import torch
     if not getattr(t, "is_cuda", False):
         return t.detach().cpu().numpy()
     t = t.detach().contiguous()
     out = np.empty(tuple(t.shape), dtype=np.dtype(str(t.dtype).replace("torch.", "")))
     if out.nbytes:
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         fn = load().fdx_download_dev if out.nbytes >= (32 << 20) else load().fdx_memcpy_d2h      # (large: threaded pinned ring)
-        check(fn(out.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(t.data_ptr()), out.nbytes, st))
+        check(fn(out.ctypes.data, t.data_ptr(), out.nbytes, current_stream()))
     return out
 
 
@@ -576,8 +596,7 @@ class CsrOnDevice:
         shape_key = (int(n), int(G), int(val.numel()), crow.data_ptr(), col.data_ptr())
         zero_copy = crow.data_ptr() == crow0.data_ptr() and col.data_ptr() == col0.data_ptr()
         known = cls._checked_lookup(Y, crow0, col0, shape_key) if zero_copy else None
-        self._fill(crow.data_ptr(), col.data_ptr(), val.data_ptr(), FDX_F32 if val.dtype == torch.float32 else FDX_F64,
-                   n, int(val.numel()), G, known_sorted=known)
+        self._fill(crow.data_ptr(), col.data_ptr(), val.data_ptr(), dtype_code(val), n, int(val.numel()), G, known_sorted=known)
         if zero_copy and known is None:
             cls._checked_store(Y, crow0, col0, shape_key, self.view.sorted_rows)
         return self

@@ -17,7 +17,7 @@ from scipy import sparse
 
 from .. import _lib
 from ..utils import genes as _genes
-from .sketching import countsketch_tables
+from .sketching import sketch_tables
 
 _PRE_MODES = ("log_cpm", "pearson", "raw")
 
@@ -138,6 +138,34 @@ def reference_tie_graph(c_ptr, coords_host, n, dim, k):
     finally:
         for b in (nbr, cnt):
             b.free()
+
+
+def _fit_timings(info, t_entry, t_graph, t_graph_end, select_s, t_lev, t_done, t_call, t_ret, ties_remedy_ms, span_from_call):
+    """timings_ of a fit (additive, not in the reference): the per-stage GPU milliseconds the fit call reports (hipEvents) and
+    the host intervals between the clock marks FlashDeconv.fit recorded - entry, the graph build call and its end, the wait for
+    the leverage SVD (t_lev .. t_done), the fit call and its return."""
+    t = {k: float(getattr(info, k)) for k in ("graph_ms", "sketch_ms", "gram_ms", "solve_ms", "finish_ms", "total_ms", "prologue_ms",
+                                              "span_ms")}
+    t["sweep_ms"] = float(info.solve.sweep_ms)
+    # ties under "auto": the stopped first call + the reference's lists (host tree) + the rebuilt graph; ahead of the fit proper
+    t["ties_remedy_ms"] = ties_remedy_ms
+    # host wall of the graph build call, and of the wait for the leverage SVD that ran beside it
+    t["graph_ms"] = (t_graph_end - t_graph) * 1e3
+    t["select_ms"] = select_s * 1e3               # gene statistics on the device + HVG/marker ranking on the host
+    t["leverage_wait_ms"] = (t_done - t_lev) * 1e3
+    # the graph is built by its own call ahead of fdx_fit_dev, whose total_ms starts after it: one figure for the fit
+    t["device_ms"] = t["total_ms"]
+    # Accounting that tiles the wall time of the fit: host_pre_ms (entry -> the graph build call: conversions, gene selection,
+    # leverage job set-up) + span_ms (device, hipEvents: first kernel of the graph build -> end of the export =
+    # prologue_ms + sketch_ms + gram_ms + solve_ms + finish_ms) + host_post_ms (fit_dev's return -> here);
+    # total_ms is their sum, and what the wall has beyond it is the host's last synchronisation.
+    # span_from_call: the device span starts with the fit call - the graph was queued on the side stream FIRST (gene selection
+    # active: gene statistics + ranking + leverage + tables all lie before the call; select_ms is the part that selects), or it
+    # was rebuilt on the reference's tie order (first build, the stopped call, the host tree, the rebuild are host time)
+    t["host_pre_ms"] = ((t_call if span_from_call else t_graph) - t_entry) * 1e3
+    t["host_post_ms"] = (time.perf_counter() - t_ret) * 1e3
+    t["total_ms"] = t["host_pre_ms"] + t["span_ms"] + t["host_post_ms"]
+    return t
 
 
 class FlashDeconv:
@@ -278,10 +306,8 @@ class FlashDeconv:
                 owned.append(csr)
                 y_ptr, y_code, y_sparse_rule = None, csr.view.dtype, True
             elif _is_torch_cuda(Y):
-                import torch
                 Y, y_f64_math = device_counts_as_float(Y)
-                y_ptr, y_code = ctypes.c_void_p(Y.data_ptr()), (_lib.FDX_F32 if Y.dtype == torch.float32 else _lib.FDX_F64)
-                y_sparse_rule = False
+                y_ptr, y_code, y_sparse_rule = Y.data_ptr(), _lib.dtype_code(Y), False
             else:
                 y_sparse_rule = False
                 Yh = np.asarray(Y)
@@ -295,7 +321,7 @@ class FlashDeconv:
             if _is_torch_cuda(coords):
                 import torch
                 cd = coords.to(torch.float64).contiguous()
-                c_ptr = ctypes.c_void_p(cd.data_ptr())
+                c_ptr = cd.data_ptr()
                 coords_host = None
             else:
                 coords_host = np.ascontiguousarray(np.asarray(coords), dtype=np.float64)
@@ -320,8 +346,7 @@ class FlashDeconv:
                     # on the library's side stream, behind whatever produced the coordinates on the default stream so far
                     _lib.check(lib.fdx_side_stream(ctypes.byref(side)))
                     if _is_torch_cuda(coords):
-                        import torch
-                        _lib.check(lib.fdx_stream_wait_stream(side, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                        _lib.check(lib.fdx_stream_wait_stream(side, _lib.current_stream()))
                 _lib.check(lib.fdx_graph_build_dev(c_ptr, n, dim, g_method, g_k, g_radius, side, ctypes.byref(gh)))
                 self._graph = _lib.Graph(gh.value)
                 t_graph_done = time.perf_counter()
@@ -333,30 +358,14 @@ class FlashDeconv:
                 gene_idx = np.arange(G_all, dtype=np.intp)
             else:
                 # the marker table depends on X only: a helper thread ranks it while the device reduces Y to its per-gene
-                # moments (the C call releases the GIL)
-                import concurrent.futures
-                tr = [time.perf_counter()] if os.environ.get("FDX_TRACE_HOST") else None
-                with concurrent.futures.ThreadPoolExecutor(max_workers=1) as pool:
-                    fut = pool.submit(_genes.select_markers, X, self.n_markers_per_type)
-                    if csr is not None:
-                        mean, var, csr_colsum = csr.gene_moments(want_colsum=self.preprocess == "pearson")
-                    else:
-                        mean, var = _genes.gene_moments_device(y_ptr, y_code, n, G_all, G_all)
-                    if tr is not None:
-                        tr.append(time.perf_counter())
-                    hvg = _genes._hvg_from_moments(mean, var, self.n_hvg, 0.0125, 3.0, 0.5)
-                    if tr is not None:
-                        tr.append(time.perf_counter())
-                    markers, _ = fut.result()
-                    if tr is not None:
-                        tr.append(time.perf_counter())
-                gene_idx = np.union1d(hvg, markers).astype(np.intp)                  # utils/genes.py:330
-                if tr is not None:
-                    tr.append(time.perf_counter())
-                    print("[fdx-host] python select: moments (device + read-back) %.0f us, hvg ranking %.0f, wait for the marker table %.0f, "
-                          "pool shutdown + union %.0f" % tuple(1e6 * (b - a) for a, b in zip(tr[:-1], tr[1:])), file=sys.stderr)
-                if len(gene_idx) == 0:
-                    raise ValueError("No genes selected. Increase n_hvg or n_markers_per_type.")
+                # moments (and, for CSR rows under "pearson", to the column sums of step 2)
+                def moments():
+                    nonlocal csr_colsum
+                    if csr is None:
+                        return _genes.gene_moments_device(y_ptr, y_code, n, G_all, G_all)
+                    mean, var, csr_colsum = csr.gene_moments(want_colsum=self.preprocess == "pearson")
+                    return mean, var
+                gene_idx = _genes.select_gene_idx(X, self.n_hvg, self.n_markers_per_type, moments)
             self.gene_idx_ = gene_idx
             t_sel_end = time.perf_counter()
             t_sel = t_sel_end - t_sel
@@ -407,35 +416,23 @@ class FlashDeconv:
 
             # Step 2+3 tables: preprocessing mode and CountSketch Omega (core/deconv.py:326-352)
             log(f"Step 2: Preprocessing with method='{self.preprocess}'...")
-            bucket, weight = countsketch_tables(G, self.sketch_dim, leverage, self.random_state)
-            weight_y = weight_x = weight
-            mode_y = mode_x = _lib.PRE_RAW
-            if self.preprocess == "log_cpm":
-                mode_y = _lib.PRE_LOG_CPM_SPARSE if y_sparse_rule else _lib.PRE_LOG_CPM
-                mode_x = _lib.PRE_LOG_CPM
-                log("  Y and X normalized to log-CPM space")
-            elif self.preprocess == "pearson":
+
+            def y_colsum():
                 if csr is not None:
-                    if csr_colsum is None:
-                        _, _, csr_colsum = csr.gene_moments(want_colsum=True)
-                    sums = csr_colsum[gene_idx]
-                else:
-                    sums = np.empty(G, dtype=np.float64)
-                    _lib.check(lib.fdx_column_sums_dev(y_ptr, y_code, n, G, ldy, _lib.ptr_f64(sums), None))
-                mu_y = sums / n + 1e-6                                        # core/deconv.py:208,214
-                mu_x = Xsel.mean(axis=0) + 1e-6                               # core/deconv.py:220
-                weight_y = weight / np.sqrt(mu_y + mu_y ** 2 / 100.0)         # sigma^2 = mu + mu^2/theta, theta = 100
-                weight_x = weight / np.sqrt(mu_x + mu_x ** 2 / 100.0)
-                log("  Y and X transformed with uncentered Pearson residuals")
-            else:
-                log("  No preprocessing applied (raw)")
+                    return (csr_colsum if csr_colsum is not None else csr.gene_moments(want_colsum=True)[2])[gene_idx]
+                sums = np.empty(G, dtype=np.float64)
+                _lib.check(lib.fdx_column_sums_dev(y_ptr, y_code, n, G, ldy, _lib.ptr_f64(sums), None))
+                return sums
+            bucket32, wy, wx, mode_y, mode_x = sketch_tables(
+                G, self.sketch_dim, leverage, self.random_state, self.preprocess, Xsel, y_sparse=y_sparse_rule,
+                f64_math=y_f64_math and csr is None and y_code == _lib.FDX_F32, y_colsum=y_colsum, n_spots=n)
+            log({"log_cpm": "  Y and X normalized to log-CPM space", "pearson": "  Y and X transformed with uncentered Pearson residuals",
+                 "raw": "  No preprocessing applied (raw)"}[self.preprocess])
             log(f"Step 3: Sketching to {self.sketch_dim} dimensions...")
             log(f"  Compressed {G} genes -> {self.sketch_dim} dims")
 
             prm = _lib.FitParams()
             prm.sketch_dim = int(self.sketch_dim)
-            if y_f64_math and csr is None and y_code == _lib.FDX_F32:
-                mode_y |= _lib.PRE_F64_MATH
             prm.mode_y, prm.mode_x = mode_y, mode_x
             prm.k_neighbors = int(self.k_neighbors)
             prm.max_iter, prm.tol, prm.verbose = int(self.max_iter), float(self.tol), 1 if self.verbose else 0
@@ -455,7 +452,7 @@ class FlashDeconv:
                 dev = Y.device if _is_torch_cuda(Y) else torch.device("cuda", torch.cuda.current_device())
                 beta_t = torch.empty((n, K), dtype=torch.float64, device=dev)
                 prop_t = torch.empty((n, K), dtype=torch.float64, device=dev)
-                b_ptr, p_ptr = ctypes.c_void_p(beta_t.data_ptr()), ctypes.c_void_p(prop_t.data_ptr())
+                b_ptr, p_ptr = beta_t.data_ptr(), prop_t.data_ptr()
             else:
                 bbuf, pbuf = _DeviceBuffer(n * K * 8), _DeviceBuffer(n * K * 8)
                 owned += [bbuf, pbuf]
@@ -465,8 +462,6 @@ class FlashDeconv:
             rels = np.zeros(max(int(self.max_iter), 1), dtype=np.float64)
             info = _lib.FitInfo()
             gh = ctypes.c_void_p(self._graph.handle.value)
-            bucket32 = np.ascontiguousarray(bucket, dtype=np.int32)
-            wy, wx = _lib.as_f64(weight_y), _lib.as_f64(weight_x)
             t_call = time.perf_counter()
             gi32 = np.ascontiguousarray(gene_idx, dtype=np.int32)
 
@@ -535,13 +530,8 @@ class FlashDeconv:
                 print(f"Iteration {t}: objective = {obj:.6f}, rel_change = {rels[t]:.6e}")
             if info.solve.converged:
                 print(f"Converged at iteration {n_it - 1}")
-        self.info_ = {
-            "converged": bool(info.solve.converged),
-            "n_iterations": n_it,
-            "final_objective": float(info.solve.final_objective),
-            "objectives": objectives if self.verbose else [],
-            "final_change": float(info.solve.final_change),
-        }
+        self.info_ = info.solve.as_dict()
+        self.info_["objectives"] = objectives if self.verbose else []
         # additive (not in the reference): spots whose k-NN set is a choice - the k-th and (k+1)-th neighbours exactly
         # equidistant.  The reference takes whichever cKDTree.query meets first (utils/graph.py:60-63), which changes
         # with the order the spots are listed in; here the lower spot index wins.  Regular lattices tie on every spot.
@@ -556,34 +546,9 @@ class FlashDeconv:
                 "Proportions can differ from the reference's by a few 1e-4 (relative); knn_ties='auto' (the default) or "
                 "'ckdtree' reproduce the reference's choice (host-side, about a second per million spots), "
                 "spatial_method='grid' builds a tie-free graph on lattices.", UserWarning, stacklevel=2)
-        # additive diagnostics (not in the reference): per-stage GPU milliseconds
-        self.timings_ = {k: float(getattr(info, k)) for k in ("graph_ms", "sketch_ms", "gram_ms", "solve_ms", "finish_ms", "total_ms",
-                                                             "prologue_ms", "span_ms")}
-        self.timings_["sweep_ms"] = float(info.solve.sweep_ms)
-        # ties under "auto": the stopped first call + the reference's lists (host tree) + the rebuilt graph; ahead of the fit proper
-        self.timings_["ties_remedy_ms"] = ties_remedy_ms
-        # host wall of the graph build call, and of the wait for the leverage SVD that ran beside it
-        self.timings_["graph_ms"] = ((t_graph_done if graph_early else t_lev) - t_graph) * 1e3
-        self.timings_["select_ms"] = t_sel * 1e3      # gene statistics on the device + HVG/marker ranking on the host
-        self.timings_["leverage_wait_ms"] = (t_done - t_lev) * 1e3
-        # the graph is built by its own call ahead of fdx_fit_dev, whose total_ms starts after it: one figure for the fit
-        self.timings_["device_ms"] = self.timings_["total_ms"]
-        # Accounting that tiles the wall time of this call: host_pre_ms (entry -> the graph build call: conversions, gene selection,
-        # leverage job set-up) + span_ms (device, hipEvents: first kernel of the graph build -> end of the export =
-        # prologue_ms + sketch_ms + gram_ms + solve_ms + finish_ms) + host_post_ms (fit_dev's return -> here);
-        # total_ms is their sum, and what the wall has beyond it is the host's last synchronisation
-        self.timings_["host_pre_ms"] = (t_graph - t_entry) * 1e3
-        if graph_early:
-            # gene selection active: the graph was queued on the side stream FIRST and the device span starts with the fit call -
-            # gene statistics (device) + ranking (host) + leverage + tables all lie before it (select_ms is the part of it that
-            # selects)
-            self.timings_["host_pre_ms"] = (t_call - t_entry) * 1e3
-        if ties_resolved_here or (resolved and n_ties):
-            # the graph was rebuilt on the reference's tie order: the device span starts with the fit call that used it, and
-            # everything before that call (first build, the stopped call, the host tree, the rebuild) is host time
-            self.timings_["host_pre_ms"] = (t_call - t_entry) * 1e3
-        self.timings_["host_post_ms"] = (time.perf_counter() - t_ret) * 1e3
-        self.timings_["total_ms"] = self.timings_["host_pre_ms"] + self.timings_["span_ms"] + self.timings_["host_post_ms"]
+        # ties resolved: the graph was rebuilt on the reference's tie order, the device span starts with the fit call that used it
+        self.timings_ = _fit_timings(info, t_entry, t_graph, t_graph_done if graph_early else t_lev, t_sel, t_lev, t_done, t_call, t_ret,
+                                     ties_remedy_ms, span_from_call=graph_early or ties_resolved_here or bool(resolved and n_ties))
         self._fitted = True
         log(f"  Converged: {self.info_['converged']}")
         log(f"  Iterations: {self.info_['n_iterations']}")

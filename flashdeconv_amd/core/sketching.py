@@ -55,6 +55,32 @@ def _countsketch_tables(n_genes, sketch_dim, leverage_scores, random_state):
     return bucket.astype(np.int64), weight
 
 
+def sketch_tables(n_genes, sketch_dim, leverage_scores, random_state, preprocess, Xsel, y_sparse=False, f64_math=False,
+                  y_colsum=None, n_spots=None):
+    """What the sketch -> H stage takes besides Y and X: (bucket int32[G], weight_y, weight_x float64[G], mode_y, mode_x).
+
+    The preprocessing of core/deconv.py:147-235 is folded into them: "log_cpm" is a mode of the kernels (the sparse rule for
+    CSR rows; PRE_F64_MATH when float32 storage holds integer counts, f64_math), "pearson" a per-gene scale of the CountSketch
+    weights - 1 / sqrt(mu + mu^2 / theta), theta = 100, mu = the gene's mean over ALL n_spots spots + 1e-6, from the column
+    sums y_colsum (an array, or a callable so that no other mode computes them) for Y and from Xsel's own rows for X."""
+    bucket, weight = countsketch_tables(n_genes, sketch_dim, leverage_scores, random_state)
+    weight_y = weight_x = weight
+    mode_y = mode_x = _lib.PRE_RAW
+    if preprocess == "log_cpm":
+        mode_y = _lib.PRE_LOG_CPM_SPARSE if y_sparse else _lib.PRE_LOG_CPM
+        mode_x = _lib.PRE_LOG_CPM
+        if f64_math:
+            mode_y |= _lib.PRE_F64_MATH
+    elif preprocess == "pearson":
+        mu_y = np.asarray(y_colsum() if callable(y_colsum) else y_colsum) / n_spots + 1e-6      # core/deconv.py:208,214
+        mu_x = Xsel.mean(axis=0) + 1e-6                                                         # core/deconv.py:220
+        weight_y = weight / np.sqrt(mu_y + mu_y ** 2 / 100.0)
+        weight_x = weight / np.sqrt(mu_x + mu_x ** 2 / 100.0)
+    elif preprocess != "raw":
+        raise ValueError(f"Unknown preprocess method: {preprocess}. Choose from 'log_cpm', 'pearson', or 'raw'.")
+    return np.ascontiguousarray(bucket, dtype=np.int32), _lib.as_f64(weight_y), _lib.as_f64(weight_x), mode_y, mode_x
+
+
 def build_countsketch_matrix(n_genes, sketch_dim, leverage_scores=None, random_state=None):
     bucket, weight = countsketch_tables(n_genes, sketch_dim, leverage_scores, random_state)
     return sparse.csr_matrix((weight, (np.arange(n_genes), bucket)), shape=(n_genes, sketch_dim), dtype=np.float64)

@@ -22,6 +22,9 @@ import time
 import numpy as np
 
 from . import _lib
+from .core.deconv import FlashDeconv, device_counts_as_float
+from .core.sketching import sketch_tables
+from .utils import genes as _genes
 
 
 def diag_mean(XtX):
@@ -70,6 +73,7 @@ class TorchComm:
         self.group = group
         self.rank = dist.get_rank(group)
         self.world = dist.get_world_size(group)
+        self._stream_ordered = self.world > 1 and dist.get_backend(group) == "nccl"    # collectives ordered on the device streams
 
     def all_reduce_max(self, t):
         if self.world > 1:
@@ -107,18 +111,15 @@ class TorchComm:
 
     def exchange(self, send_bufs, recv_bufs):
         """send_bufs / recv_bufs: {peer: contiguous tensor}.  Grouped point-to-point."""
-        if self.world > 1 and not getattr(self, "_stream_ordered", None):
+        if self.world > 1 and not self._stream_ordered:
             # nccl / RCCL operations are ordered on the device streams.  Any other backend (gloo in the tests, with W processes on one
             # GPU) reads device buffers from the HOST as soon as it is called - the kernels that pack them have to be finished
             # (measured without this: abundances 1e-9 .. 3e-5 off and different from run to run, tools/class_ranks_gloo.py)
-            if getattr(self, "_stream_ordered", None) is None:
-                self._stream_ordered = self.dist.get_backend(self.group) == "nccl"
-            if not self._stream_ordered:
-                for t in list(send_bufs.values()) + list(recv_bufs.values()):
-                    if t.is_cuda:
-                        import torch
-                        torch.cuda.current_stream(t.device).synchronize()
-                        break
+            for t in list(send_bufs.values()) + list(recv_bufs.values()):
+                if t.is_cuda:
+                    import torch
+                    torch.cuda.current_stream(t.device).synchronize()
+                    break
         ops = []
         for peer, t in sorted(recv_bufs.items()):
             ops.append(self.dist.P2POp(self.dist.irecv, t, peer, self.group))
@@ -176,12 +177,13 @@ class HaloExchange:
         self.send_off = np.concatenate([[0], np.cumsum(self.send_counts)]).astype(int)
         self.recv_off = np.concatenate([[0], np.cumsum(self.recv_counts)]).astype(int)
         self._torch = torch
+        self._buf_key = None
 
     def __call__(self, beta):
         torch = self._torch
         K = beta.shape[0]
         key = (K, beta.dtype, beta.device)
-        if getattr(self, "_buf_key", None) != key:          # staging buffers are reused across iterations and fits
+        if self._buf_key != key:          # staging buffers are reused across iterations and fits
             self._send = {r: torch.empty((K, c), dtype=beta.dtype, device=beta.device)
                           for r, c in enumerate(self.send_counts) if c and r != self.comm.rank}
             self._recv = {r: torch.empty((K, c), dtype=beta.dtype, device=beta.device)
@@ -255,30 +257,35 @@ class HipBackend:
         self.K_real = int(K_real) if K_real else int(K)        # K > K_real: all-zero pad types (fdx_solver_padded_k)
         self.stream = stream
 
-    def _st(self):
-        import torch
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     def init_beta(self, beta, n_fill):
         # the buffer arrives zeroed: the pad types' planes stay zero
-        _lib.check(self.lib.fdx_init_beta_dev(ctypes.c_void_p(beta.data_ptr()), beta.shape[1], int(n_fill), self.K_real, self._st()))
+        _lib.check(self.lib.fdx_init_beta_dev(beta.data_ptr(), beta.shape[1], int(n_fill), self.K_real, _lib.current_stream()))
 
     def sweep(self, it, b_in, b_out, lam, rho_eff, tol, stats, rel):
-        _lib.check(self.lib.fdx_bcd_sweep_dev(self.g.handle, ctypes.c_void_p(self.H.data_ptr()), self.ldh,
-                                              ctypes.c_void_p(self.XtX.data_ptr()), ctypes.c_void_p(b_in.data_ptr()),
-                                              ctypes.c_void_p(b_out.data_ptr()), b_in.shape[1], self.K, float(lam),
-                                              float(rho_eff), float(tol), int(it), ctypes.c_void_p(stats.data_ptr()),
-                                              ctypes.c_void_p(rel.data_ptr()), self._st()))
+        _lib.check(self.lib.fdx_bcd_sweep_dev(self.g.handle, self.H.data_ptr(), self.ldh, self.XtX.data_ptr(), b_in.data_ptr(),
+                                              b_out.data_ptr(), b_in.shape[1], self.K, float(lam), float(rho_eff), float(tol), int(it),
+                                              stats.data_ptr(), rel.data_ptr(), _lib.current_stream()))
 
     def fold(self, stats, rel, it):
-        _lib.check(self.lib.fdx_bcd_fold_dev(ctypes.c_void_p(stats.data_ptr()), ctypes.c_void_p(rel.data_ptr()), int(it), self._st()))
+        _lib.check(self.lib.fdx_bcd_fold_dev(stats.data_ptr(), rel.data_ptr(), int(it), _lib.current_stream()))
 
     def objective_partials(self, beta):
         out = np.zeros(4)
-        _lib.check(self.lib.fdx_objective_partials_dev(self.g.handle, ctypes.c_void_p(beta.data_ptr()), beta.shape[1],
-                                                       ctypes.c_void_p(self.H.data_ptr()), self.ldh,
-                                                       ctypes.c_void_p(self.XtX.data_ptr()), self.K, _lib.ptr_f64(out), self._st()))
+        _lib.check(self.lib.fdx_objective_partials_dev(self.g.handle, beta.data_ptr(), beta.shape[1], self.H.data_ptr(), self.ldh,
+                                                       self.XtX.data_ptr(), self.K, _lib.ptr_f64(out), _lib.current_stream()))
         return out
+
+
+def _warn_knn_ties(n_ties, n, stacklevel):
+    import warnings
+    warnings.warn(f"k-NN ties: {n_ties} of {n} spots have their k-th and (k+1)-th nearest neighbours at exactly the "
+                  "same distance (regular lattice?): the neighbour graph depends on how ties are broken - here by spot "
+                  "index, in the reference by cKDTree's traversal order.  spatial_method='grid' builds a tie-free graph "
+                  "on lattices.", UserWarning, stacklevel=stacklevel + 1)
+
+
+# libfdx's own RCCL communicator could not be created on every rank: no ShardedFlashDeconv of this process tries again
+_native_comm_failed = False
 
 
 class ShardedFlashDeconv:
@@ -296,7 +303,6 @@ class ShardedFlashDeconv:
                  spatial_method="knn", radius=None, max_iter=100, tol=1e-4, preprocess="log_cpm", random_state=0,
                  group=None, comm=None, n_markers_per_type=50, knn_ties="auto"):
         # the reference's constructor checks and messages (core/deconv.py:105-124), through the single-GPU estimator
-        from .core.deconv import FlashDeconv
         self._proto = FlashDeconv(sketch_dim=sketch_dim, lambda_spatial=lambda_spatial, rho_sparsity=rho_sparsity, n_hvg=n_hvg,
                                   n_markers_per_type=n_markers_per_type, spatial_method=spatial_method, k_neighbors=k_neighbors,
                                   radius=radius, max_iter=max_iter, tol=tol, preprocess=preprocess, random_state=random_state)
@@ -311,19 +317,35 @@ class ShardedFlashDeconv:
         self.n_hvg, self.k_neighbors, self.spatial_method, self.radius = n_hvg, k_neighbors, spatial_method, radius
         self.max_iter, self.tol, self.preprocess, self.random_state = max_iter, tol, preprocess, random_state
         self.comm = comm if comm is not None else TorchComm(group)
-        self._native = None           # fdx_comm handle: the C++ / RCCL iteration loop (csrc/comm.cpp)
+        self._native = None               # fdx_comm handle: the C++ / RCCL iteration loop (csrc/comm.cpp)
+        self._native_borrowed = False     # ... brought by the comm object: not this model's to destroy
+        self.native_error_ = None         # why libfdx's own communicator could not be created
+        self.time_sweeps = False          # set by a caller: hipEvents around every sweep of the Python loop -> sweep_ms_
+        self.sweep_ms_ = self.sweep_loop_ms_ = None
+        # the plan
         self._full = self._local = None
+        self._coords = self._halo = self.bounds = self.own_ids = self.plan_route_ = None
+        self.n_total_spots = self.n_own = self.n_halo = self.own_nnz_ = self.nnz_total = self.knn_ties_ = 0
+        self.knn_ties_resolved_ = False
+        self.plan_rebuilt_stepwise_ = False   # (diagnostic, never reset: this rank's graph once came from _plan_stepwise_local)
+        self._pending_plan = None         # "shard": a queued plan whose counts _finish_plan() has yet to take over
+        self._step_counts = None          # (edges, tied rows, far flag) of the graph _plan_stepwise_local built
+        self._lev_job = None              # (X, LeverageJob) queued by plan(coords, X) for the next fit_transform
+        self._x_dev_job = None            # the collected job whose device copy of X serves the native fit
+        self._side = None                 # the export's stream (_solve_shard)
         self.timings_ = {}
-        self.knn_ties_ = 0
+        self._t0 = 0.0                    # last stage boundary of _tick
         self._profile = bool(os.environ.get("FDX_DIST_TIMING"))
         self._trace = [] if os.environ.get("FDX_TRACE_DRIVER") else None
 
     def native_comm(self):
         """libfdx's own RCCL communicator for the native iteration loop (fdx_sharded_solve_dev): rank 0 draws the
         ncclUniqueId, torch.distributed ships the 128 bytes, every rank calls ncclCommInitRank through fdx_comm_init.
-        None when the process group is not an nccl one (the gloo tests use the Python loop) or FDX_PY_LOOP is set."""
+        None when the process group is not an nccl one (the gloo tests use the Python loop), FDX_PY_LOOP is set, or the
+        communicator could not be created earlier in this process."""
         import torch
-        if self._native is not None or os.environ.get("FDX_PY_LOOP"):
+        global _native_comm_failed
+        if self._native is not None or os.environ.get("FDX_PY_LOOP") or _native_comm_failed:
             return self._native
         lib = _lib.load()
         if getattr(self.comm, "native_handle", None) is not None:   # a comm that brings its own libfdx communicator (thread ranks
@@ -360,7 +382,7 @@ class ShardedFlashDeconv:
             if h.value:
                 lib.fdx_comm_destroy(h)
             self.native_error_ = err or "libfdx's RCCL communicator could not be created on another rank"
-            os.environ["FDX_PY_LOOP"] = "1"          # do not try again in this process
+            _native_comm_failed = True
             warnings.warn(f"libfdx could not create its own RCCL communicator on every rank ({self.native_error_}); the sharded fit falls "
                           "back to the Python exchange loop over torch.distributed", RuntimeWarning, stacklevel=2)
             return None
@@ -372,22 +394,25 @@ class ShardedFlashDeconv:
         import torch
         rep = {"rank": int(self.comm.rank), "device": int(torch.cuda.current_device()), "plan_route": self.plan_route_,
                "loop": "native" if self._native is not None else "python", "rccl_ranks": None,
-               "native_comm_error": getattr(self, "native_error_", None)}
+               "native_comm_error": self.native_error_}
         if self._native is not None:
             c = ctypes.c_int32(0)
             _lib.check(_lib.load().fdx_comm_rccl_count(self._native, ctypes.byref(c)))
             rep["rccl_ranks"] = int(c.value)
         return rep
 
-    def close(self):
-        if self._native is not None:
-            if not getattr(self, "_native_borrowed", False):
-                _lib.load().fdx_comm_destroy(self._native)
-            self._native = None
+    def _close_graphs(self):
         for g in (self._local, self._full):
             if g is not None:
                 g.close()
         self._local = self._full = None
+
+    def close(self):
+        if self._native is not None:
+            if not self._native_borrowed:
+                _lib.load().fdx_comm_destroy(self._native)
+            self._native = None
+        self._close_graphs()
 
     def _mark(self, name):
         """FDX_TRACE_DRIVER=1: host clock at the steps of plan / fit_transform (no synchronisation), printed after the fit."""
@@ -406,31 +431,43 @@ class ShardedFlashDeconv:
             print(f"[fdx-driver rank {self.comm.rank}] total {1e6 * (prev - t0):.0f} us: " + ", ".join(out), file=sys.stderr)
             self._trace = []
 
-    def _tick(self, name, t0):
-        """Stage timing for tools/dist_probe.py (FDX_DIST_TIMING=1: synchronises, so only for diagnosis)."""
+    def _tick(self, name):
+        """Stage timing for tools/dist_probe.py (FDX_DIST_TIMING=1: synchronises, so only for diagnosis): the time since the last
+        stage boundary (self._t0) goes to timings_[name]."""
         if not self._profile:
-            return t0
+            return
         import torch
         torch.cuda.current_stream().synchronize()      # this stream only: the leverage side stream keeps running
         t1 = time.perf_counter()
-        self.timings_[name] = self.timings_.get(name, 0.0) + (t1 - t0) * 1e3
-        return t1
+        self.timings_[name] = self.timings_.get(name, 0.0) + (t1 - self._t0) * 1e3
+        self._t0 = t1
+
+    @property
+    def _own_range(self):
+        """[lo, hi): this rank's range of the sorted spots."""
+        return int(self.bounds[self.comm.rank]), int(self.bounds[self.comm.rank + 1])
 
     def plan(self, coords, X=None):
         """Build the (replicated) spatial graph, cut it into shards, return the caller's ids of this rank's spots.
         With the signatures X given, their leverage SVD (one workgroup, side stream) runs under the graph build and
         the next fit_transform(Y_own, X) collects it."""
-        import torch
-        from .utils.genes import LeverageJob
-        lib = _lib.load()
         self._lev_job = None
-        self.knn_ties_ = 0
         self._mark("plan:entry")
         if X is not None:
             Xj = np.ascontiguousarray(X, dtype=np.float64)
             if Xj.shape[1] <= self.n_hvg:
-                self._lev_job = (Xj, LeverageJob(Xj))
+                self._lev_job = (Xj, _genes.LeverageJob(Xj))
         self._mark("plan:leverage job")
+        # the user's switches are read here, once: below this call the route is an argument
+        route = "allgather" if os.environ.get("FDX_PLAN_ALLGATHER") else "stepwise" if os.environ.get("FDX_PLAN_STEPWISE") else None
+        return self._plan(coords, route)
+
+    def _plan(self, coords, route):
+        """plan() proper.  route None: the queued pipeline where it applies, else the band recompute, else the exchange of the
+        lists; "stepwise": never the queued pipeline; "allgather": the exchange of the lists (also _finish_plan's remedy)."""
+        import torch
+        lib = _lib.load()
+        self.knn_ties_ = 0
         assert coords.is_cuda and coords.dtype == torch.float64
         coords = coords.contiguous()
         n, dim = coords.shape
@@ -438,172 +475,173 @@ class ShardedFlashDeconv:
             # (FlashDeconv takes the host cKDTree route there; a shard plan has no such route: say so before any work)
             raise ValueError(f"k_neighbors = {self.k_neighbors}: the sharded plan builds k-NN lists of at most 63 neighbours per spot "
                              "(FlashDeconv on one GPU takes any k; spatial_method='radius' builds denser graphs on shards)")
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        for g in (self._local, self._full):
-            if g is not None:
-                g.close()
-        self._local = self._full = None
-        t0 = time.perf_counter()
+        st = _lib.current_stream()
+        self._close_graphs()
+        self._t0 = time.perf_counter()
         h = ctypes.c_void_p()
         self.bounds = shard_bounds(n, self.comm.world)
         k = int(self.k_neighbors)
         sharded_knn = self.spatial_method == "knn" and self.comm.world > 1 and n >= 2 and k >= 1
-        self.plan_route_ = None
-        self._pending_plan = None
-        self._coords = coords
-        self.n_total_spots = n
-        self.n_own = int(self.bounds[self.comm.rank + 1] - self.bounds[self.comm.rank])
-        if (sharded_knn and dim <= 3 and 2 <= self.comm.world <= 32 and min(k, n - 1) + 1 <= 64
-                and not os.environ.get("FDX_PLAN_ALLGATHER") and not os.environ.get("FDX_PLAN_STEPWISE")):
+        self.plan_route_ = self._pending_plan = None
+        self._coords, self.n_total_spots = coords, n
+        lo, hi = self._own_range
+        self.n_own = hi - lo
+        if sharded_knn and dim <= 3 and 2 <= self.comm.world <= 32 and min(k, n - 1) + 1 <= 64 and route is None:
             # ONE queued pipeline per rank (fdx_graph_shard_knn_dev): band lists, own rows of the symmetrised graph, halo, local
             # ELL, tile tables, send lists - nothing returns to the host after the bounding box.  The counts (and the one
             # all-reduce of the plan: edges, ties, "a walk left its block") are taken over by _finish_plan(): at once when the
             # tie rule may still change the graph, otherwise behind the sketch that fit_transform queues next.
             self.plan_route_ = "band"
-            lo, hi = int(self.bounds[self.comm.rank]), int(self.bounds[self.comm.rank + 1])
             if hi > lo:
                 hl = ctypes.c_void_p()
-                _lib.check(lib.fdx_graph_shard_knn_dev(ctypes.c_void_p(coords.data_ptr()), n, dim, k, self.comm.world,
-                                                       _lib.ptr_i64(self.bounds), self.comm.rank, st, ctypes.byref(hl)))
+                _lib.check(lib.fdx_graph_shard_knn_dev(coords.data_ptr(), n, dim, k, self.comm.world, _lib.ptr_i64(self.bounds),
+                                                       self.comm.rank, st, ctypes.byref(hl)))
                 self._local = _lib.Graph(hl.value)
+                self._read_own_ids()
             else:
-                self._plan_stepwise_local(coords, lo, hi)          # a rank without rows: nothing to queue, no collective inside
-            self._mark("plan:shard_knn queued")
+                self._plan_stepwise_local(coords)          # a rank without rows: nothing to queue, no collective inside
+            self._mark("plan:shard_knn queued + perm")
             self._pending_plan = "shard"
-            perm = torch.empty(max(self.n_own, 1), dtype=torch.int32, device=coords.device)
-            _lib.check(lib.fdx_graph_perm_dev(self._local.handle, ctypes.c_void_p(perm.data_ptr()), st))
-            self.own_ids = perm[:self.n_own].long()
-            t0 = self._tick("plan_build", t0)
-            self._mark("plan:perm")
+            self._tick("plan_build")
             if self._profile:
                 self._finish_plan()
             return self.own_ids
         if sharded_knn:
-            lo, hi = int(self.bounds[self.comm.rank]), int(self.bounds[self.comm.rank + 1])
-            kk = min(k, n - 1) + 1
-            nbr = torch.empty((n, kk), dtype=torch.int32, device=coords.device)
-            cnt = torch.empty((n,), dtype=torch.int32, device=coords.device)
-            plan = ctypes.c_void_p()
-            if not os.environ.get("FDX_PLAN_ALLGATHER") and dim <= 3:      # more than 3 coordinates: exhaustive search, no band
+            nbr, cnt = self._list_buffers(coords)
+            if route != "allgather" and dim <= 3:      # more than 3 coordinates: exhaustive search, no band
                 # Band recompute ("recompute, don't communicate"): the lists of the own rows AND of the rows in the grid
                 # cells next to an own cell, which are all the rows that can point at an own row while every k-NN walk stays inside
                 # its 3 x 3 block of cells - own rows of the symmetrised graph without moving a list (include/fdx.h).  Each rank
                 # checks the condition for its own rows; the flag rides in the all-reduce of the edge counts.
                 self.plan_route_ = "band"
-                _lib.check(lib.fdx_graph_knn_lists_band_dev(ctypes.c_void_p(coords.data_ptr()), n, dim, k, lo, hi,
-                                                            ctypes.c_void_p(nbr.data_ptr()), ctypes.c_void_p(cnt.data_ptr()), st,
-                                                            ctypes.byref(plan)))
-                t0 = self._tick("plan_knn", t0)
-                _lib.check(lib.fdx_graph_from_knn_lists_dev(plan, ctypes.c_void_p(nbr.data_ptr()), ctypes.c_void_p(cnt.data_ptr()), lo, hi,
-                                                            st, ctypes.byref(h)))
-                self._full = _lib.Graph(h.value)
-                own = torch.tensor([float(self._full.info()[1]), float(self._full.knn_ties()), float(self._full.knn_far())],
-                                   dtype=torch.float64, device=coords.device)
-                self.comm.all_reduce_sum(own)
-                tot = own.cpu().numpy()
+                self._full = self._band_graph(coords, nbr, cnt, between=lambda plan: self._tick("plan_knn"))
+                tot = self._sum_over_ranks([self._full.info()[1], self._full.knn_ties(), self._full.knn_far()])
                 if tot[2] == 0:
                     self.nnz_total, self.knn_ties_ = int(round(float(tot[0]))), int(round(float(tot[1])))
                 else:       # some rank's walk left its block (very uneven density) or a band list overflowed: exchange the lists
                     self._full.close()
-                    self._full, h, plan = None, ctypes.c_void_p(), ctypes.c_void_p()
+                    self._full = None
         if sharded_knn and self._full is None:
             # sharded build by exchange: own k-NN lists -> all-gather of the list rows -> own rows of the symmetrised graph
             self.plan_route_ = "allgather"
-            _lib.check(lib.fdx_graph_knn_lists_dev(ctypes.c_void_p(coords.data_ptr()), n, dim, k, lo, hi,
-                                                   ctypes.c_void_p(nbr.data_ptr()), ctypes.c_void_p(cnt.data_ptr()), st,
+            plan = ctypes.c_void_p()
+            _lib.check(lib.fdx_graph_knn_lists_dev(coords.data_ptr(), n, dim, k, lo, hi, nbr.data_ptr(), cnt.data_ptr(), st,
                                                    ctypes.byref(plan)))
-            t0 = self._tick("plan_knn", t0)
+            self._tick("plan_knn")
             try:
                 self.comm.all_gather_rows(nbr, cnt, self.bounds)
             except Exception:
                 # a failed collective leaves the ranks out of step: release the plan (it owns device buffers; its rows of
                 # the other ranks stay marked empty) without letting a second error mask the first, and re-raise
                 nbr[:lo], nbr[hi:], cnt[:lo], cnt[hi:] = -1, -1, 0, 0
-                dead = ctypes.c_void_p()
-                lib.fdx_graph_from_knn_lists_dev(plan, ctypes.c_void_p(nbr.data_ptr()), ctypes.c_void_p(cnt.data_ptr()), lo, hi, st,
-                                                 ctypes.byref(dead))
-                if dead.value:
-                    _lib.Graph(dead.value).close()
+                try:
+                    self._symmetrise(plan, nbr, cnt).close()
+                except _lib.FdxError:
+                    pass
                 raise
-            t0 = self._tick("plan_gather", t0)
-            _lib.check(lib.fdx_graph_from_knn_lists_dev(plan, ctypes.c_void_p(nbr.data_ptr()),
-                                                        ctypes.c_void_p(cnt.data_ptr()), lo, hi, st, ctypes.byref(h)))
-            self._full = _lib.Graph(h.value)
+            self._tick("plan_gather")
+            self._full = self._symmetrise(plan, nbr, cnt)
             # nnz of the whole graph (auto lambda) and, in the same all-reduce, the spots whose k-th neighbour is tied
-            own_nnz = torch.tensor([float(self._full.info()[1]), float(self._full.knn_ties())], dtype=torch.float64,
-                                   device=coords.device)
-            self.comm.all_reduce_sum(own_nnz)
-            tot = own_nnz.cpu().numpy()
+            tot = self._sum_over_ranks([self._full.info()[1], self._full.knn_ties()])
             self.nnz_total, self.knn_ties_ = int(round(float(tot[0]))), int(round(float(tot[1])))
         elif not sharded_knn:
             # "radius" / "grid" resolve their radius exactly as FlashDeconv does (utils/graph.py:163-212)
             method, gk, gradius = self._proto._graph_request(coords, None)
             if method == _lib.GRAPH_RADIUS and self.comm.world > 1 and n >= 2:
                 # sharded build: a radius graph is symmetric by construction, the own rows need no exchange
-                lo, hi = int(self.bounds[self.comm.rank]), int(self.bounds[self.comm.rank + 1])
-                _lib.check(lib.fdx_graph_build_radius_rows_dev(ctypes.c_void_p(coords.data_ptr()), n, dim, float(gradius), lo, hi, st,
-                                                               ctypes.byref(h)))
+                _lib.check(lib.fdx_graph_build_radius_rows_dev(coords.data_ptr(), n, dim, float(gradius), lo, hi, st, ctypes.byref(h)))
                 self._full = _lib.Graph(h.value)
-                own_nnz = torch.tensor([float(self._full.info()[1])], dtype=torch.float64, device=coords.device)
-                self.comm.all_reduce_sum(own_nnz)                           # nnz of the whole graph (auto lambda)
-                self.nnz_total = int(round(float(own_nnz.item())))
+                self.nnz_total = int(round(float(self._sum_over_ranks([self._full.info()[1]])[0])))    # (auto lambda)
             else:
-                _lib.check(lib.fdx_graph_build_dev(ctypes.c_void_p(coords.data_ptr()), n, dim, method, gk, float(gradius), st,
-                                                   ctypes.byref(h)))
+                _lib.check(lib.fdx_graph_build_dev(coords.data_ptr(), n, dim, method, gk, float(gradius), st, ctypes.byref(h)))
                 self._full = _lib.Graph(h.value)
                 self.nnz_total = self._full.info()[1]
                 self.knn_ties_ = self._full.knn_ties() if method == _lib.GRAPH_KNN else 0
-        t0 = self._tick("plan_build", t0)
-        self._resolve_ties_and_localize(coords, st, t0)
+        self._tick("plan_build")
+        self._resolve_ties_and_localize(coords)
         return self.own_ids
 
-    def _plan_stepwise_local(self, coords, lo, hi):
-        """This rank's local graph by the three stepwise calls of the band route (lists of own rows + band, own rows of the
-        symmetrised graph, localize) - no collective inside: the remedy when a bound of the queued pipeline was too small, and
-        the path of a rank that owns no row."""
+    def _sum_over_ranks(self, counts):
+        """A few counts of this rank's part of the plan, summed over the ranks (one all-reduce, read back)."""
         import torch
-        lib = _lib.load()
+        t = torch.tensor([float(c) for c in counts], dtype=torch.float64, device=self._coords.device)
+        self.comm.all_reduce_sum(t)
+        return t.cpu().numpy()
+
+    def _list_buffers(self, coords):
+        """(nbr, cnt): the k-NN lists of all n spots (self included) and their lengths, to be filled on the device."""
+        import torch
+        n = coords.shape[0]
+        kk = min(int(self.k_neighbors), n - 1) + 1
+        return (torch.empty((n, kk), dtype=torch.int32, device=coords.device),
+                torch.empty((n,), dtype=torch.int32, device=coords.device))
+
+    def _symmetrise(self, plan, nbr, cnt):
+        """This rank's rows of the symmetrised graph from the lists (a full-size graph for _localize); consumes the plan."""
+        lo, hi = self._own_range
+        h = ctypes.c_void_p()
+        _lib.check(_lib.load().fdx_graph_from_knn_lists_dev(plan, nbr.data_ptr(), cnt.data_ptr(), lo, hi, _lib.current_stream(),
+                                                            ctypes.byref(h)))
+        return _lib.Graph(h.value)
+
+    def _band_graph(self, coords, nbr, cnt, between=None):
+        """The stepwise band route without a collective: the lists of the own rows and of the band around them, then
+        _symmetrise.  between(plan) runs between the two, where the lists can still be replaced."""
         n, dim = coords.shape
-        k = int(self.k_neighbors)
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        kk = min(k, n - 1) + 1
-        nbr = torch.empty((n, kk), dtype=torch.int32, device=coords.device)
-        cnt = torch.empty((n,), dtype=torch.int32, device=coords.device)
-        plan, h, hl = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-        _lib.check(lib.fdx_graph_knn_lists_band_dev(ctypes.c_void_p(coords.data_ptr()), n, dim, k, lo, hi,
-                                                    ctypes.c_void_p(nbr.data_ptr()), ctypes.c_void_p(cnt.data_ptr()), st, ctypes.byref(plan)))
-        _lib.check(lib.fdx_graph_from_knn_lists_dev(plan, ctypes.c_void_p(nbr.data_ptr()), ctypes.c_void_p(cnt.data_ptr()), lo, hi,
-                                                    st, ctypes.byref(h)))
-        full = _lib.Graph(h.value)
-        self._step_counts = (float(full.info()[1]), float(full.knn_ties()), float(full.knn_far()))
-        _lib.check(lib.fdx_graph_localize(full.handle, self.comm.world, _lib.ptr_i64(self.bounds), self.comm.rank, st, ctypes.byref(hl)))
+        lo, hi = self._own_range
+        plan = ctypes.c_void_p()
+        _lib.check(_lib.load().fdx_graph_knn_lists_band_dev(coords.data_ptr(), n, dim, int(self.k_neighbors), lo, hi, nbr.data_ptr(),
+                                                            cnt.data_ptr(), _lib.current_stream(), ctypes.byref(plan)))
+        if between is not None:
+            between(plan)
+        return self._symmetrise(plan, nbr, cnt)
+
+    def _read_own_ids(self):
+        """own_ids: the caller's ids of the own spots, in the local graph's (Morton) order."""
+        import torch
+        perm = torch.empty(max(self.n_own, 1), dtype=torch.int32, device=self._coords.device)
+        _lib.check(_lib.load().fdx_graph_perm_dev(self._local.handle, perm.data_ptr(), _lib.current_stream()))
+        self.own_ids = perm[:self.n_own].long()
+
+    def _localize(self, full):
+        """This rank's local graph (own rows + halo bookkeeping) cut out of `full`, which is closed; own_ids follow it."""
+        hl = ctypes.c_void_p()
+        _lib.check(_lib.load().fdx_graph_localize(full.handle, self.comm.world, _lib.ptr_i64(self.bounds), self.comm.rank,
+                                                  _lib.current_stream(), ctypes.byref(hl)))
         full.close()
         if self._local is not None:
             self._local.close()
         self._local = _lib.Graph(hl.value)
-        self.plan_rebuilt_stepwise_ = True          # (diagnostic: this rank's graph came from the remedy / the no-row path)
+        self._read_own_ids()
 
-    def _ties_remedy_lists(self, coords, st):
+    def _plan_stepwise_local(self, coords):
+        """This rank's local graph by the stepwise calls of the band route (lists of own rows + band, own rows of the
+        symmetrised graph, localize) - no collective inside: the remedy when a bound of the queued pipeline was too small (same
+        rows, same order, exact sizes), and the path of a rank that owns no row."""
+        nbr, cnt = self._list_buffers(coords)
+        full = self._band_graph(coords, nbr, cnt)
+        self._step_counts = (float(full.info()[1]), float(full.knn_ties()), float(full.knn_far()))
+        self._localize(full)
+        self.plan_rebuilt_stepwise_ = True
+
+    def _ties_remedy_lists(self, coords):
         """The reference's neighbour lists (cKDTree's choice among equidistant candidates) for this rank's own rows and band, in
-        place of the device's index-rule lists; then the stepwise symmetrise + localize.  Needs the band to hold every row that
-        can point at an own row - the same condition as the band recompute itself (no far walk: checked before this is called)."""
+        place of the device's index-rule lists; then the stepwise symmetrise + localize (the same Morton range as before).  Needs
+        the band to hold every row that can point at an own row - the same condition as the band recompute itself (no far walk:
+        checked before this is called)."""
         import torch
         from .utils.graph import _ckdtree_restatement_matches_scipy
         lib = _lib.load()
         n, dim = coords.shape
-        k = int(self.k_neighbors)
-        kk = min(k, n - 1) + 1
-        lo, hi = int(self.bounds[self.comm.rank]), int(self.bounds[self.comm.rank + 1])
-        dev = coords.device
-        nbr = torch.empty((n, kk), dtype=torch.int32, device=dev)
-        cnt = torch.empty((n,), dtype=torch.int32, device=dev)
-        plan, h, hl = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-        _lib.check(lib.fdx_graph_knn_lists_band_dev(ctypes.c_void_p(coords.data_ptr()), n, dim, k, lo, hi,
-                                                    ctypes.c_void_p(nbr.data_ptr()), ctypes.c_void_p(cnt.data_ptr()), st, ctypes.byref(plan)))
-        perm_t = torch.empty(n, dtype=torch.int32, device=dev)
-        _lib.check(lib.fdx_graph_plan_order_dev(plan, ctypes.c_void_p(perm_t.data_ptr()), None, st))
-        rows_pos = torch.nonzero(cnt > 0).flatten()                       # own rows + band: the rows that have lists
-        if rows_pos.numel():
+        st = _lib.current_stream()
+        nbr, cnt = self._list_buffers(coords)
+
+        def reference_lists(plan):
+            perm_t = torch.empty(n, dtype=torch.int32, device=coords.device)
+            _lib.check(lib.fdx_graph_plan_order_dev(plan, perm_t.data_ptr(), None, st))
+            rows_pos = torch.nonzero(cnt > 0).flatten()                       # own rows + band: the rows that have lists
+            if not rows_pos.numel():
+                return
             ids = np.ascontiguousarray(_lib.tensor_to_host(perm_t[rows_pos].long()))
             cd = coords if (coords.dtype == torch.float64 and coords.is_contiguous()) else coords.double().contiguous()
             _ckdtree_restatement_matches_scipy()
@@ -613,97 +651,68 @@ class ShardedFlashDeconv:
             lib.fdx_kdtree_set_threads(int(share))
             # the restated tree on the host, its queries for these rows on the device; the answers (caller ids, self included) go to
             # solver positions, self dropped (utils/graph.py:70-74), at the rows' positions
-            _lib.check(lib.fdx_graph_plan_set_ckdtree_lists_dev(plan, None, ctypes.c_void_p(cd.data_ptr()), n, dim,
-                                                                ids.ctypes.data, len(ids), ctypes.c_void_p(nbr.data_ptr()),
-                                                                ctypes.c_void_p(cnt.data_ptr()), st))
+            _lib.check(lib.fdx_graph_plan_set_ckdtree_lists_dev(plan, None, cd.data_ptr(), n, dim, ids.ctypes.data, len(ids),
+                                                                nbr.data_ptr(), cnt.data_ptr(), st))
             lib.fdx_kdtree_set_threads(0)
-        _lib.check(lib.fdx_graph_from_knn_lists_dev(plan, ctypes.c_void_p(nbr.data_ptr()), ctypes.c_void_p(cnt.data_ptr()), lo, hi,
-                                                    st, ctypes.byref(h)))
-        full = _lib.Graph(h.value)
-        own = torch.tensor([float(full.info()[1])], dtype=torch.float64, device=dev)
-        self.comm.all_reduce_sum(own)                                        # edges of the reference's graph (auto lambda)
-        self.nnz_total = int(round(float(own.item())))
-        _lib.check(lib.fdx_graph_localize(full.handle, self.comm.world, _lib.ptr_i64(self.bounds), self.comm.rank, st, ctypes.byref(hl)))
-        full.close()
-        if self._local is not None:
-            self._local.close()
-        self._local = _lib.Graph(hl.value)
-        perm = torch.empty(max(self.n_own, 1), dtype=torch.int32, device=dev)
-        _lib.check(lib.fdx_graph_perm_dev(self._local.handle, ctypes.c_void_p(perm.data_ptr()), st))
-        self.own_ids = perm[:self.n_own].long()                              # the same Morton range as before
+
+        full = self._band_graph(coords, nbr, cnt, between=reference_lists)
+        self.nnz_total = int(round(float(self._sum_over_ranks([full.info()[1]])[0])))    # edges of the reference's graph (auto lambda)
+        self._localize(full)
 
     def _finish_plan(self, totals=None):
         """Second half of a queued plan (fdx_graph_shard_knn_dev): wait for the counts, all-reduce (edges, tied rows, far flag),
         apply the remedies (a bound too small: this rank rebuilds stepwise; a far walk anywhere: every rank rebuilds by the list
         exchange; ties under "auto" / "ckdtree": the reference's neighbour choice), halo bookkeeping.  totals: (edges, tied rows,
         far) already all-reduced by fdx_shard_fit_dev."""
-        if getattr(self, "_pending_plan", None) is None:
+        if self._pending_plan is None:
             return
-        import torch
         lib = _lib.load()
         self._pending_plan = None
         coords = self._coords
-        n = coords.shape[0]
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        t0 = time.perf_counter()
-        lo, hi = int(self.bounds[self.comm.rank]), int(self.bounds[self.comm.rank + 1])
+        self._t0 = time.perf_counter()
+        lo, hi = self._own_range
         if hi > lo:
             nnz, ties, far, over = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int32(0)
             _lib.check(lib.fdx_graph_shard_status(self._local.handle, ctypes.byref(nnz), ctypes.byref(ties), ctypes.byref(far),
                                                   ctypes.byref(over)))
             counts = (float(nnz.value), float(ties.value), float(far.value))
             if over.value and not far.value and not (totals is not None and totals[2]):
-                self._plan_stepwise_local(coords, lo, hi)          # same rows, same order, exact sizes
+                self._plan_stepwise_local(coords)
                 counts = self._step_counts
         else:
             counts = self._step_counts
         self._mark("finish_plan:status")
-        if totals is None:
-            own = torch.tensor(counts, dtype=torch.float64, device=coords.device)
-            self.comm.all_reduce_sum(own)
-            tot = own.cpu().numpy()
-        else:
-            tot = np.asarray(totals, dtype=np.float64)
-        t0 = self._tick("plan_counts", t0)
+        tot = self._sum_over_ranks(counts) if totals is None else np.asarray(totals, dtype=np.float64)
+        self._tick("plan_counts")
         self._mark("finish_plan:allreduce+cpu")
         if tot[2] != 0:
             # some rank's walk left its block (very uneven density) or a band list overflowed: every rank rebuilds by the exchange
-            self._local.close()
-            self._local = None
-            prev = os.environ.get("FDX_PLAN_ALLGATHER")
-            os.environ["FDX_PLAN_ALLGATHER"] = "1"
-            try:
-                lev = getattr(self, "_lev_job", None)
-                self.plan(coords)
-                self._lev_job = lev
-            finally:
-                if prev is None:
-                    del os.environ["FDX_PLAN_ALLGATHER"]
-                else:
-                    os.environ["FDX_PLAN_ALLGATHER"] = prev
+            # (the leverage job that plan() queued stays where it is)
+            self._plan(coords, "allgather")
             return
         self.nnz_total, self.knn_ties_ = int(round(float(tot[0]))), int(round(float(tot[1])))
         self._full = None
-        self._resolve_ties_and_localize(coords, st, t0, localized=True)
+        self._resolve_ties_and_localize(coords, localized=True)
 
-    def _resolve_ties_and_localize(self, coords, st, t0, localized=False):
+    def _resolve_ties_and_localize(self, coords, localized=False):
         """Tail of plan(): the reference's tie order when asked for, the local graph of this rank, its halo bookkeeping."""
         import torch
         lib = _lib.load()
         n = coords.shape[0]
+        st = _lib.current_stream()
         self.knn_ties_resolved_ = False
-        if (getattr(self, "knn_ties_", 0) and self.spatial_method == "knn" and self.knn_ties != "index" and self.comm.world > 1
+        if (self.knn_ties_ and self.spatial_method == "knn" and self.knn_ties != "index" and self.comm.world > 1
                 and coords.shape[1] <= 3 and not os.environ.get("FDX_TIES_FULL_GRAPH")):
             # The device builds chose among equidistant neighbours by spot index; the reference takes whichever cKDTree's query
             # meets first.  The shards stay what they are (Morton ranges: own_ids do not change): every rank asks the restated
             # tree (csrc/kdtree_order.cpp: the tree of all points - O(n log n) on the host - but only the queries of its own rows
             # and of its band) for the reference's lists, puts them in the place of the device's, and symmetrises / localises as
             # before - the reference's rows index for index.
-            self._ties_remedy_lists(coords, st)
+            self._ties_remedy_lists(coords)
             self.plan_route_ = "ckdtree-lists"
             self.knn_ties_resolved_ = True
             localized = True
-        elif getattr(self, "knn_ties_", 0) and self.spatial_method == "knn" and self.knn_ties != "index":
+        elif self.knn_ties_ and self.spatial_method == "knn" and self.knn_ties != "index":
             # (one rank, or more than 3 coordinates) every rank builds the reference's whole graph on the host and takes its rows;
             # the graph is in the CALLER's order (no Morton sort), so a shard is a range of the caller's spot numbers.
             from .utils.graph import ckdtree_knn_adjacency
@@ -715,25 +724,12 @@ class ShardedFlashDeconv:
             self.plan_route_ = "ckdtree"
             self.knn_ties_resolved_ = True
             localized = False
-        if getattr(self, "knn_ties_", 0) and not self.knn_ties_resolved_ and self.comm.rank == 0:
-            import warnings
-            warnings.warn(f"k-NN ties: {self.knn_ties_} of {n} spots have their k-th and (k+1)-th nearest neighbours at exactly the "
-                          "same distance (regular lattice?): the neighbour graph depends on how ties are broken - here by spot "
-                          "index, in the reference by cKDTree's traversal order.  spatial_method='grid' builds a tie-free graph "
-                          "on lattices.", UserWarning, stacklevel=2)
-        self.n_total_spots = n
+        if self.knn_ties_ and not self.knn_ties_resolved_ and self.comm.rank == 0:
+            _warn_knn_ties(self.knn_ties_, n, stacklevel=2)
         if not localized:
-            hl = ctypes.c_void_p()
-            _lib.check(lib.fdx_graph_localize(self._full.handle, self.comm.world, _lib.ptr_i64(self.bounds), self.comm.rank, st,
-                                              ctypes.byref(hl)))
-            if self._local is not None:
-                self._local.close()
-            self._local = _lib.Graph(hl.value)
-            t0 = self._tick("plan_localize", t0)
-            self.n_own = int(self.bounds[self.comm.rank + 1] - self.bounds[self.comm.rank])
-            perm = torch.empty(max(self.n_own, 1), dtype=torch.int32, device=coords.device)
-            _lib.check(lib.fdx_graph_perm_dev(self._local.handle, ctypes.c_void_p(perm.data_ptr()), st))
-            self.own_ids = perm[:self.n_own].long()
+            full, self._full = self._full, None
+            self._localize(full)
+            self._tick("plan_localize")
         self.own_nnz_ = int(self._local.info()[1])
         n_halo = ctypes.c_int64(0)
         sc = np.zeros(self.comm.world, dtype=np.int32)
@@ -741,97 +737,71 @@ class ShardedFlashDeconv:
         _lib.check(lib.fdx_graph_halo_info(self._local.handle, ctypes.byref(n_halo), _lib.ptr_i32(sc), _lib.ptr_i32(rc)))
         self.n_halo = int(n_halo.value)
         sidx = torch.empty(max(int(sc.sum()), 1), dtype=torch.int32, device=coords.device)
-        _lib.check(lib.fdx_graph_send_indices_dev(self._local.handle, ctypes.c_void_p(sidx.data_ptr()), st))
+        _lib.check(lib.fdx_graph_send_indices_dev(self._local.handle, sidx.data_ptr(), st))
         self._halo = HaloExchange(self.comm, self.n_own, sidx[:int(sc.sum())].long(), sc, rc)
         self._mark("plan:halo lists")
-        self._tick("plan_lists", t0)
+        self._tick("plan_lists")
 
     def fit_transform(self, Y_own, X):
         import torch
-        from .core.sketching import countsketch_tables
         # Every libfdx call of this driver is enqueued on torch's CURRENT stream, except the gene statistics and the column
         # gather (G > n_hvg), which use the legacy default stream: under a non-default, non-blocking torch stream those two
         # would not be ordered after the producer of Y_own, so that combination is refused rather than raced.
         if Y_own.shape[1] > self.n_hvg and torch.cuda.current_stream() != torch.cuda.default_stream():
             raise RuntimeError("ShardedFlashDeconv with gene selection active must run on torch's default stream")
-        from .utils.genes import compute_leverage_scores
         lib = _lib.load()
         dev = Y_own.device
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        st = _lib.current_stream()
         X = np.ascontiguousarray(X, dtype=np.float64)
         K, G = X.shape
         if _lib.is_torch_sparse_csr(Y_own):
             return self._fit_transform_csr(Y_own, X)
         self._mark("fit:entry")
         # integer counts keep the float64 transform chain, as in FlashDeconv.fit (numpy promotes them: core/deconv.py:190-191)
-        from .core.deconv import device_counts_as_float
         Y_own, y_f64_math = device_counts_as_float(Y_own)
         assert Y_own.shape == (self.n_own, G)
-        y_code = _lib.FDX_F32 if Y_own.dtype == torch.float32 else _lib.FDX_F64
+        y_code = _lib.dtype_code(Y_own)
         self.gene_idx_ = np.arange(G, dtype=np.intp)
         if G > self.n_hvg:
             # gene selection over ALL spots (utils/genes.py:293-341): every rank reduces its own rows to per-gene sums of
             # z = log1p(CPM-10k) and z^2 (fdx_gene_moments_dev), one all-reduce(SUM) of 2G doubles makes them global, the
             # ranking of the G-vector and the marker table are replicated host work
-            from .utils import genes as _genes
-            sums = torch.zeros((2, G), dtype=torch.float64, device=dev)
-            if self.n_own:
-                mean_r, var_r = _genes.gene_moments_device(ctypes.c_void_p(Y_own.data_ptr()), y_code, self.n_own, G, G)
-                sums[0], sums[1] = combine_moment_sums(mean_r, var_r, self.n_own, dev)
-            self.comm.all_reduce_sum(sums)
-            mean, var = moments_from_sums(_lib.tensor_to_host(sums[0]), _lib.tensor_to_host(sums[1]), self.n_total_spots)
-            hvg = _genes._hvg_from_moments(mean, var, self.n_hvg, 0.0125, 3.0, 0.5)
-            markers, _ = _genes.select_markers(X, n_markers=self.n_markers_per_type)
-            self.gene_idx_ = np.union1d(hvg, markers).astype(np.intp)
-            if len(self.gene_idx_) == 0:
-                raise ValueError("No genes selected. Increase n_hvg or n_markers_per_type.")
+            def moments():
+                sums = torch.zeros((2, G), dtype=torch.float64, device=dev)
+                if self.n_own:
+                    mean_r, var_r = _genes.gene_moments_device(Y_own.data_ptr(), y_code, self.n_own, G, G)
+                    sums[0], sums[1] = combine_moment_sums(mean_r, var_r, self.n_own, dev)
+                self.comm.all_reduce_sum(sums)
+                return moments_from_sums(_lib.tensor_to_host(sums[0]), _lib.tensor_to_host(sums[1]), self.n_total_spots)
+            self.gene_idx_ = _genes.select_gene_idx(X, self.n_hvg, self.n_markers_per_type, moments)
             gi32 = np.ascontiguousarray(self.gene_idx_, dtype=np.int32)
             Y_sel = torch.empty((self.n_own, len(gi32)), dtype=Y_own.dtype, device=dev)
             if self.n_own:
-                _lib.check(lib.fdx_gather_columns_dev(ctypes.c_void_p(Y_own.data_ptr()), y_code, self.n_own, G, G,
-                                                      _lib.ptr_i32(gi32), len(gi32), ctypes.c_void_p(Y_sel.data_ptr()), st))
+                _lib.check(lib.fdx_gather_columns_dev(Y_own.data_ptr(), y_code, self.n_own, G, G, _lib.ptr_i32(gi32), len(gi32),
+                                                      Y_sel.data_ptr(), st))
             Y_own, X = Y_sel, np.ascontiguousarray(X[:, self.gene_idx_])
             G = len(gi32)
-        t0 = time.perf_counter()
-        job, self._lev_job = getattr(self, "_lev_job", None), None
-        self._x_dev_job = None
-        if job is not None and job[0].shape == X.shape and np.array_equal(job[0], X):
-            lev = job[1].result(keep_x=True)       # the job's device copy of X serves the native fit below (no second upload)
-            self._x_dev_job = job[1]
-        else:
-            lev = compute_leverage_scores(X)
-        t0 = self._tick("leverage", t0)
+        self._t0 = time.perf_counter()
+        lev = self._collect_leverage(X, keep_x=True)   # the job's device copy of X serves the native fit below (no second upload)
+        self._tick("leverage")
         self._mark("fit:leverage")
-        bucket, weight = countsketch_tables(G, self.sketch_dim, lev, self.random_state)
-        weight_y = weight_x = weight
-        mode_y = mode_x = _lib.PRE_RAW
-        if self.preprocess == "log_cpm":
-            mode_y = mode_x = _lib.PRE_LOG_CPM
-            if y_f64_math and Y_own.dtype == torch.float32:
-                mode_y |= _lib.PRE_F64_MATH
-        elif self.preprocess == "pearson":
+
+        def y_colsum():
             sums = np.zeros(G)
             if self.n_own:
-                _lib.check(lib.fdx_column_sums_dev(ctypes.c_void_p(Y_own.data_ptr()), _lib.FDX_F32 if Y_own.dtype == torch.float32 else _lib.FDX_F64,
-                                                   self.n_own, G, G, _lib.ptr_f64(sums), st))
+                _lib.check(lib.fdx_column_sums_dev(Y_own.data_ptr(), y_code, self.n_own, G, G, _lib.ptr_f64(sums), st))
             tsum = torch.from_numpy(sums).to(dev)
             self.comm.all_reduce_sum(tsum)
-            mu_y = _lib.tensor_to_host(tsum) / self.n_total_spots + 1e-6
-            mu_x = X.mean(axis=0) + 1e-6
-            weight_y = weight / np.sqrt(mu_y + mu_y ** 2 / 100.0)
-            weight_x = weight / np.sqrt(mu_x + mu_x ** 2 / 100.0)
-        elif self.preprocess != "raw":
-            raise ValueError(f"Unknown preprocess method: {self.preprocess}. Choose from 'log_cpm', 'pearson', or 'raw'.")
-        t0 = self._tick("tables", t0)
+            return _lib.tensor_to_host(tsum)
+        tables = sketch_tables(G, self.sketch_dim, lev, self.random_state, self.preprocess, X,
+                               f64_math=y_f64_math and y_code == _lib.FDX_F32, y_colsum=y_colsum, n_spots=self.n_total_spots)
+        self._tick("tables")
         self._mark("fit:tables")
-        n_own = self.n_own
-        b32 = np.ascontiguousarray(bucket, dtype=np.int32)
-        wy, wx = _lib.as_f64(weight_y), _lib.as_f64(weight_x)
         try:
             for attempt in range(2):
                 # the whole rest of the fit in ONE native call (csrc/comm.cpp: fdx_shard_fit_dev) when libfdx owns the communicator;
                 # a status (far walk / bound too small / ties) sends the plan through its remedy and, with the final graph, back here
-                done = self._fit_native(Y_own, y_code, X, K, G, b32, wy, wx, mode_y, mode_x)
+                done = self._fit_native(Y_own, X, K, G, tables)
                 if done is not False:
                     break
         finally:
@@ -840,36 +810,59 @@ class ShardedFlashDeconv:
                 self._x_dev_job = None
         if done:
             return self.proportions_
-        ld = ((n_own + 1 + 63) // 64) * 64          # H is read for the own rows only: its stride does not wait for the halo count
+        prepared = self._prepare_shard(Y_own, None, X, K, G, tables)
+        self._tick("prepare")
+        self._mark("fit:prepare")
+        return self._solve_shard(*prepared)
+
+    def _collect_leverage(self, X, keep_x=False):
+        """The leverage scores of the signatures X: from the job plan(coords, X) queued, when it was queued for this very
+        matrix.  keep_x: the job keeps its device copy of X (self._x_dev_job, until release_x())."""
+        job, self._lev_job = self._lev_job, None
+        self._x_dev_job = None
+        if job is None or job[0].shape != X.shape or not np.array_equal(job[0], X):
+            return _genes.compute_leverage_scores(X)
+        if keep_x:
+            self._x_dev_job = job[1]
+        return job[1].result(keep_x=keep_x)
+
+    def _prepare_shard(self, Y_own, gene_idx32, X, K, G, tables):
+        """H = X_sketch Y_sketch^T of the own rows, X_sketch X_sketch^T (device and host) and this shard's part of YtY - the
+        buffers and the one call that fills them: dense rows, or a CsrOnDevice with the columns gene_idx32 to keep.  Returns
+        the arguments of _solve_shard."""
+        import torch
+        lib = _lib.load()
+        b32, wy, wx, mode_y, mode_x = tables
+        dev = self._coords.device
+        ld = ((self.n_own + 1 + 63) // 64) * 64          # H is read for the own rows only: its stride does not wait for the halo count
         H = torch.zeros((K, ld), dtype=torch.float64, device=dev)
         XtX = torch.empty((K, K), dtype=torch.float64, device=dev)
         XtX_h = np.empty((K, K))
         yty = ctypes.c_double(0.0)
-        _lib.check(lib.fdx_prepare_dev(ctypes.c_void_p(Y_own.data_ptr()), _lib.FDX_F32 if Y_own.dtype == torch.float32 else _lib.FDX_F64,
-                                       n_own, G, G, None, _lib.ptr_f64(X), K, _lib.ptr_i32(b32), _lib.ptr_f64(wy), _lib.ptr_f64(wx),
-                                       int(self.sketch_dim), mode_y, mode_x, ctypes.c_void_p(H.data_ptr()), ld,
-                                       ctypes.c_void_p(XtX.data_ptr()), _lib.ptr_f64(XtX_h), ctypes.byref(yty), st))
-        t0 = self._tick("prepare", t0)
-        self._mark("fit:prepare")
-        return self._solve_shard(H, XtX, XtX_h, yty.value, K, ld)
+        rest = (_lib.ptr_f64(X), K, _lib.ptr_i32(b32), _lib.ptr_f64(wy), _lib.ptr_f64(wx), int(self.sketch_dim), mode_y, mode_x,
+                H.data_ptr(), ld, XtX.data_ptr(), _lib.ptr_f64(XtX_h), ctypes.byref(yty), _lib.current_stream())
+        if isinstance(Y_own, _lib.CsrOnDevice):
+            _lib.check(lib.fdx_prepare_csr_dev(ctypes.byref(Y_own.view), _lib.ptr_i32(gene_idx32), G, *rest))
+        else:
+            _lib.check(lib.fdx_prepare_dev(Y_own.data_ptr(), _lib.dtype_code(Y_own), self.n_own, G, G, None, *rest))
+        return H, XtX, XtX_h, yty.value, K, ld
 
-    def _fit_native(self, Y_own, y_code, X, K, G, b32, wy, wx, mode_y, mode_x):
+    def _fit_native(self, Y_own, X, K, G, tables):
         """fdx_shard_fit_dev: sketch -> H, the plan's counts all-reduced beside it, lambda, the loop, objective, export - one
         call.  True: done (results set); False: a remedy was applied to the plan, call again; None: not applicable here (the
         process group is not libfdx's own communicator, more than 96 cell types, a rank without rows, sweeps being timed)."""
         import torch
         # every rank must take the same route (the native call all-reduces on libfdx's communicator, the stepwise flow on
         # torch's): the conditions are properties of the JOB - a rank without rows anywhere sends all ranks the stepwise way
-        if (os.environ.get("FDX_NO_SHARD_FIT") or getattr(self, "time_sweeps", False) or K > 96 or self._local is None
+        if (os.environ.get("FDX_NO_SHARD_FIT") or self.time_sweeps or K > 96 or self._local is None
                 or bool(np.any(np.diff(self.bounds) <= 0))):
             return None
         native = self.native_comm()
         if native is None:
             return None
-        lib = _lib.load()
+        b32, wy, wx, mode_y, mode_x = tables
         dev = Y_own.device
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        pending = getattr(self, "_pending_plan", None) is not None
+        pending = self._pending_plan is not None
         prm = _lib.ShardFitParams()
         prm.sketch_dim, prm.mode_y, prm.mode_x = int(self.sketch_dim), int(mode_y), int(mode_x)
         prm.lambda_auto = 1 if self.lambda_spatial == "auto" else 0
@@ -878,8 +871,7 @@ class ShardedFlashDeconv:
         prm.stop_on_ties = 1 if (pending and self.spatial_method == "knn" and self.knn_ties != "index") else 0
         prm.n_total_spots = int(self.n_total_spots)
         prm.nnz_total = -1 if pending else int(self.nnz_total)
-        xj = getattr(self, "_x_dev_job", None)
-        prm.X_dev = getattr(xj, "x_dev", None) if xj is not None else None
+        prm.X_dev = self._x_dev_job.x_dev if self._x_dev_job is not None else None
         if getattr(self.comm, "loopback", False) and pending:               # measurement: the job's total, known to the stand-in
             tot = getattr(self.comm, "totals", {}).get((3,))
             if tot is not None:
@@ -888,10 +880,10 @@ class ShardedFlashDeconv:
         rel = np.zeros(max(int(self.max_iter), 1))
         beta_t = torch.empty((self.n_own, K), dtype=torch.float64, device=dev)
         prop_t = torch.empty((self.n_own, K), dtype=torch.float64, device=dev)
-        _lib.check(lib.fdx_shard_fit_dev(native, self._local.handle, ctypes.c_void_p(Y_own.data_ptr()), y_code, self.n_own, G, G,
-                                         _lib.ptr_f64(X), K, _lib.ptr_i32(b32), _lib.ptr_f64(wy), _lib.ptr_f64(wx), ctypes.byref(prm),
-                                         ctypes.c_void_p(beta_t.data_ptr()), ctypes.c_void_p(prop_t.data_ptr()), _lib.ptr_f64(rel),
-                                         ctypes.byref(info), st))
+        _lib.check(_lib.load().fdx_shard_fit_dev(native, self._local.handle, Y_own.data_ptr(), _lib.dtype_code(Y_own), self.n_own, G, G,
+                                                 _lib.ptr_f64(X), K, _lib.ptr_i32(b32), _lib.ptr_f64(wy), _lib.ptr_f64(wx),
+                                                 ctypes.byref(prm), beta_t.data_ptr(), prop_t.data_ptr(), _lib.ptr_f64(rel),
+                                                 ctypes.byref(info), _lib.current_stream()))
         self._mark("fit:native call")
         if info.status != 0:
             # (a bound too small on some rank: that rank rebuilds, and its exact edge count enters the job's total through a fresh
@@ -905,17 +897,11 @@ class ShardedFlashDeconv:
             self.knn_ties_resolved_ = False
             self.n_halo, self.own_nnz_ = int(info.n_halo), int(info.own_nnz)
             if self.knn_ties_ and self.comm.rank == 0:
-                import warnings
-                warnings.warn(f"k-NN ties: {self.knn_ties_} of {self.n_total_spots} spots have their k-th and (k+1)-th nearest "
-                              "neighbours at exactly the same distance (regular lattice?): the neighbour graph depends on how ties "
-                              "are broken - here by spot index, in the reference by cKDTree's traversal order.  "
-                              "spatial_method='grid' builds a tie-free graph on lattices.", UserWarning, stacklevel=3)
+                _warn_knn_ties(self.knn_ties_, self.n_total_spots, stacklevel=3)
         self.beta_, self.proportions_ = beta_t, prop_t
         self.lambda_used_ = float(info.lambda_used)
-        n_it = int(info.solve.n_iterations)
-        self.info_ = {"converged": bool(info.solve.converged), "n_iterations": n_it, "final_change": float(info.solve.final_change),
-                      "rel_changes": [float(v) for v in rel[:n_it]], "final_objective": float(info.solve.final_objective),
-                      "objectives": []}
+        self.info_ = info.solve.as_dict(rel)
+        self.info_["objectives"] = []
         self.sweep_loop_ms_ = float(info.solve.sweep_ms)
         self._mark_dump()
         return True
@@ -924,65 +910,41 @@ class ShardedFlashDeconv:
         """CSR shard (the own rows as a CUDA torch.sparse_csr tensor; reference core/deconv.py:181-188, utils/genes.py:52-83):
         the rows stay sparse in HBM, gene statistics are all-reduced, selected columns are filtered inside the sketch kernel."""
         import torch
-        from .core.sketching import countsketch_tables
-        from .utils import genes as _genes
-        from .utils.genes import compute_leverage_scores
-        lib = _lib.load()
         dev = Y_own.device
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         K, G_all = X.shape
         assert tuple(Y_own.shape) == (self.n_own, G_all)
-        if self.preprocess not in ("log_cpm", "raw", "pearson"):
-            raise ValueError(f"Unknown preprocess method: {self.preprocess}. Choose from 'log_cpm', 'pearson', or 'raw'.")
         csr = _lib.CsrOnDevice.from_torch(Y_own)
         try:
             self.gene_idx_ = np.arange(G_all, dtype=np.intp)
             colsum = None
-            if G_all > self.n_hvg or self.preprocess == "pearson":
+
+            def reduced_sums():
+                """Per gene, over ALL spots: (sum z, sum z^2, sum of the counts), on the device; the last on the host."""
                 sums = torch.zeros((3, G_all), dtype=torch.float64, device=dev)
                 if self.n_own:
                     mean_r, var_r, col_r = csr.gene_moments(want_colsum=True)
                     sums[0], sums[1] = combine_moment_sums(mean_r, var_r, self.n_own, dev)
                     sums[2] = torch.from_numpy(col_r).to(dev)
                 self.comm.all_reduce_sum(sums)
-                colsum = _lib.tensor_to_host(sums[2])
-                if G_all > self.n_hvg:
-                    mean, var = moments_from_sums(_lib.tensor_to_host(sums[0]), _lib.tensor_to_host(sums[1]), self.n_total_spots)
-                    hvg = _genes._hvg_from_moments(mean, var, self.n_hvg, 0.0125, 3.0, 0.5)
-                    markers, _ = _genes.select_markers(X, n_markers=self.n_markers_per_type)
-                    self.gene_idx_ = np.union1d(hvg, markers).astype(np.intp)
-                    if len(self.gene_idx_) == 0:
-                        raise ValueError("No genes selected. Increase n_hvg or n_markers_per_type.")
+                return sums, _lib.tensor_to_host(sums[2])
+
+            def moments():
+                nonlocal colsum
+                sums, colsum = reduced_sums()
+                return moments_from_sums(_lib.tensor_to_host(sums[0]), _lib.tensor_to_host(sums[1]), self.n_total_spots)
+            if G_all > self.n_hvg:
+                self.gene_idx_ = _genes.select_gene_idx(X, self.n_hvg, self.n_markers_per_type, moments)
+            elif self.preprocess == "pearson":
+                colsum = reduced_sums()[1]
             Xs = np.ascontiguousarray(X[:, self.gene_idx_])
             G = Xs.shape[1]
-            job, self._lev_job = getattr(self, "_lev_job", None), None
-            lev = job[1].result() if (job is not None and job[0].shape == Xs.shape and np.array_equal(job[0], Xs)) else compute_leverage_scores(Xs)
-            bucket, weight = countsketch_tables(G, self.sketch_dim, lev, self.random_state)
-            weight_y = weight_x = weight
-            mode_y = mode_x = _lib.PRE_RAW
-            if self.preprocess == "log_cpm":
-                mode_y, mode_x = _lib.PRE_LOG_CPM_SPARSE, _lib.PRE_LOG_CPM
-            elif self.preprocess == "pearson":
-                mu_y = colsum[self.gene_idx_] / self.n_total_spots + 1e-6
-                mu_x = Xs.mean(axis=0) + 1e-6
-                weight_y = weight / np.sqrt(mu_y + mu_y ** 2 / 100.0)
-                weight_x = weight / np.sqrt(mu_x + mu_x ** 2 / 100.0)
-            n_own = self.n_own
-            ld = ((n_own + 1 + 63) // 64) * 64
-            H = torch.zeros((K, ld), dtype=torch.float64, device=dev)
-            XtX = torch.empty((K, K), dtype=torch.float64, device=dev)
-            XtX_h = np.empty((K, K))
-            yty = ctypes.c_double(0.0)
-            gi32 = np.ascontiguousarray(self.gene_idx_, dtype=np.int32)
-            b32 = np.ascontiguousarray(bucket, dtype=np.int32)
-            wy, wx = _lib.as_f64(weight_y), _lib.as_f64(weight_x)
-            _lib.check(lib.fdx_prepare_csr_dev(ctypes.byref(csr.view), _lib.ptr_i32(gi32), G, _lib.ptr_f64(Xs), K, _lib.ptr_i32(b32),
-                                               _lib.ptr_f64(wy), _lib.ptr_f64(wx), int(self.sketch_dim), mode_y, mode_x,
-                                               ctypes.c_void_p(H.data_ptr()), ld, ctypes.c_void_p(XtX.data_ptr()), _lib.ptr_f64(XtX_h),
-                                               ctypes.byref(yty), st))
+            lev = self._collect_leverage(Xs)
+            tables = sketch_tables(G, self.sketch_dim, lev, self.random_state, self.preprocess, Xs, y_sparse=True,
+                                   y_colsum=lambda: colsum[self.gene_idx_], n_spots=self.n_total_spots)
+            prepared = self._prepare_shard(csr, np.ascontiguousarray(self.gene_idx_, dtype=np.int32), Xs, K, G, tables)
         finally:
             csr.free()
-        return self._solve_shard(H, XtX, XtX_h, yty.value, K, ld)
+        return self._solve_shard(*prepared)
 
     def _solve_shard(self, H, XtX, XtX_h, yty_part, K, ldh):
         """Everything after H / XtX exist for the own rows: global YtY, lambda, the sharded BCD solve, the objective,
@@ -990,11 +952,11 @@ class ShardedFlashDeconv:
         import torch
         lib = _lib.load()
         dev = H.device
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        st = _lib.current_stream()
         self._finish_plan()                      # a queued plan: its counts have long arrived behind the sketch
         n_own, n_total = self.n_own, self.n_own + self.n_halo
         ld = ((n_total + 1 + 63) // 64) * 64     # abundance planes: own rows, halo, the all-zero pad row
-        t0 = time.perf_counter()
+        self._t0 = time.perf_counter()
         # YtY only enters the final objective: its sum over the ranks rides in the objective's all-reduce at the end
         dmean = diag_mean(XtX_h)
         if self.lambda_spatial == "auto":                                     # core/spatial.py:181-190
@@ -1002,7 +964,7 @@ class ShardedFlashDeconv:
         else:
             lam = float(self.lambda_spatial)
         rho_eff = float(self.rho_sparsity) * dmean                            # core/solver.py:359-360
-        t0 = self._tick("scalars", t0)
+        self._tick("scalars")
         self._mark("solve:finish_plan+scalars")
         K_real = K
         if K > 64:
@@ -1016,43 +978,41 @@ class ShardedFlashDeconv:
                 H, XtX = Hp, Gp
         backend = HipBackend(self._local, H, ldh, XtX, K, K_real=K_real)
         native = self.native_comm()
-        if native is not None and not getattr(self, "time_sweeps", False):
+        if native is not None and not self.time_sweeps:
             # the whole iteration loop in C++ on RCCL: boundary tiles first, halo traffic beside the interior sweep
             bufs = [torch.empty((K, ld), dtype=torch.float64, device=dev) for _ in range(2)]
             sinfo = _lib.SolveInfo()
             rel = np.zeros(max(int(self.max_iter), 1))
             which = ctypes.c_int32(0)
-            _lib.check(lib.fdx_sharded_solve_padded_dev(native, self._local.handle, ctypes.c_void_p(H.data_ptr()), ldh,
-                                                 ctypes.c_void_p(XtX.data_ptr()), K, K_real, float(lam), float(rho_eff), float(self.tol),
-                                                 int(self.max_iter), ctypes.c_void_p(bufs[0].data_ptr()),
-                                                 ctypes.c_void_p(bufs[1].data_ptr()), ld, ctypes.byref(sinfo), _lib.ptr_f64(rel),
-                                                 ctypes.byref(which), st))
+            _lib.check(lib.fdx_sharded_solve_padded_dev(native, self._local.handle, H.data_ptr(), ldh, XtX.data_ptr(), K, K_real,
+                                                        float(lam), float(rho_eff), float(self.tol), int(self.max_iter),
+                                                        bufs[0].data_ptr(), bufs[1].data_ptr(), ld, ctypes.byref(sinfo),
+                                                        _lib.ptr_f64(rel), ctypes.byref(which), st))
             beta = bufs[which.value]
-            info = {"converged": bool(sinfo.converged), "n_iterations": int(sinfo.n_iterations),
-                    "final_change": float(sinfo.final_change), "rel_changes": [float(v) for v in rel[:sinfo.n_iterations]]}
+            info = sinfo.as_dict(rel, objective=False)
             self.sweep_loop_ms_ = float(sinfo.sweep_ms)
         else:
             solver = ShardedSolver(backend, self.comm, self._halo, K, ld, n_own, n_total, self.max_iter, self.tol)
-            if getattr(self, "time_sweeps", False):
+            if self.time_sweeps:
                 solver.sweep_events = []
             beta, info = solver.run(lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev), lam, rho_eff)
             if solver.sweep_events:
                 torch.cuda.current_stream().synchronize()
                 real = solver.sweep_events[:info["n_iterations"]]              # later launches are post-convergence no-ops
                 self.sweep_ms_ = [a.elapsed_time(b) for a, b in real]
-        t0 = self._tick("solve", t0)
+        self._tick("solve")
         self._mark("solve:loop")
         # the export (reads the final abundances, writes two (n_own, K) matrices) runs on a side stream BESIDE the objective pass
         # (reads the same abundances), as in the single-GPU fit; the objective's read-back then waits for both
         self.beta_ = torch.empty((n_own, K_real), dtype=torch.float64, device=dev)
         self.proportions_ = torch.empty((n_own, K_real), dtype=torch.float64, device=dev)
         cur = torch.cuda.current_stream()
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             self._side = torch.cuda.Stream(device=dev, priority=-1)   # a distinct priority: same-priority streams share hardware queues and can serialise
         side = self._side
         side.wait_stream(cur)
-        _lib.check(lib.fdx_normalize_dev(ctypes.c_void_p(beta.data_ptr()), ld, n_own, K_real, ctypes.c_void_p(self.beta_.data_ptr()),
-                                         ctypes.c_void_p(self.proportions_.data_ptr()), ctypes.c_void_p(side.cuda_stream)))
+        _lib.check(lib.fdx_normalize_dev(beta.data_ptr(), ld, n_own, K_real, self.beta_.data_ptr(), self.proportions_.data_ptr(),
+                                         side.cuda_stream))
         part_h = np.concatenate([backend.objective_partials(beta), [yty_part]])
         cur.wait_stream(side)
         if self.comm.world > 1:
@@ -1064,7 +1024,7 @@ class ShardedFlashDeconv:
         YtY = float(c[4])
         info["final_objective"] = float(0.5 * (YtY - 2.0 * c[0] + c[1]) + 0.5 * lam * c[2] + rho_eff * c[3])
         info["objectives"] = []
-        self._tick("finish", t0)
+        self._tick("finish")
         self.lambda_used_, self.info_ = lam, info
         self._mark("solve:finish")
         self._mark_dump()
@@ -1128,7 +1088,7 @@ def bench_main(a, rank, world, local_rank):
     model.time_sweeps = True
     step()
     model.time_sweeps = False
-    sweep_ms = float(np.mean(model.sweep_ms_)) if getattr(model, "sweep_ms_", None) else None
+    sweep_ms = float(np.mean(model.sweep_ms_)) if model.sweep_ms_ else None
     roof = None
     if sweep_ms:
         own_nnz = int(model.own_nnz_)

@@ -33,18 +33,16 @@ def _type_sums_device(expr, codes, K, mean):
     if _lib.is_torch_sparse_csr(expr):
         csr = _lib.CsrOnDevice.from_torch(expr)
         try:
-            _lib.check(lib.fdx_type_sums_csr_dev(ctypes.byref(csr.view), ctypes.c_void_p(rows_d.data_ptr()),
-                                                 ctypes.c_void_p(off_d.data_ptr()), K, 1 if mean else 0,
-                                                 ctypes.c_void_p(X.data_ptr()), st))
+            _lib.check(lib.fdx_type_sums_csr_dev(ctypes.byref(csr.view), rows_d.data_ptr(), off_d.data_ptr(), K, 1 if mean else 0,
+                                                 X.data_ptr(), st))
             torch.cuda.synchronize(dev)
         finally:
             csr.free()
     else:
         Yd = expr if expr.dtype in (torch.float32, torch.float64) else expr.to(torch.float64)
         Yd = Yd.contiguous()
-        _lib.check(lib.fdx_type_sums_dev(ctypes.c_void_p(Yd.data_ptr()), _lib.FDX_F32 if Yd.dtype == torch.float32 else _lib.FDX_F64,
-                                         n, G, G, ctypes.c_void_p(rows_d.data_ptr()), ctypes.c_void_p(off_d.data_ptr()), K,
-                                         1 if mean else 0, ctypes.c_void_p(X.data_ptr()), st))
+        _lib.check(lib.fdx_type_sums_dev(Yd.data_ptr(), _lib.dtype_code(Yd), n, G, G, rows_d.data_ptr(), off_d.data_ptr(), K,
+                                         1 if mean else 0, X.data_ptr(), st))
     return X.cpu().numpy()
 
 

@@ -6,6 +6,9 @@
     select_informative_genes  <- utils/genes.py:293-341
 """
 import ctypes
+import os
+import sys
+import time
 
 import numpy as np
 from scipy import sparse
@@ -230,10 +233,33 @@ def _hvg_from_moments_numpy(mean, var, n_top, min_mean, max_mean, min_disp):
     return np.sort(pick)
 
 
-def select_informative_genes(Y, X, n_hvg=2000, n_markers_per_type=50):
-    hvg = select_hvg(Y, n_top=n_hvg)
-    markers, _ = select_markers(X, n_markers=n_markers_per_type)
-    gene_idx = np.union1d(hvg, markers).astype(np.intp)
+def select_gene_idx(X, n_hvg, n_markers_per_type, moments):
+    """HVGs of the spots united with the markers of the signatures X (utils/genes.py:318-341), sorted.  moments() returns the
+    per-gene (mean, ddof-1 variance) of log1p(CPM-10k) over ALL spots - a device reduction, with an all-reduce behind it on a
+    shard; the marker table depends on X only, so a helper thread ranks it meanwhile (the C calls release the GIL).  moments
+    None: no more genes than n_hvg, every one of them counts as highly variable (select_hvg's short-circuit)."""
+    import concurrent.futures
+    tr = [] if os.environ.get("FDX_TRACE_HOST") else None
+    mark = (lambda: None) if tr is None else (lambda: tr.append(time.perf_counter()))
+    mark()
+    with concurrent.futures.ThreadPoolExecutor(max_workers=1) as pool:
+        fut = pool.submit(select_markers, X, n_markers_per_type)
+        mean_var = None if moments is None else moments()
+        mark()
+        hvg = np.arange(np.shape(X)[1]) if mean_var is None else _hvg_from_moments(*mean_var, n_hvg, 0.0125, 3.0, 0.5)
+        mark()
+        markers, _ = fut.result()
+        mark()
+    gene_idx = np.union1d(hvg, markers).astype(np.intp)                  # utils/genes.py:330
+    if tr is not None:
+        mark()
+        print("[fdx-host] python select: moments (device + read-back) %.0f us, hvg ranking %.0f, wait for the marker table %.0f, "
+              "pool shutdown + union %.0f" % tuple(1e6 * (b - a) for a, b in zip(tr[:-1], tr[1:])), file=sys.stderr)
     if len(gene_idx) == 0:
         raise ValueError("No genes selected. Increase n_hvg or n_markers_per_type.")
+    return gene_idx
+
+
+def select_informative_genes(Y, X, n_hvg=2000, n_markers_per_type=50):
+    gene_idx = select_gene_idx(X, n_hvg, n_markers_per_type, (lambda: _gene_moments(Y)) if Y.shape[1] > n_hvg else None)
     return gene_idx, compute_leverage_scores(np.asarray(X)[:, gene_idx])

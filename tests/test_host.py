@@ -605,3 +605,78 @@ def test_hvg_ranking_restatement_equals_numpy():
         got = genes._hvg_from_moments(mean, var, n_top, 0.0125, 3.0, 0.5)
         want = genes._hvg_from_moments_numpy(mean, var, n_top, 0.0125, 3.0, 0.5)
         assert np.array_equal(got, want), (trial, G, n_top, mode)
+
+
+def test_sketch_tables_fold_the_preprocessing_of_the_oracle():
+    """core/sketching.py: sketch_tables against oracle/fdx_oracle.py: preprocess for the three modes.  "pearson" is a per-gene scale
+    of the CountSketch weights: Y * (weight_y / weight) must be the oracle's Y_tilde entry for entry (X likewise) within 2 machine
+    epsilons - the builder multiplies by a rounded reciprocal square root (a rounded quotient of two rounded weights) where the
+    reference divides once.  "log_cpm" and "raw" are kernel modes with countsketch_tables' own weights."""
+    import datagen
+    import fdx_oracle
+    from flashdeconv_amd import _lib
+    from flashdeconv_amd.core.sketching import countsketch_tables, sketch_tables
+    Y, X, _, _ = datagen.count_like(800, 300, 6, 0.1, 3)
+    n, G = Y.shape
+    lev = np.random.RandomState(5).rand(G) + 0.1
+    bucket, weight = countsketch_tables(G, 64, lev, 7)
+
+    def tables(pre, **kw):
+        b, wy, wx, my, mx = sketch_tables(G, 64, lev, 7, pre, X, **kw)
+        assert b.dtype == np.int32 and b.flags.c_contiguous and np.array_equal(b, bucket)
+        for w in (wy, wx):
+            assert w.dtype == np.float64 and w.flags.c_contiguous and w.shape == (G,)
+        return wy, wx, my, mx
+
+    asked = []
+
+    def colsum():
+        asked.append(1)
+        return Y.sum(axis=0).astype(np.float64)
+    for sums in (colsum, colsum()):                                       # a callable, or the sums themselves
+        wy, wx, my, mx = tables("pearson", y_colsum=sums, n_spots=n)
+        assert (my, mx) == (_lib.PRE_RAW, _lib.PRE_RAW)
+        Yt, Xt = fdx_oracle.preprocess(Y, X, "pearson")
+        eps = np.finfo(np.float64).eps
+        for name, got, want in (("Y", Y * (wy / weight), Yt), ("X", X * (wx / weight), Xt)):
+            err = float(np.max(np.abs(got - want) / np.abs(np.where(want == 0, 1.0, want))))
+            print(f"pearson {name}: largest relative difference {err / eps:.2f} eps")
+            np.testing.assert_allclose(got, want, rtol=4.5e-16, atol=0.0)
+    n_asked = len(asked)
+    for sparse_rows, mode in ((False, _lib.PRE_LOG_CPM), (True, _lib.PRE_LOG_CPM_SPARSE)):
+        wy, wx, my, mx = tables("log_cpm", y_sparse=sparse_rows, y_colsum=colsum, n_spots=n)
+        assert (my, mx) == (mode, _lib.PRE_LOG_CPM) and wy is weight and wx is weight
+    assert tables("log_cpm", f64_math=True)[2:] == (_lib.PRE_LOG_CPM | _lib.PRE_F64_MATH, _lib.PRE_LOG_CPM)
+    for kw in ({}, {"f64_math": True}, {"y_sparse": True}):               # float64 math is a property of the log chain only
+        wy, wx, my, mx = tables("raw", y_colsum=colsum, **kw)
+        assert (my, mx) == (_lib.PRE_RAW, _lib.PRE_RAW) and wy is weight and wx is weight
+    assert tables("pearson", f64_math=True, y_colsum=colsum, n_spots=n)[2:] == (_lib.PRE_RAW, _lib.PRE_RAW)
+    assert len(asked) == n_asked + 1                                       # nobody computes column sums for log_cpm or raw
+    with pytest.raises(ValueError) as e:
+        sketch_tables(G, 64, lev, 7, "zscore", X)
+    with pytest.raises(ValueError) as want:
+        fdx_oracle.preprocess(Y, X, "zscore")
+    assert str(e.value) == str(want.value)
+
+
+def test_select_gene_idx_equals_the_oracle_on_host_moments():
+    """utils/genes.py: select_gene_idx (HVG ranking + marker table on a helper thread + union) against the oracle's
+    select_informative_genes, the moments computed on the host as the reference computes them (utils/genes.py:85-102)."""
+    import datagen
+    import fdx_oracle
+    from flashdeconv_amd.utils import genes
+    Y, X, _, _ = datagen.count_like(300, 900, 6, 0.1, 3)
+    Yd = Y.astype(np.float64)
+    Z = np.log1p(Yd / np.maximum(Yd.sum(axis=1, keepdims=True), 1) * 10000)
+    calls = []
+
+    def moments():
+        calls.append(1)
+        return Z.mean(axis=0), Z.var(axis=0, ddof=1)
+    got = genes.select_gene_idx(X, 250, 50, moments)
+    want, _ = fdx_oracle.select_informative_genes(Y, X, n_hvg=250, n_markers_per_type=50)
+    assert len(calls) == 1 and got.dtype == np.intp
+    assert np.array_equal(got, want)
+    assert 250 < len(got) < 900                                            # both parts contribute
+    with pytest.raises(ValueError, match="No genes selected"):
+        genes.select_gene_idx(X, 0, 0, moments)
