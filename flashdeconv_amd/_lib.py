@@ -187,6 +187,7 @@ SIGNATURES = {
                                              c_i32, c_void_p, c_void_p, c_i64, ctypes.POINTER(SolveInfo), p_double, p_i32, c_void_p]),
     "fdx_tile_schedule": (c_int, [p_i32, p_double, c_i32, c_i32, c_i32, c_i32, c_i32, p_i32, p_i32, c_void_p, p_i32, p_double,
                                   c_void_p, c_i64]),
+    "fdx_sketch_path": (c_int, [c_i32, c_void_p, c_i64, c_i32, c_i32, c_i32, c_i32, p_i32, p_double, p_i32, p_i32]),
     "fdx_column_sums": (c_int, [c_void_p, c_i32, c_i64, c_i32, p_double]),
     "fdx_log1p_f32": (c_int, [c_void_p, ctypes.c_float, c_i64, c_void_p]),
     "fdx_graph_build_knn": (c_int, [p_double, c_i64, c_i32, c_i32, ctypes.POINTER(c_void_p)]),

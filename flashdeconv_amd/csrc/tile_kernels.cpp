@@ -711,7 +711,12 @@ static const TilePlanDevice* tile_plan_for(const SketchPlan& sp, int dtype, int 
     // whether 5000 genes take 7 blocks or 10 (21 % more lockstep padding)
     const int unit = (cfg.wide || NST == 3 ? 128 : 1024) / sz;
     std::unique_ptr<TilePlanDevice> best;
-    for (int GB = (int)round_up(sp.G, unit); GB >= unit; GB -= unit) {
+    // The reduction area overlays a stage buffer.  Rows shorter than it (up to 256 float32 genes in the log modes, 512 with two
+    // type tiles; 128 float64 genes in the wide raw form) used to find no block size at all and went to the two-kernel path
+    // unseen: they take one column block long enough to hold the area - only the row's own bytes are staged into it.
+    int GB0 = (int)round_up(sp.G, unit);
+    while ((size_t)(wg ? round_up((GB0 + 1) * 8, 16) : 0) + (size_t)TILE_ROWS * (GB0 * sz + TILE_ROW_PAD) < red_bytes) GB0 += unit;
+    for (int GB = GB0; GB >= unit; GB -= unit) {
         const int RS = GB * sz + TILE_ROW_PAD;
         const int WB = wg ? (int)round_up((GB + 1) * 8, 16) : 0;
         if ((size_t)WB + (size_t)TILE_ROWS * RS < red_bytes) break;
@@ -1027,6 +1032,32 @@ extern "C" int fdx_tile_schedule(const int32_t* gene_bucket, const double* gene_
     std::copy(h.ent_base.begin(), h.ent_base.end(), ent_base_out);
     std::copy(h.w.begin(), h.w.end(), w_out);
     std::copy(h.off.begin(), h.off.end(), off_out);
+    return 0;
+}
+
+// include/fdx.h: what queue_rows_to_h (prepare.cpp) chooses for a dense matrix, through the functions it calls itself - the
+// cached plan of (bucket, weight_y), then fused_sketch_contract_ok, then the schedule launch_tile_sketch would fetch.
+extern "C" int fdx_sketch_path(int32_t y_dtype, const void* Y_dev, int64_t ldy, int32_t G, int32_t d, int32_t K, int32_t mode_y_in,
+                               const int32_t* bucket, const double* weight_y, int32_t* path_out,
+                               int32_t* dims_out /* NWC, NWL, JW, TT, GB, NBLK */) {
+    using namespace fdx;
+    FDX_REQUIRE(bucket && weight_y && path_out, "fdx_sketch_path: null argument");
+    FDX_REQUIRE(G > 0 && K > 0 && d > 0 && ldy >= G, "fdx_sketch_path: bad shape");
+    const int32_t mode_y = mode_y_in & 0xff;
+    if (dims_out) std::fill(dims_out, dims_out + 6, 0);
+    hipStream_t st = nullptr;
+    PoolStream pool_stream(st);
+    std::shared_ptr<SketchPlan> plan;
+    FDX_TRY(sketch_plan_cached(bucket, weight_y, G, d, st, &plan));
+    *path_out = 0;
+    if (!fused_sketch_contract_ok(y_dtype, ldy, Y_dev, G, d, K, mode_y, plan->dev(), st)) return 0;
+    const TilePlanDevice* t = tile_plan_for(*plan, y_dtype, mode_y, K, st);
+    FDX_REQUIRE(t != nullptr, "fdx_sketch_path: the one-kernel form was accepted without a schedule");
+    *path_out = t->wide ? 2 : 1;
+    if (dims_out) {
+        dims_out[0] = t->NWC; dims_out[1] = t->NWL; dims_out[2] = t->JW; dims_out[3] = t->TT;
+        dims_out[4] = t->h.GB; dims_out[5] = t->h.NBLK;
+    }
     return 0;
 }
 #endif  // !FDX_TILE_PART

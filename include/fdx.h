@@ -108,6 +108,14 @@ int fdx_sketch(const void* Y, int32_t dtype, int64_t n, int32_t G, const int64_t
 int fdx_tile_schedule(const int32_t* gene_bucket, const double* gene_w, int32_t G, int32_t d, int32_t NW, int32_t JW,
                       int32_t GB, int32_t* dims_out, int32_t* slot_bucket_out, uint8_t* len_out, int32_t* ent_base_out,
                       double* w_out, uint16_t* off_out, int64_t cap_entries);
+/* Which kernels fdx_prepare_dev / fdx_fit_dev run for the sketch -> H stage of a DENSE matrix with these arguments (Y_dev
+ * may be NULL: only its 16-byte alignment matters; mode_y as for fdx_prepare_dev): *path_out = 0 the two-kernel path
+ * (sketch_rows_* + contraction), 1 the narrow and 2 the wide form of the tile kernel.  For the tile forms dims_out[6]
+ * (may be NULL) = {consumer waves, loader waves, groups per wave, type tiles, genes per column block, column blocks}.
+ * The answer comes from the functions the launch itself calls (the cached plan of the Omega, the runtime switches), so
+ * it builds and caches that plan; no kernel is launched.  Tests state the path they mean to cover with it. */
+int fdx_sketch_path(int32_t y_dtype, const void* Y_dev, int64_t ldy, int32_t G, int32_t d, int32_t K, int32_t mode_y,
+                    const int32_t* bucket, const double* weight_y, int32_t* path_out, int32_t* dims_out);
 /* out[i] = log1p(y[i] * scale) exactly as the fused sketch kernel evaluates the log-CPM transform (core/deconv.py:190-191)
  * for FLOAT32 rows with every argument in [0, 32000): float32-class (the reference computes this step in float32 for
  * float32 input, numpy dtype rules), v_log_f32 plus a first-order correction of the rounding of 1 + x.  Host arrays;

@@ -202,7 +202,10 @@ def test_public_header_is_plain_c99(tmp_path):
 
 @pytest.mark.parametrize("G,d,NW,JW,GB", [(2000, 512, 16, 8, 1024), (2000, 512, 8, 16, 768), (2000, 512, 16, 8, 2048),
                                           (3300, 512, 16, 8, 768), (1001, 500, 16, 8, 256), (300, 64, 16, 8, 512),
-                                          (5000, 512, 8, 16, 512), (40, 7, 16, 8, 256)])
+                                          (5000, 512, 8, 16, 512), (40, 7, 16, 8, 256),
+                                          # the splits the library launches: raw narrow 12 x 11, raw wide 12 x 22, log wide 8 x 32
+                                          (2000, 512, 12, 11, 1024), (2000, 528, 12, 11, 2048), (5000, 1024, 12, 22, 1024),
+                                          (1200, 1024, 12, 22, 1280), (3000, 700, 8, 32, 768), (1500, 1024, 8, 32, 512)])
 def test_tile_schedule_replays_to_the_countsketch(G, d, NW, JW, GB):
     """The tile kernel's static schedule (csrc/tile_plan.cpp), replayed on the host exactly as the kernel walks it,
     must reproduce f(Y) @ Omega: every gene visited once, in its bucket, with its weight, inside its column block."""
@@ -261,6 +264,24 @@ def test_tile_schedule_replays_to_the_countsketch(G, d, NW, JW, GB):
     if G >= 1000 and nblk <= 5:
         assert steps * 4 <= 1.35 * inside.sum(), (steps * 4, inside.sum())
         assert wave_max * NW <= 1.15 * steps
+
+
+def test_tile_schedule_refuses_a_bucket_with_more_than_255_genes_in_a_column_block():
+    """A group's length in a column block is one byte of the schedule: an Omega that puts 256 genes of one bucket into one block
+    cannot be scheduled (the dispatch then takes the two-kernel path), 255 can."""
+    from flashdeconv_amd import _lib
+    lib = _lib.load()
+    G, d = 2040, 4
+    bucket = (np.arange(G) % d).astype(np.int32)
+    weight = np.where(np.arange(G) % 3 == 0, -1.0, 1.0)
+    dims = np.zeros(4, dtype=np.int32)
+    for NW, JW in ((16, 8), (12, 11), (12, 22), (8, 32)):
+        with pytest.raises(_lib.FdxError, match="cannot be scheduled"):
+            _lib.check(lib.fdx_tile_schedule(_lib.ptr_i32(bucket), _lib.ptr_f64(weight), G, d, NW, JW, 1024, _lib.ptr_i32(dims),
+                                             None, None, None, None, None, 0))                      # 256 genes of every bucket in block 0
+        _lib.check(lib.fdx_tile_schedule(_lib.ptr_i32(bucket), _lib.ptr_f64(weight), G, d, NW, JW, 1020, _lib.ptr_i32(dims),
+                                         None, None, None, None, None, 0))                          # 255 in each of the two blocks
+        assert dims[0] == 2
 
 
 def test_bench_spawns_its_own_ranks():
