@@ -476,15 +476,10 @@ int fdx_shard_fit_dev(fdx_comm* c, const fdx_graph* g, const void* Y_dev, int32_
     FDX_REQUIRE(Gh != nullptr, "fdx_shard_fit_dev: pinned host buffer");
     // A shard build may still be on its way (graph_shard_knn: second phase queued by the helper thread on the plan stream): the
     // sketch of the own rows does not need the graph and runs beside it.
-    // (FDX_SKETCH_RESERVE: compute units the sketch's persistent workgroups leave to that build; measured at 16 / 32 / 64 on a
-    // 125k-spot shard it only slowed both down - the build is a chain of dependent launches, not a matter of free units.)
-    int reserve = 0;
-    if (g->shard_pending) if (const char* e = fdx::exp_env("FDX_SKETCH_RESERVE")) reserve = atoi(e);
-    const int reserve_prev = tile_sketch_reserve_cus(reserve);
-    const int prc = prepare_queue(&job, Y_dev, y_dtype, n_own, G, ldy, nullptr, X, K, bucket, weight_y, weight_x, prm->sketch_dim,
-                                  prm->mode_y, prm->mode_x, dH.as<double>(), ldh, Gh, st, prm->X_dev);
-    tile_sketch_reserve_cus(reserve_prev);
-    FDX_TRY(prc);
+    // (Leaving 16 / 32 / 64 compute units of the sketch's persistent workgroups to that build only slowed both down on a 125k-spot
+    // shard - the build is a chain of dependent launches, not a matter of free units.)
+    FDX_TRY(prepare_queue(&job, Y_dev, y_dtype, n_own, G, ldy, nullptr, X, K, bucket, weight_y, weight_x, prm->sketch_dim,
+                          prm->mode_y, prm->mode_x, dH.as<double>(), ldh, Gh, st, prm->X_dev));
     shard_trace("X side + sketch queued");
     FDX_TRY(graph_shard_join(g));
     shard_trace("rest of the plan queued");
@@ -651,7 +646,7 @@ static int sharded_solve_impl(fdx_comm* c, const fdx_graph* g, const double* H_d
     // every rank must take the same route for the convergence slots: they ride with the halo only when NO rank of the job can
     // split (shards are equal to within one tile: the largest has at most ceil(tiles / W) + 1 of them)
     const long long tiles_max = g->world_n > 0 ? ((g->world_n + 255) / 256 + W - 1) / W + 1 : (1LL << 40);
-    const bool piggy_ok = W > 1 && !c->loopback && (c->nccl || c->local) && !fdx::exp_env("FDX_STATS_ALLREDUCE") &&
+    const bool piggy_ok = W > 1 && !c->loopback && (c->nccl || c->local) &&
                           (tiles_max < split_min_tiles || fdx::env("FDX_NO_OVERLAP") != nullptr);
     // (piggy_ok is the JOB's decision - world size and spot count only.  A rank whose own shard is larger than the balanced bound, from
     // bounds that fdx_graph_localize accepted but shard_bounds() would not have made, must not split on its own: it would all-reduce
@@ -742,7 +737,7 @@ static int sharded_solve_impl(fdx_comm* c, const fdx_graph* g, const double* H_d
         return 0;
     };
     // the in-process transport meets at host barriers: nothing is gained by queueing ahead there
-    const int n_ahead = (c->local || fdx::exp_env("FDX_NO_SWEEP_AHEAD")) ? 0 : 2;
+    const int n_ahead = c->local ? 0 : 2;
     LoopResult loop;
     const int rc = solver_loop(stats, max_iter, tol, 4, n_ahead, iterate, &loop, st);
     if (rc && c->local) c->local->abort();     // the other thread ranks leave their barriers with an error instead of hanging

@@ -510,7 +510,6 @@ static size_t csr_contract_lds(int d, int TT, int sel_words) {
 // shapes the fused kernel takes: the A operands of a wave (NB x TT x 4 doubles) must fit beside the row's registers, and the keep
 // buffers need room for a wave's worth of entries at least
 bool csr_contract_ok(int d, int K, int sel_words) {
-    if (fdx::exp_env("FDX_CSR_NO_FUSED")) return false;
     if (d <= 0 || K <= 0 || K > 64 || d % 4 != 0) return false;
     const int NB = (d + 255) / 256, TT = (K + 15) / 16;
     if (NB * TT > 4) return false;
@@ -839,29 +838,23 @@ static int launch_csr_moments_t(const long long* indptr, const int* indices, con
                                 double* scale, double* part, double* mean, double* var, double* colsum, bool sorted_rows,
                                 hipStream_t st) {
     // sorted rows: ONE 16-wave workgroup per CU at 128 registers with as much of the gene axis as 152 KB of LDS hold (fewer
-    // visits per row, fewer windows that end beside a tile edge); FDX_CSR_MOM_CFG=2: two workgroups per CU, 64 KB tiles
-    const bool cursor_path = sorted_rows && nnz > 0 && !fdx::exp_env("FDX_CSR_NO_CURSOR");
-    const bool one_wg = cursor_path && !(fdx::exp_env("FDX_CSR_MOM_CFG") && atoi(fdx::exp_env("FDX_CSR_MOM_CFG")) == 2);
+    // visits per row, fewer windows that end beside a tile edge); unsorted rows: 64 KB tiles
+    const bool cursor_path = sorted_rows && nnz > 0;
     // (+ 16 waves x 512 B of log1p tables, + 16 KB of row cursors on the sorted path)
-    const int tile_max = (int)((one_wg ? 136 : (cursor_path ? 56 : 64)) * 1024 / (NS * sizeof(double)));
+    const int tile_max = (int)((cursor_path ? 136 : 64) * 1024 / (NS * sizeof(double)));
     const int tiles = ceil_div(G, tile_max);
-    const int tile = one_wg ? std::min(G, (ceil_div(G, tiles) + 63) & ~63) : std::min(G, tile_max);
-    const int stripes = one_wg ? (int)std::min<long long>(csr_moment_stripes(n), 256) : csr_moment_stripes(n);
+    const int tile = cursor_path ? std::min(G, (ceil_div(G, tiles) + 63) & ~63) : std::min(G, tile_max);
+    const int stripes = cursor_path ? (int)std::min<long long>(csr_moment_stripes(n), 256) : csr_moment_stripes(n);
     const int rows_per_stripe = (int)((n + stripes - 1) / stripes);
     const int no_table = fdx::env("FDX_NO_LOG_TABLE") ? 1 : 0;
     hipLaunchKernelGGL(csr_row_scale_kernel<T>, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, st, indptr, data, n, scale, no_table);
     FDX_CHECK_LAUNCH();
     const size_t lds_m = (size_t)NS * tile * sizeof(double) + 16 * 64 * sizeof(double);
     if (cursor_path) {     // rows sorted by column: one pass over the indices
-        auto launch = [&](auto kern) -> int {
-            const size_t lds_c = lds_m + (size_t)CSR_MOM_SUB * sizeof(int);
-            FDX_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
-            hipLaunchKernelGGL(kern, dim3(stripes), dim3(1024), lds_c, st, indptr, indices, data, scale, n, nnz, G, tile,
-                               rows_per_stripe, part);
-            return 0;
-        };
-        if (one_wg) FDX_TRY(launch(csr_moments_cursor_kernel<T, NS, 8, 4>));
-        else FDX_TRY(launch(csr_moments_cursor_kernel<T, NS, 6, 8>));
+        const size_t lds_c = lds_m + (size_t)CSR_MOM_SUB * sizeof(int);
+        FDX_HIP(hipFuncSetAttribute((const void*)csr_moments_cursor_kernel<T, NS, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
+        hipLaunchKernelGGL((csr_moments_cursor_kernel<T, NS, 8, 4>), dim3(stripes), dim3(1024), lds_c, st, indptr, indices, data, scale, n, nnz,
+                           G, tile, rows_per_stripe, part);
     } else {
         FDX_HIP(hipFuncSetAttribute((const void*)csr_moments_tiled_kernel<T, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
         hipLaunchKernelGGL((csr_moments_tiled_kernel<T, NS>), dim3(stripes, tiles), dim3(1024), lds_m, st,

@@ -5,7 +5,9 @@
 #include <atomic>
 #include <chrono>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <mutex>
 #include <string>
 
@@ -14,56 +16,66 @@
 namespace fdx {
 namespace {
 
+// value: what env() returns - NULL (unset) or a string that lives as long as the process.  Readers load the pointer and never
+// touch a string that is being written; a reload publishes a NEW string for a value that changed and keeps the old one.
 struct Switch {
     const char* name;
     const char* what;
-    bool set;
-    std::string value;
+    std::atomic<const char*> value{nullptr};
 };
 
 Switch g_switches[] = {
-    {"FDX_TRACE_HOST", "host time between the marked points of a fit / a graph build (stderr)", false, {}},
-    {"FDX_DEBUG", "one-line reports of the routes taken (leverage route, ELL rebuilds)", false, {}},
-    {"FDX_NO_LOG_TABLE", "log1p without the per-row table of the 64 small counts (bit-identical: tests)", false, {}},
-    {"FDX_GRAPH_WCAP", "ELL width bound of a graph build: forces the 'bound too small' rebuild / remedy (tests)", false, {}},
-    {"FDX_GRAPH_WCAP_RANK", "... on this rank of a shard plan only", false, {}},
-    {"FDX_NO_TILED", "global-gather sweep instead of the LDS-tiled one", false, {}},
-    {"FDX_NO_INIT_SWEEP", "first sweep reads a written start vector instead of the constant 1/K", false, {}},
-    {"FDX_SPLIT_MIN_TILES", "tiles from which a shard sweeps boundary and interior separately", false, {}},
-    {"FDX_NO_OVERLAP", "sharded loop: one sweep launch per iteration, halo on the compute stream", false, {}},
-    {"FDX_NO_FUSED", "two-kernel sketch -> H (scatter + contraction) instead of the tile kernel", false, {}},
-    {"FDX_NO_TILE_WIDE", "no wide tile kernel (K > 32 / d > 704): the two-kernel path takes those shapes", false, {}},
-    {"FDX_TILE_LOGV", "0: float64 log1p chain for float32 rows in the tile kernel", false, {}},
-    {"FDX_TILE_CFG", "wave split of the tile kernel: 12 (12 + 4), 16 (16 + 0), 8 (8 + 2)", false, {}},
-    {"FDX_SKETCH_GATHER", "gather form of the row sketch kernel", false, {}},
-    {"FDX_GRAPH_SORT", "Morton order by a radix sort instead of by counting", false, {}},
-    {"FDX_GRAPH_SYNC", "graph build completed inside the call (no deferred counts)", false, {}},
-    {"FDX_GRAPH_TWO_ELL_KERNELS", "fill_ell + tile_halo as two kernels", false, {}},
-    {"FDX_NO_FUSED_PACK", "sharded loop: halo_pack_kernel instead of the sweep writing the send staging", false, {}},
-    {"FDX_LEV_ONE_WG", "leverage scores by the single-workgroup route", false, {}},
-    {"FDX_KDTREE_HOST_QUERIES", "tie remedy: cKDTree queries on host threads instead of kd_query_kernel", false, {}},
-    {"FDX_KDTREE_THREADS", "host threads of the restated cKDTree (build forks, host queries)", false, {}},
-    {"FDX_KDTREE_PAR_DEPTH", "fork depth of the restated cKDTree build", false, {}},
-    {"FDX_NO_PLAN_CACHE", "sketch plans / tile schedules rebuilt every fit (bench.py: cold_ms)", false, {}},
-    {"FDX_NO_SIDE_STREAM", "everything on the caller's stream", false, {}},
-    {"FDX_CSR_KEEP_CAP", "entries per wave of the fused CSR sketch's keep buffer (tests: rows that overflow it)", false, {}},
+    {"FDX_TRACE_HOST", "host time between the marked points of a fit / a graph build (stderr)"},
+    {"FDX_DEBUG", "one-line reports of the routes taken (leverage route, ELL rebuilds)"},
+    {"FDX_NO_LOG_TABLE", "log1p without the per-row table of the 64 small counts (bit-identical: tests)"},
+    {"FDX_GRAPH_WCAP", "ELL width bound of a graph build: forces the 'bound too small' rebuild / remedy (tests)"},
+    {"FDX_GRAPH_WCAP_RANK", "... on this rank of a shard plan only"},
+    {"FDX_NO_TILED", "global-gather sweep instead of the LDS-tiled one"},
+    {"FDX_NO_INIT_SWEEP", "first sweep reads a written start vector instead of the constant 1/K"},
+    {"FDX_SPLIT_MIN_TILES", "tiles from which a shard sweeps boundary and interior separately"},
+    {"FDX_NO_OVERLAP", "sharded loop: one sweep launch per iteration, halo on the compute stream"},
+    {"FDX_NO_FUSED", "two-kernel sketch -> H (scatter + contraction) instead of the tile kernel"},
+    {"FDX_NO_TILE_WIDE", "no wide tile kernel (K > 32 / d > 704): the two-kernel path takes those shapes"},
+    {"FDX_TILE_LOGV", "0: float64 log1p chain for float32 rows in the tile kernel"},
+    {"FDX_TILE_CFG", "wave split of the tile kernel: 12 (12 + 4), 16 (16 + 0), 8 (8 + 2)"},
+    {"FDX_SKETCH_GATHER", "gather form of the row sketch kernel"},
+    {"FDX_GRAPH_SORT", "Morton order by a radix sort instead of by counting"},
+    {"FDX_GRAPH_SYNC", "graph build completed inside the call (no deferred counts)"},
+    {"FDX_GRAPH_TWO_ELL_KERNELS", "fill_ell + tile_halo as two kernels"},
+    {"FDX_NO_FUSED_PACK", "sharded loop: halo_pack_kernel instead of the sweep writing the send staging"},
+    {"FDX_LEV_ONE_WG", "leverage scores by the single-workgroup route"},
+    {"FDX_KDTREE_HOST_QUERIES", "tie remedy: cKDTree queries on host threads instead of kd_query_kernel"},
+    {"FDX_KDTREE_THREADS", "host threads of the restated cKDTree (build forks, host queries)"},
+    {"FDX_KDTREE_PAR_DEPTH", "fork depth of the restated cKDTree build"},
+    {"FDX_NO_PLAN_CACHE", "sketch plans / tile schedules rebuilt every fit (bench.py: cold_ms)"},
+    {"FDX_NO_SIDE_STREAM", "everything on the caller's stream"},
+    {"FDX_CSR_KEEP_CAP", "entries per wave of the fused CSR sketch's keep buffer (tests: rows that overflow it)"},
 };
 constexpr int kSwitches = sizeof(g_switches) / sizeof(g_switches[0]);
 std::once_flag g_once;
-std::mutex g_mu;
+std::mutex g_mu;                          // serialises load_all()
 std::atomic<bool> g_trace_host{false};   // FDX_TRACE_HOST as load_all() last saw it: a trace point that is off costs this load, not a walk of the registry
 
 const char* lookup(const char* name) {
     for (const Switch& s : g_switches)
-        if (std::strcmp(s.name, name) == 0) return s.set ? s.value.c_str() : nullptr;
+        if (std::strcmp(s.name, name) == 0) return s.value.load(std::memory_order_acquire);
     return nullptr;          // not a runtime switch (tests/test_host.py checks the sources against the registry)
 }
 
 void load_all() {
+    // every value ever published, never destroyed (a library thread may hold a pointer past exit()); it grows only when a value
+    // changes between reloads - the tests, and bench.py around its cold fit
+    static std::deque<std::string>* const kept = new std::deque<std::string>();
+    std::lock_guard<std::mutex> lk(g_mu);
     for (Switch& s : g_switches) {
         const char* v = getenv(s.name);
-        s.set = v != nullptr;
-        s.value = v ? v : "";
+        const char* cur = s.value.load(std::memory_order_relaxed);
+        if (v && cur && std::strcmp(v, cur) == 0) continue;
+        if (v) {
+            kept->emplace_back(v);
+            v = kept->back().c_str();
+        }
+        s.value.store(v, std::memory_order_release);
     }
     g_trace_host.store(lookup("FDX_TRACE_HOST") != nullptr, std::memory_order_relaxed);
 }
@@ -87,7 +99,6 @@ void trace_host(const char* scope, const char* what) {
 
 void env_reload() {
     std::call_once(g_once, load_all);
-    std::lock_guard<std::mutex> lk(g_mu);
     load_all();
 }
 

@@ -1,6 +1,5 @@
 // Internal launch interfaces between the kernel translation units and the C-ABI layer.
 #pragma once
-#include "fdx_env.h"
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 
@@ -20,7 +19,7 @@ constexpr int FDX_MAX_K_FAST = 64;  // register-resident sweep kernels are insta
 // at one wave per SIMD: 3.9; generic ~10), 120: 4.0, 200: 16.
 constexpr int FDX_MAX_K_PAD = 96;
 inline int solver_padded_K(int K) {
-    if (K <= FDX_MAX_K_FAST || K > FDX_MAX_K_PAD || fdx::exp_env("FDX_NO_K_PAD")) return K;
+    if (K <= FDX_MAX_K_FAST || K > FDX_MAX_K_PAD) return K;
     for (int kp : {72, 80, 88, 96})
         if (K <= kp) return kp;
     return K;
@@ -107,8 +106,6 @@ int launch_tile_sketch(const void* Y, int dtype, long long ldy, const int* row_m
 int launch_sketch_contract(const void* Y, int dtype, long long ldy, const int* row_map, long long n, int G, int d, int mode,
                            const SketchPlanDev& plan, const double* Xs, int K, double* H, long long ldh, double* row_sumsq,
                            hipStream_t st);
-// units the next tile-kernel launches of this thread leave to other streams (0 = none); returns the previous setting
-int tile_sketch_reserve_cus(int cus);
 int column_sums_parts(long long n);
 int launch_column_sums(const void* Y, int dtype, long long ldy, long long n, int G, double* partials, double* out,
                        hipStream_t st);

@@ -105,7 +105,7 @@ extern "C" int fdx_leverage_begin_opt(const double* X, int32_t K, int32_t G, dou
     std::memcpy(job->hX, X, (size_t)K * G * sizeof(double));
     // the upload (a pageable copy: the host waits for it) and the launches cost ~75 us of host time that the caller - on its way to
     // a graph build, with the scores not needed before the sketch tables - has better uses for: the helper thread queues them
-    const bool async = queue_async != 0 && !fdx::exp_env("FDX_NO_HELPER_THREAD");
+    const bool async = queue_async != 0;
     auto run = [job, K, G, regularization]() -> int {
         PoolStream pool_stream(job->st);
         FDX_TRY(job->dX.alloc((size_t)K * G * sizeof(double)));
@@ -431,7 +431,7 @@ int fit_impl(const YSource& ysrc, int64_t n, int32_t G, const double* X, int32_t
     // (0.2 ms) both only read the final abundances: the export goes to the library's side stream (idle here - the leverage
     // job was collected before this call) and runs beside the objective pass instead of after it.
     Event evSolved, evExported;
-    if ((beta_out_dev || prop_out_dev) && !prm->verbose && !fdx::exp_env("FDX_NO_EXPORT_OVERLAP") && side) {
+    if ((beta_out_dev || prop_out_dev) && !prm->verbose && side) {
         FDX_TRY(evSolved.record(st));
         FDX_TRY(evSolved.wait_on(side));
         FDX_TRY(launch_normalize_export(p.beta[r.result_buffer], ld, row_map, (int)n, g->n_slices, K, beta_out_dev,

@@ -350,13 +350,12 @@ __global__ __launch_bounds__(128) void knn_kernel(const double* __restrict__ sc,
                                                   long long n, GridParams gp, int kk, int* __restrict__ nbr_out,
                                                   int* __restrict__ nbr_cnt, double* __restrict__ nn_dist,
                                                   long long lo, long long hi, int* __restrict__ indeg,
-                                                  int* __restrict__ arrival, int* __restrict__ tie_count, int gp_no_batch,
+                                                  int* __restrict__ arrival, int* __restrict__ tie_count,
                                                   const int* __restrict__ row_list, const int* __restrict__ row_count,
                                                   int* __restrict__ far_flag, int far_R, int far_drop, int n_direct, int list_cap) {
-    // rows [lo, hi) of the sorted order, or (row_list != NULL: the band of a spot shard) the first min(*row_count, hi) listed rows,
-    // or (n_direct >= 0: a spot shard's own rows AND its band in one launch - each of the two launches lasted one walk's latency,
-    // ~50 us, whatever its size) rows lo .. lo + n_direct - 1 followed by the first min(*row_count, list_cap) listed rows; ties and
-    // far walks are counted for the own rows only
+    // rows [lo, hi) of the sorted order, or (n_direct >= 0: a spot shard's own rows AND its band in one launch - each of the two
+    // launches lasted one walk's latency, ~50 us, whatever its size) rows lo .. lo + n_direct - 1 followed by the first
+    // min(*row_count, list_cap) rows of row_list; ties and far walks are counted for the own rows only
     long long p = lo + blockIdx.x * (long long)blockDim.x + threadIdx.x;
     bool listed = false, ghost = false;
     if (n_direct >= 0) {
@@ -367,9 +366,6 @@ __global__ __launch_bounds__(128) void knn_kernel(const double* __restrict__ sc,
             p = row_list[j];
             listed = true;
         }
-    } else if (row_list) {
-        if (p >= hi || p >= (long long)*row_count) return;
-        p = row_list[p];
     } else if (p >= hi) {
         if (!indeg) return;
         ghost = true;                                     // whole-graph build: the block's in-degree counters meet at barriers below -
@@ -413,7 +409,7 @@ __global__ __launch_bounds__(128) void knn_kernel(const double* __restrict__ sc,
     // The nine cells' (first position, count) sit in LDS, one column per lane: the walk steps through them with a running
     // cell number, and a register array indexed by it is nine selects per candidate.  A lane only ever reads its own column -
     // no barrier anywhere.
-    const bool use_block = KMAX <= 16 && gp.dim <= 2 && sc2 != nullptr && !gp_no_batch;
+    const bool use_block = KMAX <= 16 && gp.dim <= 2 && sc2 != nullptr;
     __shared__ int s_cs[9][128], s_cn[9][128];
     const int tid = threadIdx.x;
     int total = 0;
@@ -1245,7 +1241,7 @@ static int bbox_begin(const double* d_coords, long long n, int dim, hipStream_t 
     FDX_HIP(hipGetDevice(&job->dev));
     // (256 to 16384 blocks, one to sixteen points per thread, four loads in flight or one: 33-60 us for the 16 MB of a million 2-D
     // points whatever the shape - the kernel's time is not its loop; 512 blocks measured best)
-    const int nblk = (int)std::min<long long>(fdx::exp_env("FDX_BBOX_BLOCKS") ? atoi(fdx::exp_env("FDX_BBOX_BLOCKS")) : 512, (n + 255) / 256);
+    const int nblk = (int)std::min<long long>(512, (n + 255) / 256);
     FDX_TRY(job->part.alloc((size_t)nblk * 6 * sizeof(double)));
     job->host = (double*)pinned_block_get();
     FDX_REQUIRE(job->host != nullptr, "graph: pinned host block");
@@ -1354,7 +1350,7 @@ static int bin_points(const double* d_coords, long long n, int dim, double targe
     while ((1LL << axis_bits) < (long long)max_axis) ++axis_bits;
     const int bits = std::min(64, axis_bits * dim);      // significant bits of the Morton key
     const bool counting = bits <= 22 && (1LL << bits) <= 8 * n + 1024 && !fdx::env("FDX_GRAPH_SORT");
-    const bool shard_need = counting && shard_hi > shard_lo && (shard_lo > 0 || shard_hi < n) && shard_R > 0 && !fdx::exp_env("FDX_BAND_FULL_BINNING");
+    const bool shard_need = counting && shard_hi > shard_lo && (shard_lo > 0 || shard_hi < n) && shard_R > 0;
     {
         // the cell table, the key counters and (spot shards) the need flags start as zero: one block, one fill
         auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
@@ -1569,22 +1565,17 @@ static void launch_knn_range(const BinnedPoints& b, const int* perm, int kk, int
     const long long n_threads = n_direct >= 0 ? (long long)n_direct + list_cap : hi - lo;
     // candidates per round trip: 4 leaves the kernel 77 registers (6 waves per SIMD), 6: 87 (5 waves), 8: 97 (4 waves);
     // 1M spots, wall per fit: 4.69 / 4.84 / 4.88 ms
-    const int batch_env = fdx::exp_env("FDX_KNN_BATCH") ? atoi(fdx::exp_env("FDX_KNN_BATCH")) : 0;
     // a launch of a few hundred thousand rows does not fill the chip anyway (a spot shard's own rows + band): what it takes is one
     // walk's chain of round trips, and 8 candidates per round trip halve that chain (97 registers, 4 waves per SIMD - no loss here)
-    const int batch_auto = (KMAX <= 16 && n_threads <= 300000) ? 8 : 4;
-    const int batch = (KMAX <= 16 && (batch_env == 4 || batch_env == 6 || batch_env == 8)) ? batch_env : (KMAX <= 16 ? batch_auto : 8);
+    const int batch = (KMAX <= 16 && n_threads > 300000) ? 4 : 8;
     auto go = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(ceil_div(n_threads, 128)), dim3(128), 0, st, b.sc.as<double>(), b.sc2.as<double2>(), perm,
                            b.rank.as<int>(), b.cstart.as<int>(), b.cend_p, b.n, b.gp, kk, nbr, cnt, nn_dist, lo, hi, indeg, arrival,
-                           KMAX > kk ? ties : nullptr, fdx::exp_env("FDX_KNN_NO_BATCH") ? 1 : 0, row_list, row_count, far_flag, far_R, far_drop,
+                           KMAX > kk ? ties : nullptr, row_list, row_count, far_flag, far_R, far_drop,
                            n_direct, list_cap);
     };
     if constexpr (KMAX <= 16) {
         if (batch == 4) go(knn_kernel<KMAX, 4>);
-#ifdef FDX_EXPERIMENT
-        else if (batch == 6) go(knn_kernel<KMAX, 6>);
-#endif
         else go(knn_kernel<KMAX, 8>);
     } else {
         go(knn_kernel<KMAX, 8>);
@@ -1662,8 +1653,8 @@ int graph_knn_lists(const double* d_coords, long long n, int dim, int k, long lo
     plan->st = st;
     // ~4 points per grid cell: the 3 x 3 block of cells then always holds the k <= 8 nearest (no second shell, no divergence),
     // and the 256-spot Morton tiles come out more compact (1M jittered-lattice spots: graph 1.11 -> 0.95 ms, sweep 0.192 -> 0.186 ms;
-    // uniform random spots: unchanged); FDX_GRAPH_TPC overrides (experiments)
-    const double tpc = fdx::exp_env("FDX_GRAPH_TPC") ? atof(fdx::exp_env("FDX_GRAPH_TPC")) : 4.0;
+    // uniform random spots: unchanged)
+    const double tpc = 4.0;
     int rc = 0;
     if (dim > 3) {
         // solver order from the first three coordinates, exhaustive search in all of them
@@ -1723,15 +1714,12 @@ int graph_knn_lists(const double* d_coords, long long n, int dim, int k, long lo
         if (hipMemsetAsync(cnt, 0, (size_t)n * 4, st) != hipSuccess) { delete plan; return fail(FDX_ERR_HIP, "graph: memset failed"); }
     }
     // one slot more than the list length, for the tie test (kk = 64 has none: no tie count there).
-    // One launch (FDX_KNN_PIECES splits it: while the leverage scores still came from the Jacobi SVD passes on the library's
-    // side stream, 2-4 pieces let their small workgroups in between; the Cholesky-QR route is over before this kernel starts).
     // Where the kernel's time goes at 1M spots (300 us): ~110 us are the 7M in-degree counters (returning atomics; measured
     // with the counters taken out), the rest the walk - waves parked on its gathers two thirds of their life.
     const long long rows = hi - lo;
-    const int pieces_env = fdx::exp_env("FDX_KNN_PIECES") ? atoi(fdx::exp_env("FDX_KNN_PIECES")) : 0;
-    const int pieces = pieces_env > 0 ? pieces_env : 1;
-    const long long step = ((rows + pieces - 1) / pieces + 127) / 128 * 128;
-    const bool merged = band && rows > 0 && pieces == 1 && rows < 0x3fffffffLL && !fdx::exp_env("FDX_KNN_TWO_LAUNCHES");
+    // a shard's own rows and its band share ONE launch; the kernel's int row counts hold both (n * kk < 2^31 and kk >= 2 above:
+    // rows <= n < 2^30)
+    const bool merged = band && rows > 0;
     if (band && rows > 0) {
         // the band: cells next to a cell with an own row -> their rows outside [lo, hi) -> the lists of those rows.  Room for as
         // many band rows as own rows (a band is a surface: thousands of rows beside a million); an overflow is reported and the
@@ -1745,7 +1733,7 @@ int graph_knn_lists(const double* d_coords, long long n, int dim, int k, long lo
         if (!rc) rc = plan->band_rows.alloc((size_t)std::max(plan->band_cap, 1) * 4);
         if (!rc) rc = plan->band_counters.alloc(16);
         if (rc) { delete plan; return rc; }
-        const bool from_need = b.need_p && b.bins > 0 && !fdx::exp_env("FDX_BAND_CELLS");
+        const bool from_need = b.need_p && b.bins > 0;
         if ((!from_need && hipMemsetAsync(cell_flag.p, 0, cell_flag.bytes, st) != hipSuccess) ||
             hipMemsetAsync(plan->band_counters.p, 0, 16, st) != hipSuccess) {
             delete plan;
@@ -1770,26 +1758,14 @@ int graph_knn_lists(const double* d_coords, long long n, int dim, int k, long lo
     const int* bl = plan->band_rows.as<int>();
     const int* bctr = plan->band_counters.p ? plan->band_counters.as<int>() + 1 : nullptr;
     const int nd = merged ? (int)rows : -1, lc = merged ? plan->band_cap : 0;
-    for (long long a = lo; a < hi; a += step) {
-        const long long e = std::min(hi, a + step);
-        const int fd = shard_band ? 1 : 0;
-        const int* rl = merged ? bl : nullptr;
-        const int* rcnt = merged ? bctr : nullptr;
-        if (kk < 8) launch_knn_range<8>(b, perm, kk, nbr, cnt, nullptr, a, e, st, indeg, arrival, ties, rl, rcnt, ties + 1, fd, nd, lc);
-        else if (kk < 16) launch_knn_range<16>(b, perm, kk, nbr, cnt, nullptr, a, e, st, indeg, arrival, ties, rl, rcnt, ties + 1, fd, nd, lc);
-        else if (kk < 32) launch_knn_range<32>(b, perm, kk, nbr, cnt, nullptr, a, e, st, indeg, arrival, ties, rl, rcnt, ties + 1, fd, nd, lc);
-        else launch_knn_range<64>(b, perm, kk, nbr, cnt, nullptr, a, e, st, indeg, arrival, ties, rl, rcnt, ties + 1, fd, nd, lc);
-    }
+    const int fd = shard_band ? 1 : 0;
+    const int* rl = merged ? bl : nullptr;
+    const int* rcnt = merged ? bctr : nullptr;
+    if (kk < 8) launch_knn_range<8>(b, perm, kk, nbr, cnt, nullptr, lo, hi, st, indeg, arrival, ties, rl, rcnt, ties + 1, fd, nd, lc);
+    else if (kk < 16) launch_knn_range<16>(b, perm, kk, nbr, cnt, nullptr, lo, hi, st, indeg, arrival, ties, rl, rcnt, ties + 1, fd, nd, lc);
+    else if (kk < 32) launch_knn_range<32>(b, perm, kk, nbr, cnt, nullptr, lo, hi, st, indeg, arrival, ties, rl, rcnt, ties + 1, fd, nd, lc);
+    else launch_knn_range<64>(b, perm, kk, nbr, cnt, nullptr, lo, hi, st, indeg, arrival, ties, rl, rcnt, ties + 1, fd, nd, lc);
     trace_host("knn: kernel launched");
-    if (band && rows > 0 && !merged) {
-        const long long cap = plan->band_cap;
-        if (cap > 0) {
-            if (kk < 8) launch_knn_range<8>(b, perm, kk, nbr, cnt, nullptr, 0, cap, st, nullptr, nullptr, nullptr, bl, bctr, nullptr, 1);
-            else if (kk < 16) launch_knn_range<16>(b, perm, kk, nbr, cnt, nullptr, 0, cap, st, nullptr, nullptr, nullptr, bl, bctr, nullptr, 1);
-            else if (kk < 32) launch_knn_range<32>(b, perm, kk, nbr, cnt, nullptr, 0, cap, st, nullptr, nullptr, nullptr, bl, bctr, nullptr, 1);
-            else launch_knn_range<64>(b, perm, kk, nbr, cnt, nullptr, 0, cap, st, nullptr, nullptr, nullptr, bl, bctr, nullptr, 1);
-        }
-    }
     if (hipGetLastError() != hipSuccess) { delete plan; return fail(FDX_ERR_HIP, "graph: k-NN kernel launch failed"); }
     *out = plan;
     return 0;
@@ -2560,7 +2536,6 @@ namespace fdx {
 hipStream_t library_plan_stream() {
     static hipStream_t streams[64] = {};
     static std::mutex mu;
-    if (fdx::exp_env("FDX_NO_PLAN_STREAM")) return nullptr;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
     std::lock_guard<std::mutex> lk(mu);
@@ -2620,10 +2595,8 @@ int graph_shard_knn(const double* d_coords, long long n, int dim, int k, int n_r
     loc->keep_shard = sb.release();
     // The second phase (~35 dependent launches, 0.12 ms of host time) is queued by the library's helper thread on the plan stream
     // while this thread returns to the caller: a rank's critical path is the host's way to the sketch of its own rows, which does
-    // not need the graph.  Consumers join (graph_shard_join).  FDX_SHARD_EAGER=1: here and now, on the caller's stream (=2: on the
-    // plan stream); FDX_NO_HELPER_THREAD: by the first consumer.
-    if (const char* e = fdx::exp_env("FDX_SHARD_EAGER")) return shard_queue_rest(loc, atoi(e) == 2 ? nullptr : st);   // 2: on the plan stream
-    if (!fdx::exp_env("FDX_NO_HELPER_THREAD")) loc->keep_shard->ticket = helper_submit([loc] { return shard_queue_rest(loc, nullptr); });
+    // not need the graph.  Consumers join (graph_shard_join).
+    loc->keep_shard->ticket = helper_submit([loc] { return shard_queue_rest(loc, nullptr); });
     return 0;
 }
 

@@ -386,10 +386,7 @@ void team_nth_element(KdTree& t, long long* idx, long long first, long long nth,
     std::__insertion_sort(idx + first, idx + last, icmp);
 }
 
-static long long kd_fork_min() {
-    static const long long v = fdx::exp_env("FDX_KDTREE_FORK_MIN") ? std::max(1024, atoi(fdx::exp_env("FDX_KDTREE_FORK_MIN"))) : 32768;
-    return v;
-}
+constexpr long long kKdForkMin = 32768;   // points from which a node's `less` child becomes a task of the pool
 
 // The two children of a node, the `less` one as a task of the pool when the node is large and forks are left (see the note at
 // KdTree): build(nodes, lesser) appends the subtree of that child to `nodes` and returns its root's index there.  The parent
@@ -529,7 +526,7 @@ long long kd_build_local(KdTree& t, std::vector<KdNode>& nodes, KdRec<M>* rec, l
         }
     }
     long long less = -1, greater = -1;
-    const bool fork = par_depth > 0 && n > kd_fork_min();
+    const bool fork = par_depth > 0 && n > kKdForkMin;
     kd_children(t, nodes, fork, [&](std::vector<KdNode>& into, bool lesser) {
         if (!lesser) return kd_build_local<M>(t, into, rec, base, start + p, end, scratch, par_depth - 1);
         if (!fork) return kd_build_local<M>(t, into, rec, base, start, start + p, scratch, par_depth - 1);
@@ -682,7 +679,7 @@ long long kd_build(KdTree& t, std::vector<KdNode>& nodes, long long start, long 
         }
     }
     long long less = -1, greater = -1;
-    kd_children(t, nodes, par_depth > 0 && end - start > kd_fork_min(), [&](std::vector<KdNode>& into, bool lesser) {
+    kd_children(t, nodes, par_depth > 0 && end - start > kKdForkMin, [&](std::vector<KdNode>& into, bool lesser) {
         if (!lesser) return kd_build(t, into, p, end, maxes, mins, par_depth - 1, level + 1);
         std::vector<double> mx((size_t)m), mn((size_t)m);            // (possibly on another thread: bounds scratch of its own)
         return kd_build(t, into, start, p, mx.data(), mn.data(), par_depth - 1, level + 1);
@@ -876,7 +873,6 @@ void kd_build_tree(KdTree& t, const double* coords, int64_t n, int32_t dim) {
     // the `less` child of every node above 32768 points becomes a task, five levels deep at most: 32 subtrees for a million points
     int par = t.pooled ? 5 : 0;
     if (const char* e = fdx::env("FDX_KDTREE_PAR_DEPTH")) par = t.pooled ? std::max(0, std::min(10, atoi(e))) : 0;
-    if (fdx::exp_env("FDX_KDTREE_SERIAL_BUILD")) par = 0;
     std::vector<KdNode> top;
     top.reserve(1024);
     kd_build(t, top, 0, n, mx.data(), mn.data(), par, 0);

@@ -968,8 +968,7 @@ static int launch_leverage_qr_big(const double* X, int K, int G, double reg, dou
 }
 
 bool leverage_qr_applies(int K, int G) {
-    return K >= 2 && K <= LEV_BIG_MAX_K && G >= 1 && !fdx::exp_env("FDX_LEV_NO_QR") && !fdx::env("FDX_LEV_ONE_WG") &&
-           (K <= 128 || !fdx::exp_env("FDX_LEV_NO_QR_BIG"));
+    return K >= 2 && K <= LEV_BIG_MAX_K && G >= 1 && !fdx::env("FDX_LEV_ONE_WG");
 }
 
 size_t leverage_scratch_doubles(int K, int G) {

@@ -64,8 +64,7 @@ int queue_rows_to_h(const YSource& y, const YTables& t, long long n, int G, int 
     }
     // Y_sketch is produced and consumed in chunks of 256k rows (1 GB at d = 512): measured on MI355X, smaller chunks
     // (down to Infinity-Cache size) under-fill the chip and are slower, larger ones gain nothing.
-    long long chunk_rows = 1LL << 18;
-    if (const char* e = fdx::exp_env("FDX_FIT_CHUNK")) chunk_rows = std::max<long long>(64, atoll(e));
+    const long long chunk_rows = 1LL << 18;
     const long long chunk = std::min<long long>(n, chunk_rows);
     FDX_TRY(out->dYs.alloc((size_t)chunk * d * sizeof(double)));
     double* Ys = out->dYs.as<double>();

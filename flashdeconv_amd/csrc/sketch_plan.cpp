@@ -48,7 +48,7 @@ int SketchPlan::build(const long long* col_ptr, const int* gene_idx, const doubl
     FDX_TRY(gene_bucket.alloc(gb.size() * sizeof(int)));
     FDX_TRY(copy_h2d(gene_w.p, gw.data(), gw.size() * sizeof(double), st));
     FDX_TRY(copy_h2d(gene_bucket.p, gb.data(), gb.size() * sizeof(int), st));
-    if (scatter_ok && sketch_scatter_fits(G, d) && !fdx::env("FDX_SKETCH_GATHER") && !fdx::exp_env("FDX_SKETCH_NO_SCATTER")) {
+    if (scatter_ok && sketch_scatter_fits(G, d) && !fdx::env("FDX_SKETCH_GATHER")) {
         // the scatter kernel will serve this plan: the gather schedule below is never read
         n_groups = 0;
         total_len = 0;

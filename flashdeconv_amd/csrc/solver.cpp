@@ -246,7 +246,7 @@ int solver_run(const SolveProblem& p, SolveResult* res, hipStream_t st) {
         return 0;
     };
     LoopResult loop;
-    const int n_ahead = (p.verbose || fdx::exp_env("FDX_NO_SWEEP_AHEAD")) ? 0 : 2;
+    const int n_ahead = p.verbose ? 0 : 2;
     FDX_TRY(solver_loop(stats, max_iter, p.tol, p.first_chunk, n_ahead, queue_sweep, &loop, st));
 
     const int n_iter = loop.n_iter;

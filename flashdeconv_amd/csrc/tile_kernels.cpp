@@ -46,10 +46,7 @@ struct TileArgs {
     long long ldy, n, ldh;
     int G, d, K;
     int NE, GB, NBLK, RS, jw_used;
-    int NST;   // stage buffers: 2, or 3 (raw mode with loader waves: two blocks in flight while one is consumed)
     int WB;    // WG form: bytes of a block's weight table at the head of every stage buffer ((GB + 1) doubles, 16-byte rounded)
-    int dbg;   // experiment builds (-DFDX_TILE_EXPERIMENT): phases to skip, timing only
-    int NSP, GROW;   // flat form (FF, tile_plan.h: TileFlatHost): off_tab rows of NSP offsets per (wave, block, lane class), len_tab rows of GROW bytes
 };
 
 template <typename T> struct TileVec;
@@ -60,19 +57,6 @@ template <> struct TileVec<double> { typedef double type __attribute__((ext_vect
 __device__ __forceinline__ void dma16(const void* src, unsigned char* lds_base) {
     __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
                                      (void __attribute__((address_space(3)))*)lds_base, 16, 0, 0);
-}
-
-// s_waitcnt vmcnt(n) for a wave-uniform n known only at run time (the instruction takes an immediate): waits until at most
-// min(n, 24) of this wave's vector-memory operations are outstanding - the OLDER ones have completed (loads return in order)
-__device__ __forceinline__ void wait_vmcnt_le(int n) {
-#define FDX_VMCNT(N) case N: __builtin_amdgcn_s_waitcnt(0x0f70 | ((N) & 15) | (((N) >> 4) << 14)); break;
-    switch (n) {
-        FDX_VMCNT(0) FDX_VMCNT(1) FDX_VMCNT(2) FDX_VMCNT(3) FDX_VMCNT(4) FDX_VMCNT(5) FDX_VMCNT(6) FDX_VMCNT(7)
-        FDX_VMCNT(8) FDX_VMCNT(9) FDX_VMCNT(10) FDX_VMCNT(11) FDX_VMCNT(12) FDX_VMCNT(13) FDX_VMCNT(14) FDX_VMCNT(15)
-        FDX_VMCNT(16) FDX_VMCNT(17) FDX_VMCNT(18) FDX_VMCNT(19) FDX_VMCNT(20) FDX_VMCNT(21) FDX_VMCNT(22) FDX_VMCNT(23)
-        default: __builtin_amdgcn_s_waitcnt(0x0f70 | (24 & 15) | ((24 >> 4) << 14)); break;
-    }
-#undef FDX_VMCNT
 }
 
 // group lengths are stored 8 to a 64-bit word: JW rounded up
@@ -93,22 +77,8 @@ __host__ __device__ constexpr int JW_PAD(int jw) { return (jw + 7) & ~7; }
 // what the lockstep padding steps point at, together with the zeroed pad behind every staged row).  The 40 KB this frees make
 // the column blocks larger: 5 of 1024 genes instead of 7 of 736 at 5000 genes - fewer barriers, fewer (group, block) loop
 // entries (they average ~1.1 steps), 12 % less lockstep padding.
-// FF (with WG): the FLAT schedule.  The dynamic form walks a (wave, block)'s steps group by group - a loop per group whose
-// trip count is the group's length in that block, ~1.1 at 5000 genes x 1024 buckets: every step two dependent LDS round trips
-// (offset -> weight, value) with nothing else in flight, which three waves per SIMD cannot hide (the ISA shows a
-// `s_waitcnt lgkmcnt(0)` per step).  Here the same steps, in the same order, are one flat stream served eight at a time - one
-// 16-byte read brings a lane's eight offsets, sixteen reads (weights, values) go out together, eight fused multiply-adds follow -
-// and the group a step belongs to is DATA (a byte per step, scalar loads), not control flow: the bucket sums live in two register
-// vectors that the steps index with a wave-uniform number (s_set_gpr_idx_on + v_mov: what the compiler emits for a dynamically
-// indexed ext_vector_type in registers).  Same sums, bit for bit, as the dynamic form of the same schedule.
-// MEASURED SLOWER (one 1.25M x 5000 x 50 shard, d = 1024: 9.85 ms against 8.69 ms for the group loops) and therefore behind
-// FDX_TILE_FLAT=1 only: the round trips were not the limit - a wave64 vector instruction occupies its SIMD for four cycles, the
-// group loops spend ~5 of them per step (two address forms, convert, multiply-add, pointer bump), the flat form ~10 (offset
-// unpacking, two address forms, convert, multiply-add, four moves through the indexed register) - the gather of the wide form
-// is bound by vector-instruction issue, with the 1056 MFMAs of a tile (7 us per SIMD) behind it.  Kept as a tested variant.
-typedef double tile_acc16_t __attribute__((ext_vector_type(16)));
-typedef double tile_acc8_t __attribute__((ext_vector_type(8)));
-
+// FF: always false.  It was the flat schedule of the wide raw form, measured slower and removed; the
+// parameter keeps its place because bench.py looks the kernel up in profiler output by its ten-parameter name.
 template <typename T, int MODE, int NWC, int NWL, int JW, int TT, bool AVL2, int LOGV = 0, bool WG = false, bool FF = false>
 __global__ __launch_bounds__((NWC + NWL) * 64, (NWC + NWL) / 4) void tile_sketch_kernel(
     const TileArgs a, const T* __restrict__ Yp, const int* __restrict__ row_map, const double* __restrict__ Xs,
@@ -129,19 +99,20 @@ __global__ __launch_bounds__((NWC + NWL) * 64, (NWC + NWL) / 4) void tile_sketch
     constexpr int TH = TT > 2 ? 2 : TT;                                     // type tiles per round of the final reduction
     constexpr int ROUNDS = TT / TH;
     constexpr int TS = TH * 4 * 64;
+    static_assert(!FF, "the flat schedule is gone: FF only keeps the kernel's ten-parameter name");
+    constexpr int NST = 2;                                                  // stage buffers: block i + 1 lands while block i is consumed
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, q = lane >> 4;
     const int WB = WG ? a.WB : 0;
     const int stage_bytes = WB + TILE_ROWS * a.RS;
     const int NEp = (a.NE + 7) & ~7;
-    const int NST = (NWL > 0 && MODE == FDX_PRE_RAW) ? a.NST : 2;
     double* w_l = reinterpret_cast<double*>(smem + (size_t)NST * stage_bytes);
     unsigned short* off_l = reinterpret_cast<unsigned short*>(w_l + (WG ? 0 : NEp));
     double* scales = reinterpret_cast<double*>(off_l + NEp);               // [2][16] scale of a row (log modes)
     int* rowok = reinterpret_cast<int*>(scales + 2 * TILE_ROWS);           // [2][16] every log argument of the row in the fast range
     double* logt = reinterpret_cast<double*>(smem + LOG_TAB_LDS);          // [LOG_TAB_N] (log modes), fixed place: see LOG_TAB_LDS
-    for (int i = tid; i < a.NE; i += NT) {          // FF: NE counts the flat form's offsets (NWC x NBLK x 4 x NSP)
+    for (int i = tid; i < a.NE; i += NT) {
         if (!WG) w_l[i] = w_tab[i];
         off_l[i] = off_tab[i];
     }
@@ -171,32 +142,23 @@ __global__ __launch_bounds__((NWC + NWL) * 64, (NWC + NWL) / 4) void tile_sketch
             }
         }
     };
-    auto issue_stage = [&](const T* const (&rp)[RPL], int c, int buf) -> int {   // returns the instructions issued (wave-uniform)
-#ifdef FDX_TILE_EXPERIMENT
-        if (a.dbg & 1) return 0;
-#endif
+    auto issue_stage = [&](const T* const (&rp)[RPL], int c, int buf) {
         const int gene0 = c * a.GB;
         const int bytes = (min(a.GB, a.G - gene0)) * (int)sizeof(T);
         unsigned char* base = smem + (size_t)buf * stage_bytes + WB;
-        int issued = 0;
         if (WG) {                                                           // the block's weights by gene: pieces lw, lw + NWS, ...
             const unsigned char* wsrc = reinterpret_cast<const unsigned char*>(w_tab) + (size_t)c * WB + lane * 16;
-            for (int o = lw * 1024; o < WB; o += NWS * 1024) {
+            for (int o = lw * 1024; o < WB; o += NWS * 1024)
                 if (o + lane * 16 < WB) dma16(wsrc + o, base - WB + o);
-                ++issued;
-            }
         }
 #pragma unroll
         for (int k = 0; k < RPL; ++k) {
             if (!rp[k]) continue;                                           // row past the end: stale LDS, never stored
             const unsigned char* src = reinterpret_cast<const unsigned char*>(rp[k] + gene0) + lane * 16;
             unsigned char* dst = base + (lw + NWS * k) * a.RS;
-            for (int o = 0; o < bytes; o += 1024) {
+            for (int o = 0; o < bytes; o += 1024)
                 if (o + lane * 16 < bytes) dma16(src + o, dst + o);
-                ++issued;
-            }
         }
-        return issued;
     };
     // Row sums (log modes) in the scatter kernels' order (per-lane partials over ascending vectors, butterfly over the
     // wave), so every sketch path sees the same bits; with them the row's extremes, which tell whether every log argument
@@ -273,8 +235,8 @@ __global__ __launch_bounds__((NWC + NWL) * 64, (NWC + NWL) / 4) void tile_sketch
     // one block step of a staging wave: block c of the current tile has landed; stage the next block, sum a share of the
     // next tile's rows
     auto stage_step = [&](int c, int buf, int par) {
-        if (c + 1 < a.NBLK) (void)issue_stage(rowp, c + 1, buf ^ 1);
-        else if (has_next) (void)issue_stage(rown, 0, buf ^ 1);
+        if (c + 1 < a.NBLK) issue_stage(rowp, c + 1, buf ^ 1);
+        else if (has_next) issue_stage(rown, 0, buf ^ 1);
     };
     // Row sums of the next tile as LATE as possible (the wave's k-th pair of rows in block NBLK-1-k, counted from the end):
     // the sums read the rows from HBM, the DMA of the next tile re-reads them 0 - 1 tile periods later, and the closer the
@@ -282,48 +244,30 @@ __global__ __launch_bounds__((NWC + NWL) * 64, (NWC + NWL) / 4) void tile_sketch
     auto sums_step = [&](int c, int par) {
         if (MODE != FDX_PRE_RAW && has_next) scale_rows(rown, a.NBLK - 1 - c, a.NBLK, par ^ 1);
     };
-    int young = 0;                                                          // pieces of the youngest block in flight (loader waves)
     if (NWL == 0 || wave >= NWC) {
         load_rows(tile, rowp);
-        young = issue_stage(rowp, 0, 0);
-        if (NST == 3) young = issue_stage(rowp, 1, 1);                     // the launcher gives three stages only to NBLK >= 2
+        issue_stage(rowp, 0, 0);
         if (MODE != FDX_PRE_RAW) scale_rows(rowp, 0, 1, 0);
     }
 
     if (NWL > 0 && wave >= NWC) {
         // ================================================================================================ loader wave
-        // Ring of NST stage buffers: block s is consumed from buffer s % NST.  At the barrier that opens block s (block s has
-        // landed, block s - 1 is done with) the loaders request block s + NST - 1 into the buffer block s - 1 has left.  With
-        // three stages a request goes out while the previous one is still in flight: two blocks' worth of bytes under way
-        // instead of one (with two stages every block paid its full memory latency after the barrier).
+        // Two stage buffers: block s is consumed from buffer s % 2.  At the barrier that opens block s (block s has landed,
+        // block s - 1 is done with) the loaders request block s + 1 into the buffer block s - 1 has left.
         int buf = 0, par = 0;
         for (; tile < n_tiles; tile += gridDim.x) {
             has_next = tile + gridDim.x < n_tiles;
             load_rows(tile + gridDim.x, rown);
             for (int c = 0; c < a.NBLK; ++c) {
-                if (NST == 3) wait_vmcnt_le(young);                          // everything OLDER than the youngest request: block c has landed
-                else __builtin_amdgcn_s_waitcnt(0x0f70);                     // vmcnt(0): this wave's pieces of block c have landed
+                __builtin_amdgcn_s_waitcnt(0x0f70);                          // vmcnt(0): this wave's pieces of block c have landed
                 lds_barrier();                                              // everybody's have; the buffer of block c - 1 is free
-                if (NST == 3) {
-                    const int cn = c + 2;
-                    int into = buf + 2;
-                    if (into >= 3) into -= 3;
-                    if (cn < a.NBLK) young = issue_stage(rowp, cn, into);
-                    else if (has_next) young = issue_stage(rown, cn - a.NBLK, into);
-                    else young = 0;
-                    buf = buf + 1 == 3 ? 0 : buf + 1;
-                } else {
-                    stage_step(c, buf, par);
-                    sums_step(c, par);
-                    buf ^= 1;
-                }
+                stage_step(c, buf, par);
+                sums_step(c, par);
+                buf ^= 1;
             }
             par ^= 1;
 #pragma unroll
             for (int k = 0; k < RPL; ++k) rowp[k] = rown[k];
-#ifdef FDX_TILE_EXPERIMENT
-            if (!(a.dbg & 8))
-#endif
             for (int rd = 0; rd < ROUNDS; ++rd) {                            // the consumers' reduction
                 lds_barrier();
                 if (PAIR) lds_barrier();
@@ -363,11 +307,9 @@ __global__ __launch_bounds__((NWC + NWL) * 64, (NWC + NWL) / 4) void tile_sketch
             has_next = tile + gridDim.x < n_tiles;
             load_rows(tile + gridDim.x, rown);
         }
-        double acc[FF ? 1 : JW];
+        double acc[JW];
 #pragma unroll
-        for (int j = 0; j < (FF ? 1 : JW); ++j) acc[j] = 0.0;
-        tile_acc16_t accA = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // FF: groups 0..15
-        tile_acc8_t accB = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};                                              //     groups 16..23
+        for (int j = 0; j < JW; ++j) acc[j] = 0.0;
         double4_t accm[TT];
 #pragma unroll
         for (int t = 0; t < TT; ++t) accm[t] = double4_t{0.0, 0.0, 0.0, 0.0};
@@ -388,47 +330,6 @@ __global__ __launch_bounds__((NWC + NWL) * 64, (NWC + NWL) / 4) void tile_sketch
             constexpr bool FAST = decltype(fast_tag)::value;
             const unsigned char* rowb = smem + (size_t)buf * stage_bytes + WB + r * a.RS;
             const double* wgl = reinterpret_cast<const double*>(smem + (size_t)buf * stage_bytes);   // WG: this block's weights by gene
-            if constexpr (FF) {
-                static_assert(!FF || (WG && MODE == FDX_PRE_RAW && JW <= 24), "flat form: raw mode, weights by gene, at most 24 groups per wave");
-                typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
-                const unsigned short* so = off_l + ((size_t)(wave * a.NBLK + c) * 4 + q) * a.NSP;
-                const unsigned long long* gw = reinterpret_cast<const unsigned long long*>(len_tab + (size_t)(wave * a.NBLK + c) * a.GROW);   // scalar loads
-                const int ns_a = (int)(gw[0] & 0xffffULL), ns = (int)((gw[0] >> 16) & 0xffffULL);   // steps of groups 0..15, all steps
-                auto batch = [&](int k0, auto first_tag) {
-                    const uint4_t o = *reinterpret_cast<const uint4_t*>(so + k0);
-                    const unsigned long long g8 = gw[1 + (k0 >> 3)];        // the eight steps' groups
-                    double wv[8];
-                    T yv[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const unsigned wd = o[u >> 1];
-                        const unsigned of = (u & 1) ? (wd >> 16) : (wd & 0xffffu);   // a padding step reads the padding offset: weight 0.0
-                        wv[u] = wgl[of];
-                        yv[u] = *reinterpret_cast<const T*>(rowb + (size_t)of * sizeof(T));
-                    }
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int j = (int)((g8 >> (8 * u)) & 0xffULL);
-                        if (decltype(first_tag)::value) accA[j] = fma(wv[u], (double)yv[u], accA[j]);
-                        else accB[j - 16] = fma(wv[u], (double)yv[u], accB[j - 16]);
-                    }
-                };
-                for (int k0 = 0; k0 < ns_a; k0 += 8) batch(k0, std::true_type{});
-                for (int k0 = ns_a; k0 < ns; k0 += 8) batch(k0, std::false_type{});
-                if (LAST) {
-#pragma unroll
-                    for (int j = 0; j < JW; ++j) {
-                        double an[TT];
-                        if ((j & 3) == 0) __builtin_amdgcn_sched_barrier(0);    // at most four groups' operands in flight
-#pragma unroll
-                        for (int t = 0; t < TT; ++t) an[t] = AVL2 ? *reinterpret_cast<const double*>(reinterpret_cast<const char*>(xu + (size_t)(j * TT + t) * 64) + lane8) : av[AVL2 ? 0 : j][t];
-                        const double sum = j < 16 ? accA[j < 16 ? j : 0] : accB[j < 16 ? 0 : j - 16];
-#pragma unroll
-                        for (int t = 0; t < TT; ++t) accm[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(an[t], sum, accm[t], 0, 0, 0);
-                        sq = fma(sum, sum, sq);
-                    }
-                }
-            } else {
             int p = ent_base[wave * (a.NBLK + 1) + c] + q;
             const unsigned long long* lens = reinterpret_cast<const unsigned long long*>(len_tab + ((size_t)wave * a.NBLK + c) * JW_PAD(JW));
             const unsigned off0 = off_l[p];
@@ -447,11 +348,7 @@ __global__ __launch_bounds__((NWC + NWL) * 64, (NWC + NWL) / 4) void tile_sketch
             };
 #pragma unroll
             for (int j = 0; j < JW; ++j) {
-#ifdef FDX_TILE_EXPERIMENT
-                const int len = (a.dbg & 2) ? 0 : (int)((lens[j >> 3] >> ((j & 7) * 8)) & 0xffULL);
-#else
                 const int len = (int)((lens[j >> 3] >> ((j & 7) * 8)) & 0xffULL);
-#endif
                 double an[TT];
                 if (LAST && AVL2) {
                     __builtin_amdgcn_sched_barrier(0);                       // the operand loads of later groups stay with their groups
@@ -479,18 +376,13 @@ __global__ __launch_bounds__((NWC + NWL) * 64, (NWC + NWL) / 4) void tile_sketch
                     wv = wn;
                     yv = yn;
                 }
-#ifdef FDX_TILE_EXPERIMENT
-                if (LAST && !(a.dbg & 4)) {
-#else
                 if (LAST) {
-#endif
 #pragma unroll
                     for (int t = 0; t < TT; ++t)
                         accm[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(AVL2 ? an[t] : av[AVL2 ? 0 : j][t], acc[j], accm[t], 0, 0, 0);
                     sq = fma(acc[j], acc[j], sq);
                 }
             }
-        }
         };
         auto block = [&](int c, auto last_tag) {
             if (NWL == 0) __builtin_amdgcn_s_waitcnt(0x0f70);                // vmcnt(0): this wave's pieces of block c have landed
@@ -509,7 +401,7 @@ __global__ __launch_bounds__((NWC + NWL) * 64, (NWC + NWL) / 4) void tile_sketch
             if (MODE == FDX_PRE_RAW || fast) consume(c, last_tag, std::true_type{});
             else consume(c, last_tag, std::false_type{});
             if (NWL == 0) sums_step(c, par);
-            buf = buf + 1 == NST ? 0 : buf + 1;
+            buf ^= 1;
         };
         // raw: MFMAs interleaved with the last block's gather.  Log modes: afterwards - the gather is bound by the vector ALU
         // there, and the 16 accumulator registers held through it would spill.
@@ -538,12 +430,9 @@ __global__ __launch_bounds__((NWC + NWL) * 64, (NWC + NWL) / 4) void tile_sketch
         }
         // ---- the partial tiles are added in a fixed order through LDS (the buffer of the block just consumed) and stored,
         // TH type tiles per round (the area must fit a stage buffer)
-        double* red = reinterpret_cast<double*>(smem + (size_t)(buf == 0 ? NST - 1 : buf - 1) * stage_bytes);   // the block just consumed: [NR][TS] + [NR][64]
+        double* red = reinterpret_cast<double*>(smem + (size_t)(buf ^ 1) * stage_bytes);   // the block just consumed: [NR][TS] + [NR][64]
         double* red_sq = red + (size_t)NR * TS;
         const long long s0 = tile * TILE_ROWS;
-#ifdef FDX_TILE_EXPERIMENT
-        if (!(a.dbg & 8))
-#endif
 #pragma unroll
         for (int rd = 0; rd < ROUNDS; ++rd) {
             lds_barrier();                                                  // the last block's buffer / the previous round's sums are free
@@ -602,9 +491,8 @@ __global__ __launch_bounds__((NWC + NWL) * 64, (NWC + NWL) / 4) void tile_sketch
 struct TilePlanDevice {
     TilePlanHost h;
     DevBuf w, off, len, ent_base, slot_bucket;
-    int NWC = 0, NWL = 0, JW = 0, RS = 0, TT = 0, NST = 2;
+    int NWC = 0, NWL = 0, JW = 0, RS = 0, TT = 0;
     int WB = 0;          // WG form: bytes of a block's weights-by-gene table (w holds NBLK of them); 0 = per-entry weights
-    TileFlatHost fh;     // flat form (fh.NSP > 0): `off` holds fh.off, `len` holds fh.gid
     bool wide = false;
     size_t lds = 0;
 };
@@ -657,10 +545,10 @@ static TileCfg tile_cfg(int mode, int K, int d) {
     return c;
 }
 
-static size_t tile_lds_bytes(int RS, int NE, int mode, int NST = 2, int WB = 0) {
+static size_t tile_lds_bytes(int RS, int NE, int mode, int WB = 0) {
     const size_t NEp = ((size_t)NE + 7) & ~(size_t)7;
     // WB > 0 (WG form): weights by gene inside every stage buffer, the entry table holds the 2-byte offsets only
-    const size_t below = (size_t)NST * ((size_t)WB + (size_t)TILE_ROWS * RS) + NEp * (WB ? 2 : 10) + 2 * TILE_ROWS * (8 + 4);
+    const size_t below = 2 * ((size_t)WB + (size_t)TILE_ROWS * RS) + NEp * (WB ? 2 : 10) + 2 * TILE_ROWS * (8 + 4);
     if (mode == FDX_PRE_RAW) return below;
     // log modes: the table has a fixed place at the top of the 160 KB (LOG_TAB_LDS); everything else must end below it
     return below <= (size_t)LOG_TAB_LDS ? (size_t)160 * 1024 : (size_t)161 * 1024;
@@ -672,34 +560,14 @@ static const TilePlanDevice* tile_plan_for(const SketchPlan& sp, int dtype, int 
     const TileCfg cfg = tile_cfg(mode, K, sp.d);
     const int TT = cfg.TT;
     if (K < 1 || K > 64 || (!cfg.wide && TT > 2)) return nullptr;
-    const int key0 = cfg.wide ? 24 + ((dtype == FDX_F32 ? 0 : 1) * 2 + (mode != FDX_PRE_RAW ? 1 : 0))
+    const int key = cfg.wide ? 24 + ((dtype == FDX_F32 ? 0 : 1) * 2 + (mode != FDX_PRE_RAW ? 1 : 0))
                              : ((((dtype == FDX_F32 ? 0 : 1) * 2 + (mode != FDX_PRE_RAW ? 1 : 0)) * 2 + (TT - 1)) * 3) +
                                    (cfg.NWC == 12 ? 0 : cfg.NWC == 16 ? 1 : 2);
-    // Stage buffers: two.  FDX_TILE_NST=3 (raw mode with loader waves) makes it a ring of three - two column blocks in flight
-    // while one is consumed, smaller blocks (2000 float32 genes: 3 x 704 instead of 2 x 1024).  Measured at 1M x 2000: 1.88-1.95
-    // against 1.89-1.90 ms - the consumers' gather, not the bytes in flight, sets the block period; kept as a switch.
     // The wide raw form keeps its weights by gene in the stage buffers (WG, see the kernel): 5 column blocks of 1024 genes instead
-    // of 7 of 736 at 5000 genes (one 1.25M x 5000 x 50 shard: 8.40 -> 8.05 ms).  FDX_TILE_NO_WG=1: the per-entry weight table.
-    // Measured on the same shard and NOT the default: the ring of three stage buffers on top of it (FDX_TILE_NST=3: 8 blocks of
-    // 672, 8.94 ms - more blocks, more lockstep padding, and the consumers, not the bytes in flight, set the block period) and the
-    // flat schedule (FDX_TILE_FLAT=1, see the kernel: 9.85 ms against 8.69 in the same process).
-    // (the three alternatives - FDX_TILE_NO_WG, FDX_TILE_NST=3, FDX_TILE_FLAT - were all measured slower and are compiled only
-    // into experiment builds, `make EXTRA=-DFDX_TILE_EXPERIMENT`: the shipped library has one layout per shape)
-#ifdef FDX_TILE_EXPERIMENT
-    const bool wg = cfg.wide && mode == FDX_PRE_RAW && cfg.NWL > 0 && !fdx::exp_env("FDX_TILE_NO_WG");
-    int NST = 2;
-    if (mode == FDX_PRE_RAW && cfg.NWL > 0) {
-        const char* e = fdx::exp_env("FDX_TILE_NST");
-        NST = (e && atoi(e) == 3) ? 3 : 2;
-    }
-    const bool flat = wg && fdx::exp_env("FDX_TILE_FLAT") && cfg.JW <= 24;
-#else
+    // of 7 of 736 at 5000 genes (one 1.25M x 5000 x 50 shard: 8.40 -> 8.05 ms).  One layout per shape: the per-entry weight table
+    // for the wide raw form, a ring of three stage buffers and a flat schedule were measured slower and are gone.
     const bool wg = cfg.wide && mode == FDX_PRE_RAW && cfg.NWL > 0;
-    const int NST = 2;
-    const bool flat = false;
-#endif
-    const int key = key0 + (NST == 3 ? 28 : 0) + (cfg.wide && mode == FDX_PRE_RAW && cfg.NWL > 0 && !wg ? 56 : 0) + (flat ? 112 : 0);
-    static_assert(SketchPlan::kTileKeys == 224, "key space of the schedules");
+    static_assert(SketchPlan::kTileKeys == 28, "key space of the schedules: 24 narrow (dtype x log x type tiles x wave split) + 4 wide (dtype x log)");
     std::lock_guard<std::mutex> lock(sp.tile_mu);
     if (sp.tile_tried[key]) return sp.tile[key].get();
     sp.tile_tried[key] = true;
@@ -709,7 +577,7 @@ static const TilePlanDevice* tile_plan_for(const SketchPlan& sp, int dtype, int 
     const size_t red_bytes = (size_t)(cfg.NWC > 8 || cfg.wide ? cfg.NWC / 2 : cfg.NWC) * (std::min(TT, 2) * 4 * 64 + 64) * 8;   // the kernel's reduction area
     // block sizes tried: whole 1 KB pieces; the wide form's tables leave less room, and an eighth of a piece more or less decides
     // whether 5000 genes take 7 blocks or 10 (21 % more lockstep padding)
-    const int unit = (cfg.wide || NST == 3 ? 128 : 1024) / sz;
+    const int unit = (cfg.wide ? 128 : 1024) / sz;
     std::unique_ptr<TilePlanDevice> best;
     // The reduction area overlays a stage buffer.  Rows shorter than it (up to 256 float32 genes in the log modes, 512 with two
     // type tiles; 128 float64 genes in the wide raw form) used to find no block size at all and went to the two-kernel path
@@ -721,21 +589,14 @@ static const TilePlanDevice* tile_plan_for(const SketchPlan& sp, int dtype, int 
         const int WB = wg ? (int)round_up((GB + 1) * 8, 16) : 0;
         if ((size_t)WB + (size_t)TILE_ROWS * RS < red_bytes) break;
         // cheap bound before building: the tables hold at least G entries
-        const int nst = (NST == 3 && GB < sp.G) ? 3 : 2;                     // one block per tile: the ring's look-ahead needs two
-        if (tile_lds_bytes(RS, sp.G, mode, nst, WB) > 160 * 1024) continue;
+        if (tile_lds_bytes(RS, sp.G, mode, WB) > 160 * 1024) continue;
         auto cand = std::make_unique<TilePlanDevice>();
         if (!build_tile_plan(sp.host_bucket.data(), sp.host_w.data(), sp.G, sp.d, cfg.NWC, cfg.JW, GB, &cand->h)) return nullptr;
         cand->NWC = cfg.NWC; cand->NWL = cfg.NWL; cand->JW = cfg.JW; cand->RS = RS; cand->TT = TT; cand->wide = cfg.wide;
         cand->WB = WB;
-        cand->NST = (nst == 3 && cand->h.NBLK >= 2) ? 3 : 2;
-        int n_ent = cand->h.NE;
-        if (flat) {
-            if (!build_tile_flat(cand->h, GB, &cand->fh)) return nullptr;
-            n_ent = (int)cand->fh.off.size();
-        }
-        cand->lds = tile_lds_bytes(RS, n_ent, mode, nst, WB);
-        if (dbg) std::fprintf(stderr, "[fdx] tile plan: G=%d d=%d waves=%d+%d stages=%d GB=%d blocks=%d NE=%d steps=%d lds=%zu flat rows of %d\n", sp.G, sp.d, cfg.NWC,
-                              cfg.NWL, cand->NST, GB, cand->h.NBLK, cand->h.NE, cand->h.steps, cand->lds, cand->fh.NSP);
+        cand->lds = tile_lds_bytes(RS, cand->h.NE, mode, WB);
+        if (dbg) std::fprintf(stderr, "[fdx] tile plan: G=%d d=%d waves=%d+%d GB=%d blocks=%d NE=%d steps=%d lds=%zu\n", sp.G, sp.d, cfg.NWC,
+                              cfg.NWL, GB, cand->h.NBLK, cand->h.NE, cand->h.steps, cand->lds);
         if (cand->lds > 160 * 1024) continue;
         best = std::move(cand);
         break;
@@ -766,8 +627,7 @@ static const TilePlanDevice* tile_plan_for(const SketchPlan& sp, int dtype, int 
             if (t.h.gene[i] < 0) t.h.off[i] = (unsigned short)t.h.GB;
     }
     if ((t.WB ? up(t.w, wg_tab.data(), wg_tab.size() * 8) : up(t.w, t.h.w.data(), t.h.w.size() * 8)) ||
-        (t.fh.NSP > 0 ? up(t.off, t.fh.off.data(), t.fh.off.size() * 2) : up(t.off, t.h.off.data(), t.h.off.size() * 2)) ||
-        (t.fh.NSP > 0 ? up(t.len, t.fh.gid.data(), t.fh.gid.size()) : up(t.len, len_pad.data(), len_pad.size())) || up(t.ent_base, t.h.ent_base.data(), t.h.ent_base.size() * 4) ||
+        up(t.off, t.h.off.data(), t.h.off.size() * 2) || up(t.len, len_pad.data(), len_pad.size()) || up(t.ent_base, t.h.ent_base.data(), t.h.ent_base.size() * 4) ||
         up(t.slot_bucket, t.h.slot_bucket.data(), t.h.slot_bucket.size() * 4))
         return nullptr;
     if (hipStreamSynchronize(st) != hipSuccess) return nullptr;            // the host vectors may die with the plan
@@ -789,7 +649,7 @@ __global__ void tile_xa_kernel(const double* __restrict__ Xs, const int* __restr
 
 bool tile_sketch_ok(int dtype, long long ldy, const void* Y, int G, int d, int K, int mode, const SketchPlanDev& plan,
                     hipStream_t st) {
-    if (fdx::exp_env("FDX_NO_TILE") || !plan.owner) return false;
+    if (!plan.owner) return false;
     if (dtype != FDX_F32 && dtype != FDX_F64) return false;
     if (mode != FDX_PRE_RAW && mode != FDX_PRE_LOG_CPM && mode != FDX_PRE_LOG_CPM_SPARSE) return false;
     const int sz = dtype == FDX_F32 ? 4 : 8;
@@ -816,7 +676,6 @@ struct TileLaunch {
     const int* slot_bucket;
     const double* log_tab;
     const double* XA;
-    bool flat = false;   // the flat schedule (FF)
 };
 
 // This file is compiled twice (Makefile): FDX_TILE_PART 0 holds the schedule, the entry points and the float32 kernels,
@@ -837,21 +696,21 @@ int tile_logv() {
 
 template <typename T, int MODE, int NWC, int NWL, int JW>
 static int launch_tile_tt(const TileLaunch& L, int TT, size_t lds, int grid, hipStream_t st) {
-    const void* kern = TT == 1 ? (const void*)tile_sketch_kernel<T, MODE, NWC, NWL, JW, 1, false>
-                               : (const void*)tile_sketch_kernel<T, MODE, NWC, NWL, JW, 2, false>;
+    const void* kern = nullptr;
     // log modes, 16 self-staging waves.  float64 chain (float64 rows, integer counts, FDX_TILE_LOGV=0): operands from the L2
-    // copy as in the wide form - the 32 registers they would occupy are what the 128-register budget lacks for the log1p
-    // chains (22 spills with them; 4.23 -> 4.1 ms).  float32-class chain (float32 rows): no table, no polynomial constants -
-    // the operands fit back into registers (127 VGPRs, no spills: 3.08 -> 2.87 ms); FDX_TILE_AVL2=1 fetches them all the
-    // same.  Raw (12 + 4) keeps them in registers: 2.34 ms with the fetches against 1.98 ms.
+    // copy as in the wide form (launch_tile_sketch has made it) - the 32 registers they would occupy are what the 128-register
+    // budget lacks for the log1p chains (22 spills with them; 4.23 -> 4.1 ms).  float32-class chain (float32 rows): no table, no
+    // polynomial constants - the operands fit back into registers (127 VGPRs, no spills: 3.08 -> 2.87 ms).
+    // Raw (12 + 4) keeps them in registers: 2.34 ms with the fetches against 1.98 ms.
     if constexpr (MODE != FDX_PRE_RAW && NWC == 16) {
-        if (L.XA)
-            kern = TT == 1 ? (const void*)tile_sketch_kernel<T, MODE, 16, 0, 8, 1, true> : (const void*)tile_sketch_kernel<T, MODE, 16, 0, 8, 2, true>;
+        kern = TT == 1 ? (const void*)tile_sketch_kernel<T, MODE, 16, 0, 8, 1, true> : (const void*)tile_sketch_kernel<T, MODE, 16, 0, 8, 2, true>;
         if constexpr (std::is_same<T, float>::value) {
             if (tile_logv() != 0)
-                kern = L.XA ? (TT == 1 ? (const void*)tile_sketch_kernel<T, MODE, 16, 0, 8, 1, true, 2> : (const void*)tile_sketch_kernel<T, MODE, 16, 0, 8, 2, true, 2>)
-                            : (TT == 1 ? (const void*)tile_sketch_kernel<T, MODE, 16, 0, 8, 1, false, 2> : (const void*)tile_sketch_kernel<T, MODE, 16, 0, 8, 2, false, 2>);
+                kern = TT == 1 ? (const void*)tile_sketch_kernel<T, MODE, 16, 0, 8, 1, false, 2> : (const void*)tile_sketch_kernel<T, MODE, 16, 0, 8, 2, false, 2>;
         }
+    } else {
+        kern = TT == 1 ? (const void*)tile_sketch_kernel<T, MODE, NWC, NWL, JW, 1, false>
+                       : (const void*)tile_sketch_kernel<T, MODE, NWC, NWL, JW, 2, false>;
     }
     if (lds > 64 * 1024) FDX_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     void* args[] = {(void*)&L.a, (void*)&L.Y, (void*)&L.row_map, (void*)&L.Xs, (void*)&L.H, (void*)&L.row_sumsq, (void*)&L.w_tab,
@@ -865,14 +724,7 @@ template <typename T, int MODE, int NWC, int NWL, int JW>
 static int launch_tile_wide(const TileLaunch& L, size_t lds, int grid, hipStream_t st) {
     const void* kern = nullptr;
     if constexpr (MODE == FDX_PRE_RAW && NWL > 0) {
-#ifdef FDX_TILE_EXPERIMENT
-        kern = (const void*)tile_sketch_kernel<T, MODE, NWC, NWL, JW, 4, true>;
-        if (L.a.WB) kern = L.flat ? (const void*)tile_sketch_kernel<T, MODE, NWC, NWL, JW, 4, true, 0, true, true>
-                                  : (const void*)tile_sketch_kernel<T, MODE, NWC, NWL, JW, 4, true, 0, true>;
-#else
-        if (!L.a.WB || L.flat) return fail(FDX_ERR_INVALID, "tile sketch: this layout is compiled into experiment builds only");
-        kern = (const void*)tile_sketch_kernel<T, MODE, NWC, NWL, JW, 4, true, 0, true>;
-#endif
+        kern = (const void*)tile_sketch_kernel<T, MODE, NWC, NWL, JW, 4, true, 0, true>;   // weights by gene (tile_plan_for: wg)
     } else {
         kern = (const void*)tile_sketch_kernel<T, MODE, NWC, NWL, JW, 4, true>;
     }
@@ -913,16 +765,7 @@ template int launch_tile_mode<double>(const TileLaunch&, int, int, int, size_t, 
 extern template int launch_tile_mode<double>(const TileLaunch&, int, int, int, size_t, int, hipStream_t);
 
 // H[:, 0..n) (type-major, row stride ldh) and row_sumsq[0..n) for the n spots listed by row_map (NULL = rows 0..n-1).
-// A persistent workgroup fills its compute unit (16 waves x 127 registers): a launch of 256 leaves nothing for kernels of another
-// stream until it ends.  A caller with latency-bound work to run beside the sketch (the second phase of a shard build) asks for
-// some units to be left alone; results do not depend on the grid (tiles are independent).
-static thread_local int t_reserve_cus = 0;
-int tile_sketch_reserve_cus(int cus) {
-    const int prev = t_reserve_cus;
-    t_reserve_cus = std::max(0, std::min(cus, 192));
-    return prev;
-}
-
+// A persistent workgroup fills its compute unit (16 waves x 127 registers): one per unit, at most 256.
 // Call only when tile_sketch_ok(...) holds.
 int launch_tile_sketch(const void* Y, int dtype, long long ldy, const int* row_map, long long n, int G, int d, int mode,
                        const SketchPlanDev& plan, const double* Xs, int K, double* H, long long ldh, double* row_sumsq,
@@ -933,15 +776,7 @@ int launch_tile_sketch(const void* Y, int dtype, long long ldy, const int* row_m
     TileLaunch L{};
     TileArgs& a = L.a;
     a.ldy = ldy; a.n = n; a.ldh = ldh; a.G = G; a.d = d; a.K = K;
-    a.NE = t->h.NE; a.GB = t->h.GB; a.NBLK = t->h.NBLK; a.RS = t->RS; a.jw_used = t->h.jw_used; a.NST = t->NST; a.WB = t->WB;
-#ifdef FDX_TILE_EXPERIMENT
-    if (const char* e = fdx::exp_env("FDX_TILE_DBG")) a.dbg = atoi(e);
-#endif
-    if (t->fh.NSP > 0) {
-        a.NE = (int)t->fh.off.size();
-        a.NSP = t->fh.NSP; a.GROW = t->fh.GROW;
-        L.flat = true;
-    }
+    a.NE = t->h.NE; a.GB = t->h.GB; a.NBLK = t->h.NBLK; a.RS = t->RS; a.jw_used = t->h.jw_used; a.WB = t->WB;
     L.Y = Y; L.row_map = row_map; L.Xs = Xs; L.H = H; L.row_sumsq = row_sumsq;
     L.w_tab = t->w.as<double>(); L.off_tab = t->off.as<unsigned short>(); L.len_tab = t->len.as<unsigned char>();
     L.ent_base = t->ent_base.as<int>(); L.slot_bucket = t->slot_bucket.as<int>();
@@ -951,13 +786,13 @@ int launch_tile_sketch(const void* Y, int dtype, long long ldy, const int* row_m
         if (!L.log_tab) return fail(FDX_ERR_HIP, "tile sketch: log table upload failed");
     }
     const long long n_tiles = (n + TILE_ROWS - 1) / TILE_ROWS;
-    const int grid = (int)std::min<long long>(n_tiles, 256 - t_reserve_cus);
+    const int grid = (int)std::min<long long>(n_tiles, 256);
     DevBuf xa;                                                              // wide form: X_sketch in operand order
     L.XA = nullptr;
     // narrow log modes: the float64 chain needs the registers the operands would take (operand copy in L2, fetched per
     // group); the float32-class chain leaves room for them (127 registers, no spills; the fetches cost 0.5 ms per 1M spots)
     const bool f32log = dtype == FDX_F32 && mode != FDX_PRE_RAW && tile_logv() != 0;
-    const bool narrow_avl2 = mode != FDX_PRE_RAW && t->NWC == 16 && (f32log ? fdx::exp_env("FDX_TILE_AVL2") != nullptr : !fdx::exp_env("FDX_TILE_NO_AVL2"));
+    const bool narrow_avl2 = mode != FDX_PRE_RAW && t->NWC == 16 && !f32log;
     if (t->wide || narrow_avl2) {
         const int n_groups = t->NWC * t->JW;
         FDX_TRY(xa.alloc((size_t)n_groups * t->TT * 64 * sizeof(double)));

@@ -579,7 +579,8 @@ def test_ckdtree_order_restatement_matches_scipy(case, monkeypatch):
 def test_runtime_switch_registry_matches_the_sources_and_the_tests():
     """csrc/fdx_env.cpp: every runtime switch the sources read is in the registry (at most 25 of them), nothing else reads the
     environment with getenv, and every registered switch is exercised by a test or by bench.py / a tool (the verdict's rule:
-    a switch nobody runs is a code path nobody tests).  Experiment switches (exp_env) exist only in -DFDX_EXPERIMENT builds."""
+    a switch nobody runs is a code path nobody tests).  There is one kind of switch: no exp_env, no *_EXPERIMENT build macro in the
+    sources or the Makefile."""
     import glob
     import re
     from flashdeconv_amd import _lib
@@ -588,11 +589,16 @@ def test_runtime_switch_registry_matches_the_sources_and_the_tests():
     used, raw = set(), []
     for f in glob.glob(os.path.join(ROOT, "flashdeconv_amd", "csrc", "*.cpp")) + glob.glob(os.path.join(ROOT, "flashdeconv_amd", "csrc", "*.h")):
         src = open(f).read()
-        if os.path.basename(f) not in ("fdx_env.cpp", "fdx_env.h"):
+        if os.path.basename(f) != "fdx_env.cpp":
             raw += [(os.path.basename(f), m) for m in re.findall(r'(?<![A-Za-z_:])getenv\("(FDX_[A-Z0-9_]+)"\)', src)]
         if os.path.basename(f) != "fdx_env.h":                       # (its header comment spells the call)
             used |= set(re.findall(r'(?<!exp_)env\("(FDX_[A-Z0-9_]+)"\)', src))
     assert not raw, raw
+    for dirpath, _, names in os.walk(os.path.join(ROOT, "flashdeconv_amd", "csrc")):
+        for name in names:
+            if name.endswith((".cpp", ".h")) or name == "Makefile":
+                src = open(os.path.join(dirpath, name)).read()
+                assert "exp_env" not in src and "_EXPERIMENT" not in src, os.path.join(dirpath, name)
     assert used <= set(reg), used - set(reg)
     assert set(reg) <= used, set(reg) - used                         # no dead entries either
     where = ""

@@ -2,7 +2,7 @@
 """Times the stages of one fit under environment-variable variants and reports how far each variant's result is from the
 first one's.  Usage:
     PROBE_FAMILY=counts|gaussian PROBE_N=1000000 PROBE_G=2000 PROBE_K=30 PROBE_D=512 PROBE_ITERS=3 \
-    python tools/env_probe.py "base:" "logv1:FDX_TILE_LOGV=1" "noavl2:FDX_TILE_LOGV=2,FDX_TILE_NO_AVL2=1"
+    python tools/env_probe.py "base:" "logv0:FDX_TILE_LOGV=0" "two-kernel:FDX_NO_FUSED=1"
 """
 import json
 import os

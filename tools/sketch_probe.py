@@ -10,7 +10,7 @@ fam = os.environ.get("PROBE_FAMILY", "gaussian")
 Y, X, coords = (bench.gen_gaussian if fam == "gaussian" else bench.gen_counts)(torch, n, 2000, K, dev, 0)
 variants = [dict(e.split("=") for e in v.split(",") if e) for v in os.environ.get("PROBE_VARIANTS", "").split(";")]
 for env in variants:
-    for k in ("FDX_FIT_CHUNK", "FDX_SKETCH_NO_REG", "FDX_NO_TILED"): os.environ.pop(k, None)
+    for k in ("FDX_NO_FUSED", "FDX_SKETCH_GATHER", "FDX_NO_TILED"): os.environ.pop(k, None)
     os.environ.update(env)
     m = FlashDeconv(sketch_dim=512, preprocess="raw" if fam == "gaussian" else "log_cpm", n_hvg=2000, max_iter=int(os.environ.get("PROBE_ITERS", 100)))
     m.fit(Y, X, coords, output="torch"); m.fit(Y, X, coords, output="torch")
