@@ -56,7 +56,7 @@ class FitParams(ctypes.Structure):
         ("sketch_dim", c_i32), ("mode_y", c_i32), ("mode_x", c_i32), ("graph_method", c_i32), ("k_neighbors", c_i32),
         ("lambda_auto", c_i32), ("max_iter", c_i32), ("verbose", c_i32),
         ("radius", c_double), ("lambda_spatial", c_double), ("rho_sparsity", c_double), ("tol", c_double),
-        ("stop_on_ties", c_i32), ("reserved", c_i32), ("carry", c_void_p),
+        ("stop_on_ties", c_i32), ("reserved", c_i32), ("carry", c_void_p), ("spot_diag_out_dev", c_void_p),
     ]
 
 
@@ -87,7 +87,7 @@ class FitInfo(ctypes.Structure):
         ("solve", SolveInfo), ("lambda_used", c_double), ("rho_effective", c_double), ("YtY", c_double), ("nnz", c_i64),
         ("graph_ms", c_double), ("sketch_ms", c_double), ("gram_ms", c_double), ("solve_ms", c_double),
         ("finish_ms", c_double), ("total_ms", c_double), ("prologue_ms", c_double), ("span_ms", c_double),
-        ("knn_ties", c_i64), ("status", c_i32), ("reserved", c_i32), ("carry", c_void_p),
+        ("knn_ties", c_i64), ("status", c_i32), ("reserved", c_i32), ("carry", c_void_p), ("diag_ms", c_double),
     ]
 
 
@@ -143,6 +143,8 @@ SIGNATURES = {
                                   c_double, c_i32, c_void_p, c_void_p, c_void_p]),
     "fdx_bcd_fold_dev": (c_int, [c_void_p, c_void_p, c_i32, c_void_p]),
     "fdx_objective_partials_dev": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i32, p_double, c_void_p]),
+    "fdx_spot_diagnostics_dev": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i32, c_i32, c_void_p, c_void_p,
+                                         c_void_p]),
     "fdx_normalize_dev": (c_int, [c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_void_p]),
     "fdx_gene_moments_dev": (c_int, [c_void_p, c_i32, c_i64, c_i32, c_i64, p_double, p_double, c_void_p]),
     "fdx_gather_columns_dev": (c_int, [c_void_p, c_i32, c_i64, c_i32, c_i64, p_i32, c_i32, c_void_p, c_void_p]),

@@ -227,6 +227,7 @@ class FlashDeconv:
         self.proportions_ = None
         self.gene_idx_ = None
         self.info_ = None
+        self.spot_diagnostics_ = None
         self._fitted = False
         self._graph = None
         self._adjacency = None
@@ -247,8 +248,13 @@ class FlashDeconv:
         self._adjacency = value
 
     # ------------------------------------------------------------------ fit
-    def fit(self, Y, X, coords, cell_type_names=None, output="numpy"):
-        """Fit the model (core/deconv.py:237-405).  ``output="torch"`` keeps ``beta_``/``proportions_`` in HBM."""
+    def fit(self, Y, X, coords, cell_type_names=None, output="numpy", spot_diagnostics=False):
+        """Fit the model (core/deconv.py:237-405).  ``output="torch"`` keeps ``beta_``/``proportions_`` in HBM.
+
+        ``spot_diagnostics=True`` (additive, not in the reference) also keeps the per-spot terms of the objective in
+        ``spot_diagnostics_``: ``residual_sq`` (squared sketch residual), ``sketch_sq`` (squared norm of the sketched row) and
+        ``neighbor_sq`` (half the summed squared distance to the neighbours' abundances), each ``(n_spots,)`` float64 in the
+        caller's spot order - see ``get_spot_residuals``.  One more kernel behind the fit; off, nothing is launched."""
         t_entry = time.perf_counter()
         if Y.shape[1] != X.shape[1]:
             raise ValueError(
@@ -458,6 +464,15 @@ class FlashDeconv:
                 owned += [bbuf, pbuf]
                 b_ptr, p_ptr = bbuf.ptr, pbuf.ptr
 
+            diag_t = dbuf = None
+            if spot_diagnostics:                 # one 3n block: [residual_sq | sketch_sq | neighbor_sq]
+                if output == "torch":
+                    diag_t = torch.empty(3 * n, dtype=torch.float64, device=dev)
+                    prm.spot_diag_out_dev = diag_t.data_ptr()
+                else:
+                    dbuf = _DeviceBuffer(3 * n * 8)
+                    owned.append(dbuf)
+                    prm.spot_diag_out_dev = dbuf.ptr
             objs = np.zeros(max(int(self.max_iter), 1), dtype=np.float64)
             rels = np.zeros(max(int(self.max_iter), 1), dtype=np.float64)
             info = _lib.FitInfo()
@@ -514,6 +529,11 @@ class FlashDeconv:
                 # the device spends on the whole fit (unobservable: no other reference to the old arrays exists)
                 self.beta_ = bbuf.to_host((n, K), out=self._recyclable("beta_", (n, K)))
                 self.proportions_ = pbuf.to_host((n, K), out=self._recyclable("proportions_", (n, K)))
+            self.spot_diagnostics_ = None
+            if spot_diagnostics:
+                planes = diag_t if diag_t is not None else dbuf.to_host((3 * n,))
+                self.spot_diagnostics_ = {name: planes[j * n:(j + 1) * n]
+                                          for j, name in enumerate(("residual_sq", "sketch_sq", "neighbor_sq"))}
         finally:
             for b in owned:
                 b.free()
@@ -549,6 +569,8 @@ class FlashDeconv:
         # ties resolved: the graph was rebuilt on the reference's tie order, the device span starts with the fit call that used it
         self.timings_ = _fit_timings(info, t_entry, t_graph, t_graph_done if graph_early else t_lev, t_sel, t_lev, t_done, t_call, t_ret,
                                      ties_remedy_ms, span_from_call=graph_early or ties_resolved_here or bool(resolved and n_ties))
+        if spot_diagnostics:
+            self.timings_["diagnostics_ms"] = float(info.diag_ms)
         self._fitted = True
         log(f"  Converged: {self.info_['converged']}")
         log(f"  Iterations: {self.info_['n_iterations']}")
@@ -595,6 +617,24 @@ class FlashDeconv:
     def get_abundances(self):
         self._require_fitted()
         return self.beta_
+
+    def get_spot_residuals(self, relative=True):
+        """Per-spot goodness of fit in sketch space (additive, not in the reference): ``sqrt(residual_sq / sketch_sq)`` - the share
+        of a spot's sketched row the fitted mixture leaves unexplained, 0 where the row is all zero - or, with
+        ``relative=False``, ``sqrt(residual_sq)``.  Needs ``fit(..., spot_diagnostics=True)``; same array kind as
+        ``spot_diagnostics_``."""
+        self._require_fitted()
+        if self.spot_diagnostics_ is None:
+            raise RuntimeError("No per-spot diagnostics: call fit(..., spot_diagnostics=True) first.")
+        res, sq = self.spot_diagnostics_["residual_sq"], self.spot_diagnostics_["sketch_sq"]
+        if isinstance(res, np.ndarray):
+            if not relative:
+                return np.sqrt(res)
+            return np.sqrt(np.divide(res, sq, out=np.zeros_like(res), where=sq > 0))
+        import torch
+        if not relative:
+            return torch.sqrt(res)
+        return torch.sqrt(torch.where(sq > 0, res / torch.where(sq > 0, sq, torch.ones_like(sq)), torch.zeros_like(res)))
 
     def get_dominant_cell_type(self):
         self._require_fitted()

@@ -33,7 +33,7 @@ using namespace fdx;
 
 extern "C" {
 
-int fdx_version(void) { return 200; }  // 0.2.0
+int fdx_version(void) { return 201; }  // 0.2.1: fdx_fit_params / fdx_fit_info grew (per-spot diagnostics)
 
 const char* fdx_last_error(void) { return g_last_error.c_str(); }
 

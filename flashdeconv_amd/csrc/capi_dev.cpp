@@ -344,6 +344,21 @@ int fdx_objective_partials_dev(const fdx_graph* g, const double* beta_dev, int64
     return 0;
 }
 
+int fdx_spot_diagnostics_dev(const fdx_graph* g, const double* beta_dev, int64_t ld, const double* H_dev, int64_t ldh,
+                             const double* XtX_dev, int32_t ldg, int32_t K, const double* row_sq_dev, double* out_dev,
+                             void* stream) {
+    FDX_TRY(fdx::graph_meta_sync(g));
+    FDX_REQUIRE(g && beta_dev && H_dev && XtX_dev && row_sq_dev && out_dev, "fdx_spot_diagnostics_dev: null argument");
+    FDX_REQUIRE(K >= 1 && ldg >= K, "fdx_spot_diagnostics_dev: K must be positive and ldg at least K");
+    FDX_REQUIRE(ld >= g->n_total + 1, "fdx_spot_diagnostics_dev: ld must cover own + halo + zero row");
+    FDX_REQUIRE(ldh >= g->n, "fdx_spot_diagnostics_dev: ldh must cover the own spots");
+    if (g->n == 0) return 0;
+    // a shard's local graph keeps GLOBAL ids in perm: its rows stay in the graph's own order
+    const int* perm = (g->identity_order || !g->perm.p || g->world_n > 0) ? nullptr : g->perm.as<int>();
+    return launch_spot_diagnostics(beta_dev, ld, H_dev, ldh, XtX_dev, ldg, row_sq_dev, g->ell.as<int>(), g->slice_off.as<int>(),
+                                   g->deg.as<int>(), perm, (int)g->n, g->n_slices, K, out_dev, (hipStream_t)stream);
+}
+
 int fdx_normalize_dev(const double* beta_dev, int64_t ld, int64_t n, int32_t K, double* beta_out_dev, double* prop_out_dev,
                       void* stream) {
     FDX_REQUIRE(beta_dev && n >= 0 && K > 0, "fdx_normalize_dev: bad arguments");

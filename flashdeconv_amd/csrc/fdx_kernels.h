@@ -123,6 +123,10 @@ int launch_objective_partials(const double* beta, long long ld, const double* H,
                               double* partials, hipStream_t st, int skip_quad = 0);
 int launch_normalize_export(const double* beta, long long ld, const int* perm, int n, int n_slices, int K,
                             double* beta_out, double* prop_out, hipStream_t st);
+// out = [residual_sq | sketch_sq | neighbor_sq] (3 n doubles) at row perm[i] (null: i); XtX with row stride ldg, K real types
+int launch_spot_diagnostics(const double* beta, long long ld, const double* H, long long ldh, const double* XtX, int ldg,
+                            const double* row_sq, const int* ell, const int* slice_off, const int* deg, const int* perm, int n,
+                            int n_slices, int K, double* out, hipStream_t st);
 
 // ---- bcd_kernels.cpp
 int launch_bcd_sweep(const BcdSweepArgs& a, double* generic_scratch, size_t scratch_ld, hipStream_t st);

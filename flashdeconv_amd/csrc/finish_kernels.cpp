@@ -4,7 +4,9 @@
 //   normalize_export    <- flashdeconv/core/solver.py:431-452 (normalize_proportions) fused with the layout change
 //                          from the solver's type-major / Morton-ordered beta to the reference's (n_spots, n_types)
 //                          row-major arrays in the caller's spot order.
-// Both map one lane to one spot (coalesced reads of the type planes) and stage the wave's 64 x K tile in LDS.
+//   spot_diagnostics    <- the per-spot terms of that objective, kept instead of summed (not in the reference): the squared
+//                          sketch residual, the squared norm of the sketched row, the neighbour disagreement.
+// All map one lane to one spot (coalesced reads of the type planes) and stage the wave's 64 x K tile in LDS.
 #include "fdx_internal.h"
 #include "fdx_kernels.h"
 
@@ -121,6 +123,78 @@ __global__ __launch_bounds__(256) void normalize_export_kernel(const double* __r
     }
 }
 
+// Per-spot goodness of fit: out = [residual_sq | sketch_sq | neighbor_sq], three planes of n doubles, written at row perm[i] (the
+// caller's spot order; perm may be null).  residual_sq = ||s_i - beta_i Xs||^2 in its expanded form row_sq_i - 2 beta_i.h_i +
+// beta_i' XtX beta_i, clamped at 0; neighbor_sq = 0.5 * sum_{j in N(i)} ||beta_i - beta_j||^2 in the difference form (>= 0 per
+// spot; over a symmetric graph the plane sums to tr(beta' L beta)).  XtX has row stride ldg (the bordered matrix of a padded solve:
+// only the K real types enter).  A lane reads its own column of the [k][lane] tile only (64 consecutive doubles per LDS read: no
+// bank conflict, no hand-off between lanes); ELL pad entries (m >= deg) point at the all-zero row and are masked out - in the
+// difference form they would add ||beta_i||^2.  Each lane owns its spot: no atomics, no cross-lane reduction.  LDS_TILE is a
+// template parameter: chosen at run time inside the loops, the two sources of an own abundance became one generic (flat) load
+// behind a branch per gather.
+template <bool LDS_TILE>
+__global__ __launch_bounds__(256) void spot_diagnostics_kernel(
+    const double* __restrict__ beta, long long ld, const double* __restrict__ H, long long ldh,
+    const double* __restrict__ XtX, int ldg, const double* __restrict__ row_sq, const int* __restrict__ ell_base,
+    const int* __restrict__ slice_off, const int* __restrict__ deg, const int* __restrict__ perm, int n, int n_slices, int K,
+    double* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int slice = blockIdx.x * 4 + wib;
+    if (slice >= n_slices) return;               // (no block-wide barrier below)
+    const int i = slice * 64 + lane;
+    const bool active = i < n;
+    const int ii = active ? i : n - 1;
+    double* tile = smem + (size_t)wib * K * 64;  // [k][lane]
+    if (LDS_TILE)
+        for (int k = 0; k < K; ++k) tile[k * 64 + lane] = beta[(size_t)k * ld + ii];
+    const int w0 = slice_off[slice];
+    const int w = slice_off[slice + 1] - w0;
+    const int* ell = ell_base + (size_t)w0 * 64 + lane;
+    const int dg = deg[ii];
+    auto own = [&](int k) { return LDS_TILE ? tile[k * 64 + lane] : beta[(size_t)k * ld + ii]; };
+    // neighbours, entry by entry: ONE index per list entry, then its K abundances as K independent gathers (type by type with the
+    // index inside, as the objective kernel walks the list, every gather waits for an index load of its own: 1.68 ms at 1M x 30,
+    // bound by that chain of latencies at two workgroups per CU); the next entry's index is fetched a step ahead
+    double nbr = 0.0;
+    int j_next = w > 0 ? ell[0] : 0;
+    for (int m = 0; m < w; ++m) {
+        const int j = j_next;
+        if (m + 1 < w) j_next = ell[(size_t)(m + 1) * 64];
+        double a0 = 0.0, a1 = 0.0;
+        int k = 0;
+#pragma unroll 4
+        for (; k + 1 < K; k += 2) {
+            const double d0 = own(k) - beta[(size_t)k * ld + j];
+            const double d1 = own(k + 1) - beta[(size_t)(k + 1) * ld + j];
+            a0 = fma(d0, d0, a0);
+            a1 = fma(d1, d1, a1);
+        }
+        if (k < K) {
+            const double d0 = own(k) - beta[(size_t)k * ld + j];
+            a0 = fma(d0, d0, a0);
+        }
+        if (m < dg) nbr += a0 + a1;
+    }
+    double cross = 0.0, quad = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const double bk = own(k);
+        double gb = 0.0;
+        const double* g = XtX + (size_t)k * ldg;
+        for (int l = 0; l < K; ++l) gb = fma(g[l], own(l), gb);
+        cross = fma(bk, H[(size_t)k * ldh + ii], cross);
+        quad = fma(bk, gb, quad);
+    }
+    if (!active) return;                         // tail lanes of the last slice computed on a copy of spot n - 1: nothing to write
+    const double rs = row_sq[i];
+    const size_t o = perm ? (size_t)perm[i] : (size_t)i;
+    // 24 bytes per spot at three scattered rows of 8: plain stores (non-temporal ones measured the same time: DESIGN.md section 3)
+    out[o] = fmax(fma(-2.0, cross, rs) + quad, 0.0);
+    out[(size_t)n + o] = rs;
+    out[2 * (size_t)n + o] = 0.5 * nbr;
+}
+
 static inline size_t tile_lds_bytes(int K) { return (size_t)(K | 1) * 256 * sizeof(double); }
 static inline bool tile_fits(int K) { return tile_lds_bytes(K) <= 128 * 1024; }
 
@@ -149,6 +223,25 @@ int launch_normalize_export(const double* beta, long long ld, const int* perm, i
         FDX_HIP(hipFuncSetAttribute((const void*)normalize_export_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(normalize_export_kernel, dim3(ceil_div(n_slices, 4)), dim3(256), lds, st, beta, ld, perm, n,
                        n_slices, K, use_lds, beta_out, prop_out);
+    FDX_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_spot_diagnostics(const double* beta, long long ld, const double* H, long long ldh, const double* XtX, int ldg,
+                            const double* row_sq, const int* ell, const int* slice_off, const int* deg, const int* perm, int n,
+                            int n_slices, int K, double* out, hipStream_t st) {
+    if (n <= 0) return 0;
+    const dim3 grid(ceil_div(n_slices, 4));
+    if (tile_fits(K)) {
+        const size_t lds = (size_t)K * 256 * sizeof(double);
+        if (lds > 64 * 1024)
+            FDX_HIP(hipFuncSetAttribute((const void*)spot_diagnostics_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(spot_diagnostics_kernel<true>, grid, dim3(256), lds, st, beta, ld, H, ldh, XtX, ldg, row_sq, ell,
+                           slice_off, deg, perm, n, n_slices, K, out);
+    } else {
+        hipLaunchKernelGGL(spot_diagnostics_kernel<false>, grid, dim3(256), 0, st, beta, ld, H, ldh, XtX, ldg, row_sq, ell,
+                           slice_off, deg, perm, n, n_slices, K, out);
+    }
     FDX_CHECK_LAUNCH();
     return 0;
 }

@@ -452,6 +452,16 @@ int fit_impl(const YSource& ysrc, int64_t n, int32_t G, const double* X, int32_t
     else if (beta_out_dev || prop_out_dev)
         FDX_TRY(launch_normalize_export(p.beta[r.result_buffer], ld, row_map, (int)n, g->n_slices, K, beta_out_dev,
                                         prop_out_dev, st));
+    // per-spot diagnostics on request: one more launch behind the objective pass and the export, inside finish_ms / span_ms.  It
+    // reads the K real types only (the bordered XtX of a padded solve with its own row stride)
+    Event t_diag0(true), t_diag1(true);
+    if (prm->spot_diag_out_dev) {
+        FDX_TRY(t_diag0.record(st));
+        FDX_TRY(launch_spot_diagnostics(p.beta[r.result_buffer], ld, p.H, ld, XtX_dev, KP, rows.dRowSq.as<double>(), g->ell.as<int>(),
+                                        g->slice_off.as<int>(), g->deg.as<int>(), row_map, (int)n, g->n_slices, K,
+                                        prm->spot_diag_out_dev, st));
+        FDX_TRY(t_diag1.record(st));
+    }
     FDX_TRY(t_end.record(st));
     FDX_HIP(hipStreamSynchronize(st));
     abort_drain.armed = false;
@@ -480,6 +490,7 @@ int fit_impl(const YSource& ysrc, int64_t n, int32_t G, const double* X, int32_t
     }
     info->solve_ms = t_solved.ms_since(eS1.e);
     info->finish_ms = t_end.ms_since(t_solved.e);
+    info->diag_ms = t_diag1.ms_since(t_diag0.e);
     info->total_ms = t_end.ms_since(t_begin.e);
     info->solve.total_ms = info->total_ms;
     if (objectives_out)

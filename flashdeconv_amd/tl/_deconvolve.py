@@ -4,9 +4,12 @@ forwarding the same keyword arguments to the MI355X ``FlashDeconv``."""
 
 def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512, lambda_spatial="auto", rho_sparsity=0.01,
                n_hvg=2000, n_markers_per_type=50, spatial_method="knn", k_neighbors=6, radius=None, preprocess="log_cpm",
-               layer_st=None, layer_ref=None, spatial_key="spatial", key_added="flashdeconv", random_state=0, copy=False):
+               layer_st=None, layer_ref=None, spatial_key="spatial", key_added="flashdeconv", random_state=0, copy=False,
+               spot_diagnostics=False):
     """Writes ``.obsm[key_added]`` (proportions DataFrame), ``.obs[key_added + '_dominant']`` and
-    ``.uns[key_added + '_params']``; returns the modified copy when ``copy=True``, else ``None``."""
+    ``.uns[key_added + '_params']``; returns the modified copy when ``copy=True``, else ``None``.  ``spot_diagnostics=True``
+    (additive) also writes ``.obs[key_added + '_residual']`` (relative sketch residual per spot) and
+    ``.obs[key_added + '_roughness']`` (disagreement with the neighbours' abundances, ``neighbor_sq``)."""
     from ..core.deconv import FlashDeconv
     from ..io import prepare_data, result_to_anndata
 
@@ -17,8 +20,11 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
     model = FlashDeconv(sketch_dim=sketch_dim, lambda_spatial=lambda_spatial, rho_sparsity=rho_sparsity, n_hvg=n_hvg,
                         n_markers_per_type=n_markers_per_type, spatial_method=spatial_method, k_neighbors=k_neighbors,
                         radius=radius, preprocess=preprocess, random_state=random_state, verbose=False)
-    proportions = model.fit_transform(Y, X, coords, cell_type_names=names)
+    proportions = model.fit_transform(Y, X, coords, cell_type_names=names, spot_diagnostics=spot_diagnostics)
     result_to_anndata(proportions, adata, names, key_added=key_added)
+    if spot_diagnostics:
+        adata.obs[f"{key_added}_residual"] = model.get_spot_residuals()
+        adata.obs[f"{key_added}_roughness"] = model.spot_diagnostics_["neighbor_sq"]
     adata.uns[f"{key_added}_params"] = {
         "sketch_dim": sketch_dim,
         "lambda_spatial": float(model.lambda_used_),
@@ -36,4 +42,6 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
         "converged": model.info_.get("converged", False),
         "n_iterations": model.info_.get("n_iterations", 0),
     }
+    if spot_diagnostics:
+        adata.uns[f"{key_added}_params"]["spot_diagnostics"] = True
     return adata if copy else None

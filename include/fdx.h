@@ -282,6 +282,10 @@ typedef struct fdx_fit_params {
     int32_t reserved;
     void* carry;             /* NULL, or the info->carry of a call that stopped on ties for the SAME inputs: its sketch -> H stage is taken
                                 over instead of being run again (the rebuilt graph keeps the spot order); consumed by the call */
+    double* spot_diag_out_dev; /* NULL (a zeroed struct): off.  Otherwise 3 * n doubles on the device: the per-spot diagnostics of
+                                fdx_spot_diagnostics_dev for the fitted abundances, planes [residual_sq | sketch_sq | neighbor_sq] in
+                                the caller's spot order, queued behind the objective pass and the export (a call that stops on
+                                ties writes nothing) */
 } fdx_fit_params;
 #define FDX_FIT_TIES 3
 
@@ -302,6 +306,8 @@ typedef struct fdx_fit_info {
     int32_t reserved;
     void* carry;             /* FDX_FIT_TIES: the stopped call's sketch -> H stage, still running on the device when the call returns - hand
                                 it to the next fit of the same inputs (params->carry) or release it with fdx_fit_carry_free */
+    double diag_ms;          /* hipEvent time of the per-spot diagnostics launch (part of finish_ms and span_ms); 0 when
+                                params->spot_diag_out_dev is NULL */
 } fdx_fit_info;
 /* Releases a carry that no fit consumed (waits for the work it holds). */
 int fdx_fit_carry_free(void* carry);
@@ -528,6 +534,18 @@ int fdx_bcd_fold_dev(void* stats_dev, double* rel_change_dev, int32_t it, void* 
 /* (cross, quad, spatial, l1) partial sums of the objective over the own spots (core/solver.py:269-284), to host. */
 int fdx_objective_partials_dev(const fdx_graph* g, const double* beta_dev, int64_t ld, const double* H_dev, int64_t ldh,
                                const double* XtX_dev, int32_t K, double* out4_host, void* stream);
+/* Per-spot terms of the objective for the own spots of `g` (additive, not in the reference).  out_dev: 3 * g->n doubles, planes
+ *   residual_sq = max(0, row_sq_i - 2 beta_i . h_i + beta_i' XtX beta_i)   ( = ||s_i - beta_i Xs||^2, s_i the sketched row)
+ *   sketch_sq   = row_sq_i                                                  ( = ||s_i||^2)
+ *   neighbor_sq = 0.5 * sum_{j in N(i)} ||beta_i - beta_j||^2               (0 without neighbours)
+ * so that 0.5 sum residual_sq + 0.5 lambda sum neighbor_sq + rho_eff sum beta is the objective of a symmetric graph.  beta_dev
+ * (K, ld) and H_dev (K, ldh) type-major and row_sq_dev in the graph's solver order (halo columns of beta_dev are read for the
+ * neighbours, ld >= own + halo + 1 as for the sweep; ldh >= own spots); XtX_dev with row stride ldg >= K (the bordered matrix of
+ * a padded solve: pass the real K).  Rows of a whole graph are written in the caller's spot order (row perm[i] of
+ * fdx_graph_perm_dev); a shard's local graph, whose perm holds global ids, writes its own order.  Asynchronous on `stream`. */
+int fdx_spot_diagnostics_dev(const fdx_graph* g, const double* beta_dev, int64_t ld, const double* H_dev, int64_t ldh,
+                             const double* XtX_dev, int32_t ldg, int32_t K, const double* row_sq_dev, double* out_dev,
+                             void* stream);
 /* beta (K, ld) type-major -> beta_out / prop_out (n, K) row-major in solver order of the own spots. */
 int fdx_normalize_dev(const double* beta_dev, int64_t ld, int64_t n, int32_t K, double* beta_out_dev, double* prop_out_dev,
                       void* stream);
