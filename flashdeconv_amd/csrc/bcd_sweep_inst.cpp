@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256, ((OBJ && K > 40 && K <= 64) || (K > 64 && K <=
     // tile-local neighbour slots of this spot: the first 16 live in registers for all chunks (two 16-bit slots per VGPR),
     // wider slices (rare) read the rest from memory
     unsigned slots[8];
-    // all 16 loads go out together whatever the slice width (the table is padded by 16 rows, graph_kernels.cpp); entries
+    // all 16 loads go out together whatever the slice width (the table is padded by 16 rows, graph_ell.cpp); entries
     // past the width belong to the next slice: they are replaced by the tile's ZERO slot, so that the neighbour sums below can
     // run over whole groups of four positions - a position past the width adds an exact +0.0 - instead of asking "m < w?" at
     // each of the 16 positions of every chunk (the compiler kept those 16 wave-uniform answers as lane masks, 32 scalar

@@ -107,7 +107,7 @@ int fdx_stream_sync(void* stream) {
 // ------------------------------------------------------------------------------------------------ graph
 // Host CSR -> device sliced ELL.  The conversion runs on the host because its input is a host matrix handed
 // over by the caller (the `A` of bcd_solve); graphs built from coordinates are produced on the device
-// (graph_kernels.cpp) and never pass through here.
+// (graph_ell.cpp) and never pass through here.
 int fdx_graph_from_csr(const int64_t* indptr, const int64_t* indices, int64_t n, fdx_graph** out) {
     FDX_REQUIRE(out != nullptr, "fdx_graph_from_csr: null output");
     *out = nullptr;

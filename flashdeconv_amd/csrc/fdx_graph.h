@@ -49,7 +49,7 @@ struct fdx_graph {
     // for entry e of send_idx - the tiled sweep writes a row's new abundances straight into the send staging through them
     mutable fdx::DevBuf send_head, send_ent;
     mutable int n_tiles_boundary = -1, n_tiles_interior = 0;
-    // Deferred completion (whole-graph k-NN build, graph_kernels.cpp): every kernel of the build is queued without a host
+    // Deferred completion (whole-graph k-NN build, graph_ell.cpp): every kernel of the build is queued without a host
     // round trip - the ELL is allocated for ell_cap_rows (an upper bound the kernels respect) - and the numbers only the device
     // knows (ell_rows, nnz, max_deg, halo_max, tiled) arrive in pinned memory behind meta_event.  graph_meta_sync() waits for
     // them (and rebuilds the ELL with its exact size if the bound was too small); every consumer of a graph calls it first.
@@ -67,7 +67,7 @@ struct fdx_graph {
     // overflowed) - a band-recompute shard build is then not guaranteed to hold every reverse edge
     mutable int knn_far = 0;
     mutable struct fdx_graph_plan* keep_plan = nullptr;
-    // Deferred SHARD build (graph_shard_knn, graph_kernels.cpp): the local graph of one rank - lists of own rows + band,
+    // Deferred SHARD build (graph_shard_knn, graph_shard.cpp): the local graph of one rank - lists of own rows + band,
     // symmetrise, halo, local ELL, tile tables, send lists, boundary / interior tile lists - queued without a host round trip
     // after the bounding box.  What only the device knows (n_total, send_off / recv_off, nnz, ties, far, overflow flags)
     // arrives in the pinned block behind meta_event; graph_meta_sync() takes it over.  send_off_dev / recv_off_dev are the

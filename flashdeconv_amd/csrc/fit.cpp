@@ -298,7 +298,7 @@ int fit_impl(const YSource& ysrc, int64_t n, int32_t G, const double* X, int32_t
         if (rc) { delete g; return rc; }
         *graph_inout = g;
     }
-    // a deferred build (graph_kernels.cpp) queued on ANOTHER stream: everything below reads the graph's arrays (perm first)
+    // a deferred build (graph_ell.cpp) queued on ANOTHER stream: everything below reads the graph's arrays (perm first)
     if (g->meta_pending && g->meta_event && g->meta_stream != st) FDX_HIP(hipStreamWaitEvent(st, g->meta_event, 0));
     FDX_TRY(t_graph.record(st));
 

@@ -1,14 +1,14 @@
-// Device graph builders (graph_kernels.cpp); internal.
+// Device graph builders (graph_bin / graph_knn / graph_ell / graph_shard.cpp); internal.
 #pragma once
 #include "fdx_graph.h"
 
-struct fdx_graph_plan;   // binned points of a two-phase k-NN build (graph_kernels.cpp)
+struct fdx_graph_plan;   // binned points of a two-phase k-NN build (graph_internal.h)
 
 namespace fdx {
 
 // coords: device (n, dim) row-major float64, dim in {1,2,3}
 int graph_build_knn(const double* d_coords, long long n, int dim, int k, fdx_graph* g, hipStream_t st);
-// two-phase k-NN build for spot shards (see graph_kernels.cpp): lists of rows [lo, hi) -> caller all-gathers -> own rows
+// two-phase k-NN build for spot shards (see graph_knn.cpp): lists of rows [lo, hi) -> caller all-gathers -> own rows
 // band: also the lists of the rows outside [lo, hi) in cells next to a cell with an own row; every other row of cnt reads 0
 int graph_knn_lists(const double* d_coords, long long n, int dim, int k, long long lo, long long hi, int* nbr, int* cnt,
                     fdx_graph_plan** out, hipStream_t st, bool band = false);

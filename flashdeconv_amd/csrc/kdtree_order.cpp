@@ -3,7 +3,7 @@
 // flashdeconv/utils/graph.py:60-63 builds `cKDTree(coords)` and calls `tree.query(coords, k = k + 1)`; on a regular lattice
 // (Visium-HD bins: four neighbours at distance 1, four at sqrt 2, k = 6) the k-th neighbour is one of several at the same
 // distance, and which ones come back is decided by nothing but the order in which scipy's tree visits the points.  The
-// device build (graph_kernels.cpp) breaks such ties by spot index; with knn_ties="ckdtree" the Python driver asks this file
+// device build (graph_knn.cpp) breaks such ties by spot index; with knn_ties="ckdtree" the Python driver asks this file
 // instead whenever fdx_graph_knn_ties() reports ties, and gets the reference's neighbour lists index for index.
 //
 // This is a host restatement of the published algorithm of scipy.spatial.cKDTree (third-party dependency of the reference,

@@ -1,5 +1,5 @@
 """Spatial neighbour graphs from spot coordinates: same functions as the reference's
-``flashdeconv/utils/graph.py``, built on the GPU (csrc/graph_kernels.cpp) and returned as the same
+``flashdeconv/utils/graph.py``, built on the GPU (csrc/graph_*.cpp) and returned as the same
 ``scipy.sparse.csr_matrix`` of ones (float64, int32 indices, sorted).
 
     build_knn_graph      <- utils/graph.py:25-83
@@ -26,7 +26,7 @@ def _validate_coords(coords, knn=False):
 
 
 def check_coord_dims(n, dim, knn):
-    """What the device builders take (csrc/graph_kernels.cpp): a grid over up to three axes; k-NN graphs of points with 4 to 8
+    """What the device builders take (csrc/graph_knn.cpp): a grid over up to three axes; k-NN graphs of points with 4 to 8
     coordinates by exhaustive search (up to 262144 spots).  The reference's cKDTree takes any dimension (utils/graph.py:16-22)."""
     if dim > 3 and not knn:
         raise ValueError(f"coords has {dim} dimensions: radius / grid graphs are built for 1 to 3 coordinate dimensions "

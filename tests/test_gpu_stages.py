@@ -202,6 +202,41 @@ def test_deferred_graph_build_and_its_rebuild_path(monkeypatch):
         assert np.array_equal(b, fits[0][0]) and it == fits[0][1] and lam == fits[0][2]
 
 
+@pytest.mark.parametrize("n,dim,k", [(5000, 8, 12), (257, 2, 6), (321, 2, 6)])
+def test_tile_tables_with_failed_tiles_and_a_ragged_last_slice(n, dim, k, monkeypatch):
+    """The tile kernels (csrc/graph_ell.cpp: one body, read from the ELL or - one pass - from the row segments) where they branch.
+    n = 5000 points in 8 dimensions, k = 12: the solver order bins the first three axes only, so a tile's neighbours are spread
+    over the whole set and halos straddle FDX_TILE_HALO_CAP = 1024 (under a Morton order of a ~4-per-cell grid over three axes:
+    741 to 1690) - tiles that fail beside tiles that fit: with FDX_TRACE_HOST=1 the build reports `largest halo 998, tiled 0` of 20 tiles,
+    queued and built to the end alike.  The one-pass form must still write the global-index ELL of a failed
+    tile.  The widest rows (up to 32 entries before the union) also cross the 32-key LDS path of merge_rows_kernel.
+    n = 257 and 321 (2-D, k = 6) are one row past a tile and one row past a slice: the lanes beyond n in the last slice must carry
+    the pad index and the zero slot.
+    Under every way to build (queued one pass, queued two kernels, built to the end, queued with a bound of one entry per row) the
+    adjacency is the k-d tree oracle's index for index, and a short raw fit gives the same bits, also with the global-gather
+    sweep."""
+    from flashdeconv_amd.utils import graph as G
+    from flashdeconv_amd import FlashDeconv
+    rs = np.random.RandomState(7)
+    coords = rs.rand(n, dim) * (1.0 if dim == 8 else np.sqrt(n))
+    want = orc.knn_graph_kdtree(coords, k)
+    Y, X = datagen.gaussian_raw(n, 120, 5, seed=3)[:2]
+    switches = ("FDX_GRAPH_TWO_ELL_KERNELS", "FDX_GRAPH_SYNC", "FDX_GRAPH_WCAP", "FDX_NO_TILED")
+    fits = []
+    for env in ({}, {"FDX_GRAPH_TWO_ELL_KERNELS": "1"}, {"FDX_GRAPH_SYNC": "1"}, {"FDX_GRAPH_WCAP": "1"}, {"FDX_NO_TILED": "1"}):
+        for name in switches:
+            monkeypatch.delenv(name, raising=False)
+        for name, v in env.items():
+            monkeypatch.setenv(name, v)
+        if "FDX_NO_TILED" not in env:
+            A = G.build_knn_graph(coords, k=k)
+            assert np.array_equal(A.indptr, want.indptr) and np.array_equal(A.indices, want.indices), env
+        m = FlashDeconv(sketch_dim=64, preprocess="raw", max_iter=15, k_neighbors=k).fit(Y, X, coords)
+        fits.append((m.beta_.copy(), m.info_["n_iterations"], m.lambda_used_))
+    for b, it, lam in fits[1:]:
+        assert np.array_equal(b, fits[0][0]) and it == fits[0][1] and lam == fits[0][2]
+
+
 def test_graph_errors():
     from flashdeconv_amd.utils import graph as G
     with pytest.raises(ValueError, match="coords must be 2D"):
