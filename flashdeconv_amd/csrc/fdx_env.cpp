@@ -37,7 +37,6 @@ Switch g_switches[] = {
     {"FDX_NO_FUSED", "two-kernel sketch -> H (scatter + contraction) instead of the tile kernel"},
     {"FDX_NO_TILE_WIDE", "no wide tile kernel (K > 32 / d > 704): the two-kernel path takes those shapes"},
     {"FDX_TILE_LOGV", "0: float64 log1p chain for float32 rows in the tile kernel"},
-    {"FDX_TILE_CFG", "wave split of the tile kernel: 12 (12 + 4), 16 (16 + 0), 8 (8 + 2)"},
     {"FDX_SKETCH_GATHER", "gather form of the row sketch kernel"},
     {"FDX_GRAPH_SORT", "Morton order by a radix sort instead of by counting"},
     {"FDX_GRAPH_SYNC", "graph build completed inside the call (no deferred counts)"},

@@ -59,7 +59,7 @@ int queue_rows_to_h(const YSource& y, const YTables& t, long long n, int G, int 
         if (y.csr)     // CSR rows -> LDS accumulators -> MFMA contraction -> H  (csr_kernels.cpp)
             return launch_sketch_csr_contract((const long long*)y.csr->indptr, y.csr->indices, y.csr->data, dtype, row_map, n, d,
                                               mode_y, t.sel, Xs, K, H, ldh, row_sq, st);
-        // one kernel, no Y_sketch: rows -> LDS tile -> bucket sums -> MFMA contraction -> H  (tile_kernels.cpp)
+        // one kernel, no Y_sketch: rows -> LDS tile -> bucket sums -> MFMA contraction -> H  (tile_sketch_kernel.h)
         return launch_sketch_contract(y.dense, dtype, y.ldy, row_map, n, G, d, mode_y, plan, Xs, K, H, ldh, row_sq, st);
     }
     // Y_sketch is produced and consumed in chunks of 256k rows (1 GB at d = 512): measured on MI355X, smaller chunks

@@ -9,7 +9,7 @@
 
 namespace fdx {
 
-struct TilePlanDevice;   // tile_kernels.cpp
+struct TilePlanDevice;   // tile_kernels.cpp (host side of the tile kernel)
 
 struct SketchPlan {
     int G = 0, d = 0;
@@ -20,10 +20,10 @@ struct SketchPlan {
     bool scatter_ok = false;
     DevBuf sched_gene, sched_w, group_off, slot_bucket, sched_pack, gene_w, gene_bucket;
     // per-gene form on the host (valid when scatter_ok) and the tile kernel's schedules built from it on first use,
-    // one per (input type, raw / log, type tiles, wave split) (tile_kernels.cpp)
+    // one per (input type, raw / log, form) (tile_kernels.cpp: tile_plan_for)
     std::vector<int> host_bucket;
     std::vector<double> host_w;
-    static constexpr int kTileKeys = 28;     // (input type, raw / log, type tiles, wave split): 24, + the wide form (input type, raw / log): 4
+    static constexpr int kTileKeys = 12;     // input type x raw / log x {one type tile, two type tiles, wide form}
     mutable std::shared_ptr<TilePlanDevice> tile[kTileKeys];
     mutable bool tile_tried[kTileKeys] = {};
     mutable std::mutex tile_mu;              // plans are shared through the cache: schedules are built under this lock

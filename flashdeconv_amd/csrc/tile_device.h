@@ -1,4 +1,4 @@
-// Device helpers of the tile kernel (tile_kernels.cpp).
+// Device helpers of the tile kernel (tile_sketch_kernel.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,4 +1,4 @@
-// Static schedule of the tile kernel (tile_kernels.cpp): which lane gathers which gene of a staged 16-spot tile.
+// Static schedule of the tile kernel (tile_sketch_kernel.h): which lane gathers which gene of a staged 16-spot tile.
 //
 // The CountSketch sends every gene to one bucket (flashdeconv/core/sketching.py:58-74).  The tile kernel computes the
 // bucket sums of 16 spots at a time without atomics: the d buckets are dealt to NW waves x JW groups x 4 lanes-classes

@@ -99,7 +99,7 @@ int fdx_pinned_copy_rate(size_t bytes, int32_t to_device, double* gbps_out);
  * Ys_out is (n, d) f64.  This is project_to_sketch(Y_tilde, ., Omega) when mode = FDX_PRE_RAW. */
 int fdx_sketch(const void* Y, int32_t dtype, int64_t n, int32_t G, const int64_t* col_ptr, const int32_t* gene_idx,
                const double* weight, int32_t d, int32_t mode, double* Ys_out);
-/* Host-only inspection of the gather schedule the tile kernel (csrc/tile_kernels.cpp) runs for a CountSketch
+/* Host-only inspection of the gather schedule the tile kernel (csrc/tile_sketch_kernel.h) runs for a CountSketch
  * (core/sketching.py:58-74: gene g -> bucket gene_bucket[g] with weight gene_w[g]; -1 = gene not in Omega): buckets are
  * dealt to NW waves x JW groups x 4 lane classes, genes are cut into column blocks of GB.  No device call is made, so
  * tests can replay the schedule on the CPU.  dims_out[4] = {blocks, table entries, steps, steps of the busiest wave};

@@ -13,7 +13,7 @@ one unit roundoff of the running magnitude (first-order error analysis of a dot 
     occ_y + occ_x   a bucket sum is a dot product over the genes of the bucket: one rounding per gene (product, or fused
                     multiply-add) - the largest bucket occupancy on each side;
     d               the contraction over the sketch dimension, one rounding per bucket whatever the order or the split;
-    3 + 4 + G       log modes, per side: the device log1p is within 3 ulp (csrc/tile_device.h, tile_kernels.cpp header), the
+    3 + 4 + G       log modes, per side: the device log1p is within 3 ulp (csrc/tile_device.h, tile_sketch_kernel.h header), the
                     argument y * scale carries the roundings of (sum + 1e-10), 1 / ., . * 1e4 and the product (4), and the
                     row sum of G non-negative addends at most G roundings; d log1p(x) / log1p(x) <= dx / x, so a relative
                     error of the argument is at most that of the value;
@@ -274,17 +274,21 @@ def check_case(monkeypatch, Y, X, bucket, wy, wx, d, mode, want_path, flags=0, p
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("K", [1, 16, 17, 32, 33, 48, 49, 64])
 def test_type_tiles_narrow_and_wide(K, mode, dtype, monkeypatch):
-    """1..16 types: one type tile; 17..32: two; 33..64: the wide form with four.  300 spots: 18 whole tiles and one of 12."""
+    """1..16 types: one type tile; 17..32: two; 33..64: the wide form with four.  300 spots: 18 whole tiles and one of 12.
+    The wave split (consumer waves, loader waves, groups per consumer wave) is that of the mode and the form."""
     n, G, d = 300, 600, 128
     Y, X, bucket, wy, wx = problem(n, G, K, d, mode, dtype, seed=1000 + K)
     got = check_case(monkeypatch, Y, X, bucket, wy, wx, d, mode, 1 if K <= 32 else 2)
     assert got["dims"]["TT"] == ((K + 15) // 16 if K <= 32 else 4)
+    split = {("raw", False): (12, 4, 11), ("raw", True): (12, 4, 22), ("log", False): (16, 0, 8), ("log", True): (8, 0, 32)}
+    assert tuple(got["dims"][k] for k in ("NWC", "NWL", "JW")) == split["raw" if mode == "raw" else "log", K > 32], got["dims"]
 
 
 @pytest.mark.parametrize("mode", LOG_MODES)
-@pytest.mark.parametrize("K", [17, 32, 49])
+@pytest.mark.parametrize("K", [1, 16, 17, 32, 49])
 def test_float32_rows_on_the_float64_chain(K, mode, monkeypatch):
-    """FDX_PRE_F64_MATH (integer counts stored as float32): the float64 log chain, held to the float64 bound."""
+    """FDX_PRE_F64_MATH (integer counts stored as float32): the float64 log chain, held to the float64 bound - its own kernels
+    for one type tile, two, and the wide form."""
     from flashdeconv_amd import _lib
     n, G, d = 300, 600, 128
     Y, X, bucket, wy, wx = problem(n, G, K, d, mode, np.float32, seed=1100 + K)

@@ -471,7 +471,7 @@ def test_float32_log1p_of_the_tile_kernel_is_float32_accurate():
                                                 (500, 2000, 20, 1024, "raw", np.float64), (413, 1500, 64, 512, "log_cpm", np.float64),
                                                 (600, 5000, 50, 1024, "raw", np.float32), (257, 900, 33, 96, "pearson", np.float32)])
 def test_wide_tile_kernel_matches_the_two_kernel_path_and_the_oracle(n, G, K, d, mode, dtype, monkeypatch):
-    """The wide form of the tile kernel (csrc/tile_kernels.cpp, AVL2: 33..64 cell types or sketch_dim above what the narrow
+    """The wide form of the tile kernel (csrc/tile_sketch_kernel.h, AVL2: 33..64 cell types or sketch_dim above what the narrow
     wave split owns - BASELINE configs[4] is 50 types, d = 1024): MFMA A operands fetched per group from the operand-order
     copy of X_sketch, four type tiles reduced in two rounds.  Against the oracle and against the two-kernel path
     (FDX_NO_TILE_WIDE=1: scatter sketch + split-d contraction)."""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Times the sketch -> H stage of one fit for the kernel variants (tile kernel with 12 + 4 / 16 / 8 + 2 waves, the two-kernel
-path) on the bench's synthetic inputs.  Usage: python tools/tile_probe.py [n] [G] [K] [d]"""
+"""Times the sketch -> H stage of one fit for the tile kernel and for the two-kernel path on the bench's synthetic
+inputs.  Usage: python tools/tile_probe.py [n] [G] [K] [d]"""
 import os
 import sys
 
@@ -13,7 +13,7 @@ import torch  # noqa: E402
 import bench  # noqa: E402
 from flashdeconv_amd import FlashDeconv  # noqa: E402
 
-SWITCHES = ("FDX_TILE_CFG", "FDX_NO_FUSED")
+SWITCHES = ("FDX_NO_FUSED",)
 
 
 def main():
@@ -22,8 +22,7 @@ def main():
     K = int(sys.argv[3]) if len(sys.argv) > 3 else 30
     d = int(sys.argv[4]) if len(sys.argv) > 4 else 512
     dev = torch.device("cuda:0")
-    variants = [("tile", {}), ("tile12+4", {"FDX_TILE_CFG": "12"}), ("tile16+0", {"FDX_TILE_CFG": "16"}), ("tile8+2", {"FDX_TILE_CFG": "8"}),
-                ("two-kernel", {"FDX_NO_FUSED": "1"})]
+    variants = [("tile", {}), ("two-kernel", {"FDX_NO_FUSED": "1"})]
     only = os.environ.get("FDX_PROBE_VARIANTS")
     if only:
         variants = [v for v in variants if v[0] in only.split(",")]
