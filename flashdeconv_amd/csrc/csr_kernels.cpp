@@ -606,8 +606,9 @@ __global__ __launch_bounds__(256) void csr_row_scale_kernel(const long long* __r
     for (; q < end; q += 64) { s0 += (double)data[q]; mx = fmax(mx, (double)data[q]); }
     const double s = wave_sum((s0 + s1) + (s2 + s3));
     mx = wave_max(mx);
-    // genes.py:57-59; the sign carries "every entry of the row is below 64" (log1p by table in the moments kernel)
-    if (lane == 0) scale[row] = ((mx < 64.0 && !no_table) ? 1.0 : -1.0) * (10000.0 / fmax(s, 1.0));
+    // genes.py:57-59 (np.maximum(lib, 1): a NaN library size stays NaN, hence a select and not fmax); the sign carries "every
+    // entry of the row is below 64" (log1p by table in the moments kernel)
+    if (lane == 0) scale[row] = ((mx < 64.0 && !no_table) ? 1.0 : -1.0) * (10000.0 / (s < 1.0 ? 1.0 : s));
 }
 
 // 8 waves per SIMD (<= 64 VGPRs): two 16-wave workgroups per CU - at 66 VGPRs only one fits and the kernel takes 17.6 ms
@@ -827,7 +828,8 @@ __global__ __launch_bounds__(256) void csr_fold_moments_kernel(const double* __r
     s0 = ((red[2][0][gl] + red[2][1][gl]) + red[2][2][gl]) + red[2][3][gl];
     const double m = s1 / (double)n;
     mean[g] = m;
-    var[g] = (n >= 2) ? fmax(((s2 / (double)n) - m * m) * ((double)n / (double)(n - 1)), 0.0) : 0.0;   // genes.py:74-83
+    const double v = ((s2 / (double)n) - m * m) * ((double)n / (double)(n - 1));
+    var[g] = (n >= 2) ? (v < 0.0 ? 0.0 : v) : 0.0;      // genes.py:74-83: np.maximum(var, 0), a NaN variance stays NaN
     if (NS == 3) colsum[g] = s0;
 }
 
@@ -843,7 +845,10 @@ static int launch_csr_moments_t(const long long* indptr, const int* indices, con
     // (+ 16 waves x 512 B of log1p tables, + 16 KB of row cursors on the sorted path)
     const int tile_max = (int)((cursor_path ? 136 : 64) * 1024 / (NS * sizeof(double)));
     const int tiles = ceil_div(G, tile_max);
-    const int tile = cursor_path ? std::min(G, (ceil_div(G, tiles) + 63) & ~63) : std::min(G, tile_max);
+    // (never above tile_max: with column sums it is 5802, no multiple of 64, and the even share of 11521..11604 genes in two
+    // tiles - or of 17281..17406 in three, and so on - rounds up to 5824: 512 bytes more LDS than a workgroup can have, the
+    // launch was refused)
+    const int tile = cursor_path ? std::min({G, tile_max, (ceil_div(G, tiles) + 63) & ~63}) : std::min(G, tile_max);
     const int stripes = cursor_path ? (int)std::min<long long>(csr_moment_stripes(n), 256) : csr_moment_stripes(n);
     const int rows_per_stripe = (int)((n + stripes - 1) / stripes);
     const int no_table = fdx::env("FDX_NO_LOG_TABLE") ? 1 : 0;

@@ -535,7 +535,8 @@ __global__ __launch_bounds__(256) void row_scale_kernel(const T* __restrict__ Y,
         for (int u = 0; u < 8; ++u) s += x[u];
     }
     s = wave_sum(s);
-    if (lane == 0) scale[row] = 10000.0 / fmax(s, 1.0);          // genes.py:90-92 / :57-59
+    // genes.py:90-92 / :57-59: np.maximum(total, 1).  A select, not fmax: a NaN total stays NaN as in numpy (fmax drops it)
+    if (lane == 0) scale[row] = 10000.0 / (s < 1.0 ? 1.0 : s);
 }
 
 template <typename T>
@@ -564,7 +565,10 @@ __global__ __launch_bounds__(256) void fold_moments_kernel(const double* __restr
     for (int b = 0; b < n_parts; ++b) { s1 += part[((size_t)b * 2) * G + g]; s2 += part[((size_t)b * 2 + 1) * G + g]; }
     const double m = s1 / (double)n;
     mean[g] = m;
-    var[g] = (n >= 2) ? fmax(((s2 / (double)n) - m * m) * ((double)n / (double)(n - 1)), 0.0) : 0.0;   // genes.py:74-83
+    // genes.py:74-83; the clamp is np.maximum(var, 0): a NaN variance (a NaN or an entry below -1 in the column) stays NaN -
+    // fmax would make it 0 and give the gene's whole mean bin finite dispersions where the reference's are NaN
+    const double v = ((s2 / (double)n) - m * m) * ((double)n / (double)(n - 1));
+    var[g] = (n >= 2) ? (v < 0.0 ? 0.0 : v) : 0.0;
 }
 
 // out[r, j] = Y[r, idx[j]]  (core/deconv.py:321 Y[:, gene_idx]); one wave per row, row staged through LDS
