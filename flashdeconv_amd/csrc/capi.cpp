@@ -9,6 +9,7 @@
 #include "fdx_graph.h"
 #include "graph_build.h"
 #include "fdx_internal.h"
+#include "prepare.h"
 #include "fdx_kernels.h"
 #include "sketch_plan.h"
 #include "solver.h"
@@ -77,7 +78,18 @@ int fdx_free(void* dev_ptr) {
 }
 
 int fdx_trim(void) {
+    leverage_cache_clear();          // the X caches first: their device blocks go back to the pool, and from there to the driver
+    x_side_cache_clear();
     pool_trim();
+    return 0;
+}
+
+int fdx_x_cache_stats(int64_t out[4]) {
+    FDX_REQUIRE(out != nullptr, "fdx_x_cache_stats: null output");
+    long long v[4] = {0, 0, 0, 0};
+    leverage_cache_stats(&v[0], &v[1]);
+    x_side_cache_stats(&v[2], &v[3]);
+    for (int i = 0; i < 4; ++i) out[i] = v[i];
     return 0;
 }
 

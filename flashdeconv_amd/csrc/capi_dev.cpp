@@ -245,12 +245,13 @@ int fdx_prepare_dev(const void* Y_dev, int32_t y_dtype, int64_t n, int32_t G, in
     FDX_TRY(prepare_queue(&job, Y_dev, y_dtype, n, G, ldy, row_map_dev, X, K, bucket, weight_y, weight_x, d, mode_y_in, mode_x,
                           H_out_dev, ldh, XtX_out_host, st));
     // the caller's XtX buffer belongs to the caller's stream: filled there (the stream already waits for the X side)
-    FDX_HIP(hipMemcpyAsync(XtX_out_dev, job.x.dG.p, (size_t)K * K * sizeof(double), hipMemcpyDeviceToDevice, st));
+    FDX_HIP(hipMemcpyAsync(XtX_out_dev, job.x.b->dG.p, (size_t)K * K * sizeof(double), hipMemcpyDeviceToDevice, st));
     double yty = 0.0;
     if (n > 0 && job.evSum) FDX_TRY(job.evSum.wait_on(st));
     if (n > 0) FDX_HIP(hipMemcpyAsync(&yty, job.dSum.p, sizeof(double), hipMemcpyDeviceToHost, st));
     FDX_HIP(hipStreamSynchronize(st));
     if (job.side) FDX_HIP(hipStreamSynchronize(job.side));
+    x_side_publish(&job.x, X, XtX_out_host);        // both streams are idle: the X side is complete
     if (YtY_partial_out) *YtY_partial_out = yty;
     return 0;
 }
@@ -283,7 +284,7 @@ int fdx_prepare_csr_dev(const fdx_csr_view* Y, const int32_t* gene_idx, int32_t 
     double yty = 0.0;
     if (n > 0) {
         FDX_TRY(dSum.alloc(sizeof(double)));
-        FDX_TRY(queue_rows_to_h(ysrc, tables, n, G, d, K, mode_y, nullptr, x.dXs.as<double>(), H_out_dev, ldh, false, &rows, st));
+        FDX_TRY(queue_rows_to_h(ysrc, tables, n, G, d, K, mode_y, nullptr, x.Xs(), H_out_dev, ldh, false, &rows, st));
         FDX_TRY(queue_yty(rows.dRowSq.as<double>(), n, dSum.as<double>(), &yty, nullptr, st, st));
     }
     if (XtX_out_host)

@@ -483,7 +483,7 @@ int fdx_shard_fit_dev(fdx_comm* c, const fdx_graph* g, const void* Y_dev, int32_
     shard_trace("X side + sketch queued");
     FDX_TRY(graph_shard_join(g));
     shard_trace("rest of the plan queued");
-    const double* XtX_dev = job.x.dG.as<double>();
+    const double* XtX_dev = job.x.b->dG.as<double>();
     if (KP != K) {
         PoolStream pool_xs(job.side ? job.side : st);
         FDX_TRY(dGp.alloc((size_t)KP * KP * sizeof(double)));
@@ -539,7 +539,8 @@ int fdx_shard_fit_dev(fdx_comm* c, const fdx_graph* g, const void* Y_dev, int32_
     FDX_REQUIRE(g->send_off.size() == (size_t)W + 1, "fdx_shard_fit_dev: the graph was built for a different number of ranks");
 
     // ---- lambda, scaled rho (host scalars of the sweeps): XtX has long arrived
-    FDX_TRY(job.evX.sync());
+    if (job.evX) FDX_TRY(job.evX.sync());                                   // (a cached X side is complete: no event)
+    x_side_publish(&job.x, X, Gh);
     shard_trace("XtX on the host");
     const double diag_mean = xtx_diag_mean(Gh, K);
     const double lambda = prm->lambda_auto ? auto_lambda(diag_mean, tot[0] / (double)prm->n_total_spots) : prm->lambda_spatial;

@@ -18,6 +18,7 @@
 #include "prepare.h"
 #include "sketch_plan.h"
 #include "solver.h"
+#include "x_cache.h"
 
 using namespace fdx;
 
@@ -44,6 +45,28 @@ int build_csc_from_tables(const int32_t* bucket, const double* weight, int G, in
 
 }  // namespace
 
+// The leverage scores depend on (X, regularization) alone, and a study passes one reference X to every fit: they are kept by
+// content (x_cache.h), so that a repeated X costs one comparison instead of an upload, three kernels and the host's wait for them.
+// An entry is what the first computation produced, so a hit returns the same bits.  FDX_NO_PLAN_CACHE bypasses the cache.
+struct LevEntry {
+    XCacheKey key;                  // K, G, reg, route = the route the job starts on (FDX_LEV_ONE_WG changes it); key.X -> X
+    // the signatures, in ordinary memory: the missed job's pinned buffer goes back to its pool (kept here, the next job that misses
+    // would find that pool one buffer short and allocate a new one); end_keep uploads a hit's device copy from this one
+    std::vector<double> X;
+    std::vector<double> scores;
+    int route = LEV_ROUTE_SVD;      // the route that settled
+    int dbg[8] = {0};
+};
+// (on the heap, never destroyed: at process exit the pool's statics may be gone before this translation unit's)
+static XCache<LevEntry>& lev_cache() {
+    static XCache<LevEntry>* const c = new XCache<LevEntry>(4);
+    return *c;
+}
+namespace fdx {
+void leverage_cache_clear() { lev_cache().clear(); }
+void leverage_cache_stats(long long* hits, long long* misses) { lev_cache().stats(hits, misses); }
+}  // namespace fdx
+
 // The Jacobi SVD runs in ONE workgroup, so it occupies one CU for ~1.6 ms while the other 255 idle.  begin/end let the
 // caller put the spatial-graph build (many short, latency-bound kernels on the caller's stream) under it: the job runs
 // on a library-owned non-blocking side stream.
@@ -64,6 +87,9 @@ struct fdx_leverage_job {
     double reg = 0.0;
     hipStream_t st = nullptr;
     std::shared_ptr<fdx::HelperTicket> ticket;   // begin's launches were handed to the helper thread: end waits for them first
+    std::shared_ptr<LevEntry> hit;               // a cached X: the job was complete when begin returned, nothing above is in use
+    bool cacheable = false;                      // a miss: end inserts the entry (route0: the route the key names)
+    int route0 = LEV_ROUTE_SVD;
 };
 
 namespace fdx {
@@ -99,6 +125,18 @@ extern "C" int fdx_leverage_begin_opt(const double* X, int32_t K, int32_t G, dou
     auto* job = new fdx_leverage_job();
     job->K = K;
     job->G = G;
+    job->reg = regularization;
+    job->route0 = leverage_qr_applies(K, G) ? LEV_ROUTE_QR : LEV_ROUTE_SVD;
+    if (!fdx::env("FDX_NO_PLAN_CACHE")) {
+        XCacheKey key;
+        key.K = K; key.G = G; key.reg = regularization; key.route = job->route0; key.X = X;
+        job->hit = lev_cache().find(key);
+        if (job->hit) {                          // no device work, no helper thread, no side stream
+            *out = job;
+            return 0;
+        }
+        job->cacheable = true;
+    }
     job->st = library_side_stream();
     job->hX = (double*)pinned_buffer_get((size_t)K * G * sizeof(double), &job->hX_cap);
     if (!job->hX) { delete job; return fail(FDX_ERR_HIP, "fdx_leverage_begin: pinned host buffer"); }
@@ -115,8 +153,7 @@ extern "C" int fdx_leverage_begin_opt(const double* X, int32_t K, int32_t G, dou
         FDX_TRY(job->dDbg.alloc(8 * sizeof(int)));
         FDX_HIP(hipMemcpyAsync(job->dX.p, job->hX, (size_t)K * G * sizeof(double), hipMemcpyHostToDevice, job->st));
         FDX_TRY(job->dScratch.alloc(leverage_scratch_doubles(K, G) * sizeof(double)));
-        job->reg = regularization;
-        job->route = leverage_qr_applies(K, G) ? LEV_ROUTE_QR : LEV_ROUTE_SVD;
+        job->route = job->route0;
         FDX_TRY(launch_leverage(job->dX.as<double>(), K, G, regularization, job->dW.as<double>(), job->dS.as<double>(),
                                 job->dL.as<double>(), job->dDbg.as<int>(), job->dScratch.as<double>(), job->st, job->route));
         job->pin = (double*)pinned_buffer_get((size_t)G * sizeof(double) + 64, &job->pin_cap);
@@ -149,6 +186,28 @@ extern "C" int fdx_leverage_end_keep(fdx_leverage_job* job, double* lev_out, dou
 }
 static int leverage_end_impl(fdx_leverage_job* job, double* lev_out, double** x_dev_out) {
     FDX_REQUIRE(job != nullptr, "fdx_leverage_end: null job");
+    if (job->hit) {
+        std::unique_ptr<fdx_leverage_job> owner(job);
+        const LevEntry& c = *job->hit;
+        FDX_REQUIRE(lev_out != nullptr, "fdx_leverage_end: null output");
+        std::memcpy(lev_out, c.scores.data(), (size_t)job->G * sizeof(double));
+        if (x_dev_out) {                         // a fresh device copy of X for the caller, from the entry's copy
+            hipStream_t st = library_side_stream();
+            PoolStream pool_stream(st);
+            DevBuf dX;
+            FDX_TRY(dX.alloc(c.key.words() * sizeof(double)));
+            FDX_TRY(copy_h2d(dX.p, c.X.data(), c.key.words() * sizeof(double), st));
+            FDX_HIP(hipStreamSynchronize(st));
+            dX.mark_idle();
+            *x_dev_out = dX.as<double>();
+            dX.p = nullptr;
+            dX.bytes = dX.cap = 0;
+        }
+        if (fdx::env("FDX_DEBUG"))
+            std::fprintf(stderr, "[fdx] leverage: K=%d G=%d route=%s passes/sweeps=%d converged=%d (cached)\n", job->K, job->G,
+                         c.route == LEV_ROUTE_QR ? "cholesky-qr" : "jacobi-svd", c.dbg[0], c.dbg[6]);
+        return 0;
+    }
     if (job->ticket) {
         const int qrc = helper_wait(job->ticket);
         job->ticket.reset();
@@ -197,6 +256,16 @@ static int leverage_end_impl(fdx_leverage_job* job, double* lev_out, double** x_
         job->dX.p = nullptr;
         job->dX.bytes = job->dX.cap = 0;
     }
+    if (!rc && e == hipSuccess && job->cacheable && job->hX) {
+        // the scores have arrived and the route has settled
+        auto ent = std::make_shared<LevEntry>();
+        ent->X.assign(job->hX, job->hX + (size_t)job->K * job->G);
+        ent->key.K = job->K; ent->key.G = job->G; ent->key.reg = job->reg; ent->key.route = job->route0; ent->key.X = ent->X.data();
+        ent->scores.assign(lev_out, lev_out + job->G);
+        ent->route = job->route;
+        std::memcpy(ent->dbg, dbg, sizeof(dbg));
+        lev_cache().insert(std::move(ent));
+    }
     if (!rc && fdx::env("FDX_DEBUG"))   // phase stamps in 100 MHz ticks
         std::fprintf(stderr, "[fdx] leverage: K=%d G=%d route=%s passes/sweeps=%d converged=%d\n", job->K, job->G,
                      job->route == LEV_ROUTE_QR ? "cholesky-qr" : "jacobi-svd", dbg[0], dbg[6]);
@@ -231,7 +300,8 @@ extern "C" int fdx_column_sums_dev(const void* Y_dev, int32_t dtype, int64_t n, 
 // kernel reads, and an event behind it.  The stopped call returns at once instead of draining ~3 ms of sketch that the tie remedy's
 // host work (a kd-tree build of ~20 ms) then runs beside.
 struct fdx_fit_carry {
-    fdx::DevBuf dH, dRowSq, dXs;
+    fdx::DevBuf dH, dRowSq;
+    std::shared_ptr<fdx::XSideBufs> xs;           // X_sketch, read by the fused kernels (shared with the X-side cache when published)
     fdx::YTables tables;
     fdx::Event done;
     long long n = 0, ld = 0;
@@ -348,7 +418,7 @@ int fit_impl(const YSource& ysrc, int64_t n, int32_t G, const double* X, int32_t
         FDX_TRY(evInit.record(side));
         FDX_TRY(evInit.wait_on(st));             // tables, X_sketch, XtX, beta0: all behind this one
     }
-    const double* XtX_dev = KP != K ? x.dGp.as<double>() : x.dG.as<double>();
+    const double* XtX_dev = x.XtX(K, KP);
 
     // ---- Y_sketch in solver order, contracted into H (K, ld) as it is produced - or a carry: the sketch -> H stage of a call
     // that stopped on ties for these inputs (the rebuilt graph keeps the spot order)
@@ -372,14 +442,16 @@ int fit_impl(const YSource& ysrc, int64_t n, int32_t G, const double* X, int32_t
         rows.fused = carry_in->fused;
         rows.gram_ms = carry_in->gram_ms;
     } else {
-        FDX_TRY(queue_rows_to_h(ysrc, tables, n, G, d, K, prm->mode_y, row_map, x.dXs.as<double>(), dH.as<double>(), ld, true, &rows, st));
+        FDX_TRY(queue_rows_to_h(ysrc, tables, n, G, d, K, prm->mode_y, row_map, x.Xs(), dH.as<double>(), ld, true, &rows, st));
     }
     FDX_TRY(eS1.record(st));                      // read at the end of the fit, no wait here
     // ---- the graph's counts (a build that was only queued has long finished behind the sketch launch).  Ties under stop_on_ties: the
     // caller wants the reference's choice among equidistant neighbours - nothing is solved on this graph, and the sketch -> H stage
     // that is already running goes to the caller as a carry for the fit on the rebuilt graph (tie-free inputs never pay for the
     // question; lattices no longer pay a second sketch and the wait for the first)
-    if (!prm->verbose) FDX_TRY(evG.sync());
+    // (a cached X side is complete: no event.  A new one is published now that its last copy has arrived)
+    if (!prm->verbose && evG) FDX_TRY(evG.sync());
+    if (!prm->verbose) x_side_publish(&x, X, Gh);
     FDX_TRY(graph_meta_sync(g));
     info->knn_ties = g->knn_ties;
     info->nnz = g->nnz;
@@ -390,7 +462,7 @@ int fit_impl(const YSource& ysrc, int64_t n, int32_t G, const double* X, int32_t
         FDX_TRY(carry->done.record(st));
         carry->dH.take(dH);
         carry->dRowSq.take(rows.dRowSq);
-        carry->dXs.take(x.dXs);                   // (read by the fused kernels; the X side is cheap to redo)
+        carry->xs = x.b;                          // (X_sketch is read by the fused kernels)
         carry->tables = std::move(tables);
         carry->n = n; carry->ld = ld; carry->K = K; carry->KP = KP; carry->d = d; carry->G = G; carry->mode_y = prm->mode_y;
         carry->y_id = ysrc.id();
@@ -408,7 +480,10 @@ int fit_impl(const YSource& ysrc, int64_t n, int32_t G, const double* X, int32_t
     *YtY_h = 0.0;
     Event evY;                                    // YtY has arrived (the export is queued on the same stream later)
     FDX_TRY(queue_yty(rows.dRowSq.as<double>(), n, dSum.as<double>(), YtY_h, &evY, st, (side && !prm->verbose) ? side : st));
-    if (prm->verbose) FDX_HIP(hipStreamSynchronize(st));
+    if (prm->verbose) {
+        FDX_HIP(hipStreamSynchronize(st));
+        x_side_publish(&x, X, Gh);
+    }
     trace_host("fit", "sketch queued, XtX on the host");
     const double diag_mean = xtx_diag_mean(Gh, K);
     const double lambda = prm->lambda_auto ? auto_lambda(diag_mean, (double)g->nnz / (double)n) : prm->lambda_spatial;

@@ -2,6 +2,7 @@
 #include "prepare.h"
 
 #include <algorithm>
+#include <cstring>
 #include <vector>
 
 #include "fdx_env.h"
@@ -17,33 +18,74 @@ int YTables::build(const YSource& y, int G, int d, int K, const int32_t* bucket,
     return sel.build(y.gene_idx, G, y.csr->G, bucket, weight_y, d, csr_fused, xs, who);
 }
 
+namespace {
+// (on the heap, never destroyed: the entries own pooled device buffers - see sketch_plan.cpp)
+XCache<XSideBufs>& x_side_cache() {
+    static XCache<XSideBufs>* const c = new XCache<XSideBufs>(4);
+    return *c;
+}
+}  // namespace
+
+void x_side_cache_clear() { x_side_cache().clear(); }
+void x_side_cache_stats(long long* hits, long long* misses) { x_side_cache().stats(hits, misses); }
+
 int queue_x_side(XSide* x, const double* X, const double* X_dev, int K, int KP, int G, int d, int mode_x, const int32_t* bucket,
                  const double* weight_x, double* XtX_dev, double* XtX_host, Event* done, hipStream_t xs) {
     PoolStream pool_xs(xs);
     // The schedules of an Omega are built once per content and device (sketch_plan.cpp); a new Omega's tables are uploaded on xs
     if (!x->plan) FDX_TRY(sketch_plan_cached(bucket, weight_x, G, d, xs, &x->plan));
+    if (!XtX_dev && XtX_host && !fdx::env("FDX_NO_PLAN_CACHE")) {
+        XCacheKey& k = x->key;
+        FDX_HIP(hipGetDevice(&k.dev));
+        k.K = K; k.KP = KP; k.G = G; k.d = d; k.mode = mode_x;
+        k.route = fdx::env("FDX_SKETCH_GATHER") ? 1 : 0;      // (the other form of sketch_rows adds in another order)
+        k.plan = x->plan.get();
+        k.X = X;
+        x->b = x_side_cache().find(k);
+        if (x->b) {
+            std::memcpy(XtX_host, x->b->XtX.data(), (size_t)K * K * sizeof(double));
+            return 0;
+        }
+        x->cacheable = true;
+    }
+    x->b = std::make_shared<XSideBufs>();
+    XSideBufs& b = *x->b;
     if (!X_dev) FDX_TRY(x->dX.alloc((size_t)K * G * sizeof(double)));
-    FDX_TRY(x->dXs.alloc((size_t)K * d * sizeof(double)));
+    FDX_TRY(b.dXs.alloc((size_t)K * d * sizeof(double)));
     if (!XtX_dev) {
-        FDX_TRY(x->dG.alloc((size_t)K * K * sizeof(double)));
-        XtX_dev = x->dG.as<double>();
+        FDX_TRY(b.dG.alloc((size_t)K * K * sizeof(double)));
+        XtX_dev = b.dG.as<double>();
     }
     if (!X_dev) {                                   // (else: already there - the leverage job's copy, complete)
         FDX_TRY(copy_h2d(x->dX.p, X, (size_t)K * G * sizeof(double), xs));
         X_dev = x->dX.as<double>();
     }
-    double* Xs = x->dXs.as<double>();
+    double* Xs = b.dXs.as<double>();
     FDX_TRY(launch_sketch_rows(X_dev, FDX_F64, G, nullptr, K, G, d, mode_x, x->plan->dev(), Xs, d, nullptr, xs));
     FDX_TRY(launch_xyt(Xs, Xs, d, K, d, K, XtX_dev, K, nullptr, xs));
     if (KP != K) {
-        FDX_TRY(x->dGp.alloc((size_t)KP * KP * sizeof(double)));
-        FDX_TRY(solver_pad_square(XtX_dev, K, x->dGp.as<double>(), KP, xs));
+        FDX_TRY(b.dGp.alloc((size_t)KP * KP * sizeof(double)));
+        FDX_TRY(solver_pad_square(XtX_dev, K, b.dGp.as<double>(), KP, xs));
     }
     // XtX goes to the host NOW: lambda and the scaled rho are host scalars of the sweeps, and with them known early the solve
     // is queued behind the sketch without the host waiting for it
     if (XtX_host) FDX_HIP(hipMemcpyAsync(XtX_host, XtX_dev, (size_t)K * K * sizeof(double), hipMemcpyDeviceToHost, xs));
     if (done) FDX_TRY(done->record(xs));
     return 0;
+}
+
+void x_side_publish(XSide* x, const double* X, const double* XtX_host) {
+    if (!x->cacheable || !x->b || x->b->published || !X || !XtX_host) return;
+    XSideBufs& b = *x->b;
+    const size_t K = (size_t)x->key.K;
+    b.X.assign(X, X + x->key.words());
+    b.XtX.assign(XtX_host, XtX_host + K * K);
+    b.plan = x->plan;
+    b.key = x->key;
+    b.key.X = b.X.data();
+    b.published = true;
+    x->cacheable = false;
+    x_side_cache().insert(x->b);
 }
 
 int queue_rows_to_h(const YSource& y, const YTables& t, long long n, int G, int d, int K, int mode_y, const int* row_map,
@@ -141,11 +183,11 @@ int prepare_queue(PrepareJob* job, const void* Y_dev, int y_dtype, long long n, 
     }
     if (weight_x == weight_y) job->x.plan = job->y.plan;
     FDX_TRY(queue_x_side(&job->x, X, X_dev, K, K, G, d, mode_x, bucket, weight_x, nullptr, XtX_host, &job->evX, xs));
-    if (side) FDX_TRY(job->evX.wait_on(st));        // the tables, X_sketch, XtX: all behind this one
+    if (side && job->evX) FDX_TRY(job->evX.wait_on(st));   // the tables, X_sketch, XtX: all behind this one (a cached X side: complete)
     if (n == 0) return 0;
     FDX_REQUIRE(Y_dev != nullptr, "fdx_prepare_dev: null Y");
     FDX_TRY(job->dSum.alloc(sizeof(double)));
-    FDX_TRY(queue_rows_to_h(ysrc, job->y, n, G, d, K, mode_y, row_map_dev, job->x.dXs.as<double>(), H_out_dev, ldh, false,
+    FDX_TRY(queue_rows_to_h(ysrc, job->y, n, G, d, K, mode_y, row_map_dev, job->x.Xs(), H_out_dev, ldh, false,
                             &job->rows, st));
     // the shard's partial YtY only enters the objective: its reduction goes to the side stream (behind the sketch, beside the
     // first sweep) instead of standing between the sketch and the sweeps

@@ -61,8 +61,14 @@ int fdx_device_name(char* buf, int buflen);
 /* ---- plain device memory helpers (so a ctypes-only binding needs no other GPU runtime) ---------------- */
 int fdx_malloc(void** dev_ptr, size_t bytes);
 int fdx_free(void* dev_ptr);
-/* Device scratch is recycled through a caching pool; fdx_trim() returns every cached block to the driver. */
+/* Device scratch is recycled through a caching pool; fdx_trim() returns every cached block to the driver (and drops the two
+ * caches below, whose entries own device blocks). */
 int fdx_trim(void);
+/* What depends on the signature matrix X alone is kept by content, at most 4 entries each: the leverage scores (fdx_leverage_*)
+ * and the X side of a fit (X_sketch, XtX: fdx_fit_dev, fdx_fit_csr_dev, fdx_prepare_dev, fdx_shard_fit_dev).  A hit returns what
+ * the first computation produced, bit for bit; FDX_NO_PLAN_CACHE bypasses both.  out: {leverage hits, leverage misses, X-side
+ * hits, X-side misses} since the library was loaded (bypassed calls count as neither). */
+int fdx_x_cache_stats(int64_t out[4]);
 int fdx_memcpy_h2d(void* dev_dst, const void* host_src, size_t bytes, void* stream);
 int fdx_memcpy_d2h(void* host_dst, const void* dev_src, size_t bytes, void* stream);
 int fdx_memset(void* dev_dst, int value, size_t bytes, void* stream);
