@@ -636,6 +636,17 @@ class FlashDeconv:
             return torch.sqrt(res)
         return torch.sqrt(torch.where(sq > 0, res / torch.where(sq > 0, sq, torch.ones_like(sq)), torch.zeros_like(res)))
 
+    def get_spatial_autocorrelation(self, what="proportions", neighbor_mean=False):
+        """Moran's I per cell type, the K x K bivariate Moran matrix (neighbourhood co-localisation) and, with
+        ``neighbor_mean=True``, each spot's neighbour-averaged composition, over the graph the fit used (additive, not in the
+        reference): ``utils.spatial_stats.spatial_autocorrelation`` on ``proportions_`` (``what="proportions"``) or ``beta_``
+        (``what="abundances"``) and the model's device graph.  Works for both ``output`` kinds of ``fit``."""
+        self._require_fitted()
+        if what not in ("proportions", "abundances"):
+            raise ValueError(f"Unknown what: {what}. Choose from 'proportions', 'abundances'.")
+        from ..utils.spatial_stats import spatial_autocorrelation
+        return spatial_autocorrelation(self.proportions_ if what == "proportions" else self.beta_, self, neighbor_mean=neighbor_mean)
+
     def get_dominant_cell_type(self):
         self._require_fitted()
         if hasattr(self.proportions_, "argmax") and not isinstance(self.proportions_, np.ndarray):

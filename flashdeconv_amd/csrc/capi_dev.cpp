@@ -360,6 +360,41 @@ int fdx_spot_diagnostics_dev(const fdx_graph* g, const double* beta_dev, int64_t
                                    g->deg.as<int>(), perm, (int)g->n, g->n_slices, K, out_dev, (hipStream_t)stream);
 }
 
+int fdx_spatial_autocorr_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, int32_t K, double* mean_out, double* m2_out,
+                             double* C_out, int64_t* counts_out, double* neighbor_mean_dev, void* stream) {
+    FDX_TRY(fdx::graph_meta_sync(g));
+    FDX_REQUIRE(g && V_dev && mean_out && m2_out && C_out && counts_out, "fdx_spatial_autocorr_dev: null argument");
+    FDX_REQUIRE(K >= 1 && ldv >= K, "fdx_spatial_autocorr_dev: K must be positive and ldv at least K");
+    FDX_REQUIRE(!g->shard_pending && g->n_total == g->n && g->world_n == 0,
+                "fdx_spatial_autocorr_dev: a shard's local graph is refused (whole graphs on one GPU only)");
+    FDX_REQUIRE(g->n < (1LL << 31) - 128, "fdx_spatial_autocorr_dev: too many spots");
+    hipStream_t st = (hipStream_t)stream;
+    PoolStream pool_stream(st);
+    const size_t KK = (size_t)K * K;
+    counts_out[0] = g->n;
+    counts_out[1] = counts_out[2] = 0;
+    if (g->n == 0) {                                    // no spots: no mean
+        std::fill(mean_out, mean_out + K, std::nan(""));
+        std::fill(m2_out, m2_out + K, 0.0);
+        std::fill(C_out, C_out + KK, 0.0);
+        return 0;
+    }
+    const SpatialStatsPlan plan = spatial_stats_plan(g->n, K);
+    DevBuf scratch, out;
+    FDX_TRY(scratch.alloc(plan.scratch_doubles * sizeof(double)));
+    FDX_TRY(out.alloc(plan.out_doubles * sizeof(double)));
+    const int* perm = (g->identity_order || !g->perm.p) ? nullptr : g->perm.as<int>();
+    FDX_TRY(launch_spatial_stats(plan, V_dev, ldv, (int)g->n, K, g->ell.as<int>(), g->slice_off.as<int>(), g->deg.as<int>(), perm,
+                                 scratch.as<double>(), out.as<double>(), neighbor_mean_dev, st));
+    std::vector<double> host(plan.out_doubles);
+    FDX_TRY(copy_d2h(host.data(), out.p, plan.out_doubles * sizeof(double), st));   // the call's one host synchronisation
+    std::copy(host.begin(), host.begin() + K, mean_out);
+    std::copy(host.begin() + K, host.begin() + 2 * (size_t)K, m2_out);
+    std::copy(host.begin() + 2 * (size_t)K, host.begin() + 2 * (size_t)K + KK, C_out);
+    std::memcpy(counts_out + 1, host.data() + 2 * (size_t)K + KK, 2 * sizeof(int64_t));
+    return 0;
+}
+
 int fdx_normalize_dev(const double* beta_dev, int64_t ld, int64_t n, int32_t K, double* beta_out_dev, double* prop_out_dev,
                       void* stream) {
     FDX_REQUIRE(beta_dev && n >= 0 && K > 0, "fdx_normalize_dev: bad arguments");

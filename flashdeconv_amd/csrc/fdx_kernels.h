@@ -128,6 +128,23 @@ int launch_spot_diagnostics(const double* beta, long long ld, const double* H, l
                             const double* row_sq, const int* ell, const int* slice_off, const int* deg, const int* perm, int n,
                             int n_slices, int K, double* out, hipStream_t st);
 
+// ---- spatial_stats_kernels.cpp
+// Sizes and grids of one spatial-statistics call on n spots and K columns (functions of n and K only).
+struct SpatialStatsPlan {
+    long long ld;                // row stride of the Z and lag planes: n + 1 rounded up to 64
+    int n_slices;
+    int colsum_blocks, rows_per_block, centre_blocks, lag_blocks, cross_blocks, pair_tiles_1d;
+    size_t partials_doubles;     // largest partials block of the four passes
+    size_t scratch_doubles;      // Z and lag planes (K, ld) each, then the partials
+    size_t out_doubles;          // [mean K | m2 K | C K*K | sum deg, sum deg^2 as int64]
+};
+SpatialStatsPlan spatial_stats_plan(long long n, int K);
+// V (n, K) row-major with row stride ldv in the caller's spot order; perm null: the graph keeps that order.  out (device) as laid
+// out above; nbr_mean (n, K) row-major in the caller's order, or null.  The graph must be whole (pad index n).
+int launch_spatial_stats(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* ell,
+                         const int* slice_off, const int* deg, const int* perm, double* scratch, double* out, double* nbr_mean,
+                         hipStream_t st);
+
 // ---- bcd_kernels.cpp
 int launch_bcd_sweep(const BcdSweepArgs& a, double* generic_scratch, size_t scratch_ld, hipStream_t st);
 // More than 64 cell types, no register-resident instantiation: the LDS-resident sweep (bcd_kernels.cpp) while K x 64 doubles fit;

@@ -1,0 +1,297 @@
+// Spatial autocorrelation of per-spot values V (n, K) over the model's graph (not in the reference): with A the symmetric binary
+// adjacency held as the sliced ELL, mean_a = (1/n) sum_i V_ia, Z = V - mean, the kernels produce
+//   m2_a = sum_i Z_ia^2,   lag = A Z,   C = Z' lag (K, K),   sum_i deg_i and sum_i deg_i^2,
+// and on request the neighbour-averaged values (A V)_ia / deg_i in the caller's spot order.  Moran's I, the bivariate Moran matrix
+// and the z scores are assembled from these on the host (flashdeconv_amd/utils/spatial_stats.py).
+//
+// Four passes, each a grid-stride kernel on at most SS_CAP_BLOCKS workgroups that leaves per-workgroup partials, and one
+// fixed-order reduction of the partials behind each: no floating-point atomics, the grid depends on (n, K) only, so two calls on the
+// same inputs add the same numbers in the same order.
+//   column sums   V row-major in the caller's order -> mean
+//   centre        Z = V - mean, transposed into type-major planes (K, ld) in the graph's solver order (position p holds spot
+//                 perm[p]: the layout beta has in the solver), through a [spot][type] LDS tile of 32 types at a time; positions
+//                 n .. ld - 1 are written as zeros, so the ELL pad index (n) gathers zeros and needs no mask; m2 partials
+//   lag           one lane per spot, one wave per 64-spot slice: ONE index per ELL entry, then KC gathers into KC register
+//                 accumulators (KC a template parameter: 8, 16 or 32 types per walk of the slice's list - more types walk the list
+//                 again); lag planes (K, ld), the degree sums, neighbor_mean = lag / deg + mean
+//   cross         C = Z' lag as a skinny float64 product: a workgroup owns a 32 x 32 tile of the pair space (blockIdx.y; any K),
+//                 stages 64 positions of the 32 + 32 planes in LDS and keeps a 2 x 2 block of C per thread in registers
+// The two-pass centred form is what makes near-constant columns (proportions) safe: sum V^2 - n mean^2 is never formed.
+#include "fdx_internal.h"
+#include "fdx_kernels.h"
+
+#include <algorithm>
+
+namespace fdx {
+
+constexpr int SS_CAP_BLOCKS = 1024;      // cap of every grid here: partials do not grow with n
+constexpr int SS_KT = 32;                // centre: types staged at a time
+constexpr int SS_KS = SS_KT + 1;         //         odd row stride of the [spot][type] tile (column reads hit 64 banks)
+constexpr int SS_CT = 32;                // cross: edge of a pair-space tile
+constexpr int SS_CP = 64;                //        positions staged at a time (one slice)
+
+// same-wave LDS hand-off: a wave's ds operations execute in order; this keeps the compiler from moving them across
+__device__ __forceinline__ void wave_lds_handoff() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// partials[b][c] = sum of V[r][c] over block b's rows [b * rows_per_block, ...): 256 / K rows in flight per pass (consecutive
+// threads read consecutive addresses of a row), their running sums added in a fixed order at the end
+__global__ __launch_bounds__(256) void ss_colsum_kernel(const double* __restrict__ V, long long ldv, int n, int K,
+                                                        int rows_per_block, double* __restrict__ partials) {
+    __shared__ double red[256];
+    const long long r0 = (long long)blockIdx.x * rows_per_block;
+    const long long r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
+    for (int c0 = 0; c0 < K; c0 += 256) {
+        const int Kc = K - c0 < 256 ? K - c0 : 256;
+        const int rpp = 256 / Kc;
+        const int c = threadIdx.x % Kc, rs = threadIdx.x / Kc;
+        double s = 0.0;
+        if (rs < rpp)
+            for (long long r = r0 + rs; r < r1; r += rpp) s += V[(size_t)r * ldv + c0 + c];
+        red[threadIdx.x] = s;
+        __syncthreads();
+        if ((int)threadIdx.x < Kc) {
+            double t = 0.0;
+            for (int j = 0; j < rpp; ++j) t += red[j * Kc + threadIdx.x];
+            partials[(size_t)blockIdx.x * K + c0 + threadIdx.x] = t;
+        }
+        __syncthreads();
+    }
+}
+
+// out[i] = (partials[0][i] + partials[1][i] + ...) / div, in that order
+template <class T>
+__global__ __launch_bounds__(256) void ss_reduce_kernel(const T* __restrict__ partials, int nparts, long long width, T div,
+                                                        T* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= width) return;
+    T s = 0;
+    for (int b = 0; b < nparts; ++b) s += partials[(size_t)b * width + i];
+    out[i] = s / div;
+}
+
+// Z[k][p] = V[perm[p]][k] - mean[k] for p < n, 0 for n <= p < ld (n_slices_ld = ld / 64 slices are written);
+// m2_partials[block][k] = the block's share of sum_p Z[k][p]^2
+__global__ __launch_bounds__(256) void ss_centre_kernel(const double* __restrict__ V, long long ldv, const double* __restrict__ mean,
+                                                        const int* __restrict__ perm, int n, int n_slices_ld, int K,
+                                                        double* __restrict__ Z, long long ld, double* __restrict__ m2_partials) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];   // 4 tiles [64][SS_KS], then m2 [4][K]
+    __shared__ int row_s[4][64];
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double* tile = smem + (size_t)wib * 64 * SS_KS;
+    double* m2_all = smem + (size_t)4 * 64 * SS_KS;
+    double* m2w = m2_all + (size_t)wib * K;
+    for (int k = lane; k < K; k += 64) m2w[k] = 0.0;
+    for (int slice = blockIdx.x * 4 + wib; slice < n_slices_ld; slice += gridDim.x * 4) {
+        const long long p = (long long)slice * 64 + lane;
+        wave_lds_handoff();                                        // the previous slice's readers of row_s are done
+        row_s[wib][lane] = p < n ? (perm ? perm[p] : (int)p) : -1;
+        for (int k0 = 0; k0 < K; k0 += SS_KT) {
+            const int kc = K - k0 < SS_KT ? K - k0 : SS_KT;
+            wave_lds_handoff();
+            // element f = lane + 64 j of the wave's 64 x kc block: (spot, type) advance by (64 / kc, 64 % kc) with a carry; the
+            // lanes of one load cover whole row segments of kc doubles
+            const int total = 64 * kc;
+            const int ds = 64 / kc, dk = 64 - ds * kc;
+            int sp = lane / kc, k = lane - sp * kc;
+#pragma unroll 4
+            for (int f = lane; f < total; f += 64) {
+                const int row = row_s[wib][sp];
+                tile[sp * SS_KS + k] = row >= 0 ? V[(size_t)row * ldv + k0 + k] - mean[k0 + k] : 0.0;
+                sp += ds;
+                k += dk;
+                if (k >= kc) { k -= kc; ++sp; }
+            }
+            wave_lds_handoff();
+            for (int kk = 0; kk < kc; ++kk) Z[(size_t)(k0 + kk) * ld + p] = tile[lane * SS_KS + kk];
+            if (lane < kc) {                                       // lane owns type k0 + lane: its 64 squares in spot order
+                double s = 0.0;
+                for (int q = 0; q < 64; ++q) {
+                    const double z = tile[q * SS_KS + lane];
+                    s = fma(z, z, s);
+                }
+                m2w[k0 + lane] += s;
+            }
+        }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < K; k += 256)
+        m2_partials[(size_t)blockIdx.x * K + k] = ((m2_all[k] + m2_all[K + k]) + m2_all[2 * K + k]) + m2_all[3 * (size_t)K + k];
+}
+
+// lag[k][p] = sum over the ELL entries of position p of Z[k][entry] (pad entries read the zero column n); positions of the last
+// slice past n get 0.  deg_partials[block] = {sum deg, sum deg^2}.  nbr_mean (may be null): row perm[p] of an (n, K) row-major
+// matrix, lag / deg + mean (the mean of the neighbours' V), 0 without neighbours.
+template <int KC>
+__global__ __launch_bounds__(256) void ss_lag_kernel(const double* __restrict__ Z, long long ld, const int* __restrict__ ell_base,
+                                                     const int* __restrict__ slice_off, const int* __restrict__ deg,
+                                                     const int* __restrict__ perm, const double* __restrict__ mean, int n,
+                                                     int n_slices, int K, double* __restrict__ lag, double* __restrict__ nbr_mean,
+                                                     long long* __restrict__ deg_partials) {
+    __shared__ long long red[4][2];
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    long long sd = 0, sd2 = 0;
+    for (int slice = blockIdx.x * 4 + wib; slice < n_slices; slice += gridDim.x * 4) {
+        const long long p = (long long)slice * 64 + lane;
+        const bool active = p < n;
+        const int w0 = slice_off[slice];
+        const int w = slice_off[slice + 1] - w0;
+        const int* ell = ell_base + (size_t)w0 * 64 + lane;
+        const int dg = active ? deg[p] : 0;
+        sd += dg;
+        sd2 += (long long)dg * dg;
+        const size_t orow = active ? (perm ? (size_t)perm[p] : (size_t)p) : 0;
+        for (int k0 = 0; k0 < K; k0 += KC) {
+            const double* zp[KC];                                  // planes past K - 1 repeat the last one: loaded, not kept
+#pragma unroll
+            for (int kk = 0; kk < KC; ++kk) zp[kk] = Z + (size_t)(k0 + kk < K ? k0 + kk : K - 1) * ld;
+            double acc[KC];
+#pragma unroll
+            for (int kk = 0; kk < KC; ++kk) acc[kk] = 0.0;
+            int j_next = (w > 0 && active) ? ell[0] : n;
+            for (int m = 0; m < w; ++m) {
+                const int j = j_next;
+                if (m + 1 < w) j_next = active ? ell[(size_t)(m + 1) * 64] : n;
+#pragma unroll
+                for (int kk = 0; kk < KC; ++kk) acc[kk] += zp[kk][j];
+            }
+#pragma unroll
+            for (int kk = 0; kk < KC; ++kk)
+                if (k0 + kk < K) {
+                    lag[(size_t)(k0 + kk) * ld + p] = active ? acc[kk] : 0.0;
+                    if (nbr_mean && active)
+                        nbr_mean[orow * K + k0 + kk] = dg > 0 ? acc[kk] / (double)dg + mean[k0 + kk] : 0.0;
+                }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sd += __shfl_xor(sd, off, 64);
+        sd2 += __shfl_xor(sd2, off, 64);
+    }
+    if (lane == 0) { red[wib][0] = sd; red[wib][1] = sd2; }
+    __syncthreads();
+    if (threadIdx.x < 2)
+        deg_partials[(size_t)blockIdx.x * 2 + threadIdx.x] =
+            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+// partials[blockIdx.x][a][b] = sum over the block's 64-position chunks of Z[a][p] * lag[b][p], for the (a, b) of pair-space tile
+// blockIdx.y = tile_a * ntb + tile_b.  Thread (ta, tb) of 16 x 16 owns a in {ta, ta + 16}, b in {tb, tb + 16} of the tile: per
+// position two LDS reads of each operand (the ta reads broadcast) feed four FMAs; the row stride of 65 doubles puts the 16 lag
+// rows a half-wave reads on 16 different bank pairs.
+__global__ __launch_bounds__(256) void ss_cross_kernel(const double* __restrict__ Z, const double* __restrict__ lag, long long ld,
+                                                       int n_chunks, int K, int ntb, double* __restrict__ partials) {
+    __shared__ double zs[SS_CT][SS_CP + 1], ls[SS_CT][SS_CP + 1];
+    const int a_base = (blockIdx.y / ntb) * SS_CT, b_base = (blockIdx.y % ntb) * SS_CT;
+    const int ta = threadIdx.x >> 4, tb = threadIdx.x & 15;
+    const int sr = threadIdx.x >> 6, sc = threadIdx.x & 63;
+    double c00 = 0.0, c01 = 0.0, c10 = 0.0, c11 = 0.0;
+    for (int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const size_t p = (size_t)chunk * SS_CP + sc;
+#pragma unroll
+        for (int i = 0; i < SS_CT / 4; ++i) {
+            const int r = sr + 4 * i;
+            zs[r][sc] = a_base + r < K ? Z[(size_t)(a_base + r) * ld + p] : 0.0;
+            ls[r][sc] = b_base + r < K ? lag[(size_t)(b_base + r) * ld + p] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int q = 0; q < SS_CP; ++q) {
+            const double z0 = zs[ta][q], z1 = zs[ta + 16][q];
+            const double l0 = ls[tb][q], l1 = ls[tb + 16][q];
+            c00 = fma(z0, l0, c00);
+            c01 = fma(z0, l1, c01);
+            c10 = fma(z1, l0, c10);
+            c11 = fma(z1, l1, c11);
+        }
+        __syncthreads();
+    }
+    double* out = partials + (size_t)blockIdx.x * K * K;
+    const int a0 = a_base + ta, a1 = a0 + 16, b0 = b_base + tb, b1 = b0 + 16;
+    if (a0 < K && b0 < K) out[(size_t)a0 * K + b0] = c00;
+    if (a0 < K && b1 < K) out[(size_t)a0 * K + b1] = c01;
+    if (a1 < K && b0 < K) out[(size_t)a1 * K + b0] = c10;
+    if (a1 < K && b1 < K) out[(size_t)a1 * K + b1] = c11;
+}
+
+SpatialStatsPlan spatial_stats_plan(long long n, int K) {
+    SpatialStatsPlan s;
+    s.ld = round_up(n + 1, 64);
+    s.n_slices = ceil_div(n, 64);
+    s.colsum_blocks = (int)std::min<long long>(SS_CAP_BLOCKS, std::max<long long>(1, ceil_div(n, 1024)));
+    s.rows_per_block = ceil_div(n, s.colsum_blocks);
+    s.colsum_blocks = ceil_div(n, s.rows_per_block);
+    s.centre_blocks = (int)std::min<long long>(SS_CAP_BLOCKS, ceil_div(s.ld / 64, 4));
+    s.lag_blocks = std::min(SS_CAP_BLOCKS, ceil_div(s.n_slices, 4));
+    s.pair_tiles_1d = ceil_div(K, SS_CT);
+    const int tiles = s.pair_tiles_1d * s.pair_tiles_1d;
+    // the product runs over the positions the lag pass wrote: n_slices chunks of 64 (Z is 0 from n on)
+    s.cross_blocks = (int)std::max<long long>(1, std::min<long long>(s.n_slices, SS_CAP_BLOCKS / tiles));
+    const size_t KK = (size_t)K * K;
+    s.partials_doubles = std::max({(size_t)s.colsum_blocks * K, (size_t)s.centre_blocks * K, (size_t)s.cross_blocks * KK,
+                                   (size_t)s.lag_blocks * 2});
+    s.scratch_doubles = 2 * (size_t)K * s.ld + s.partials_doubles;
+    s.out_doubles = 2 * (size_t)K + KK + 2;
+    return s;
+}
+
+template <int KC>
+static void launch_lag(const SpatialStatsPlan& s, const double* Z, const int* ell, const int* slice_off, const int* deg,
+                       const int* perm, const double* mean, int n, int K, double* lag, double* nbr_mean, long long* deg_part,
+                       hipStream_t st) {
+    hipLaunchKernelGGL(ss_lag_kernel<KC>, dim3(s.lag_blocks), dim3(256), 0, st, Z, s.ld, ell, slice_off, deg, perm, mean, n,
+                       s.n_slices, K, lag, nbr_mean, deg_part);
+}
+
+int launch_spatial_stats(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* ell,
+                         const int* slice_off, const int* deg, const int* perm, double* scratch, double* out, double* nbr_mean,
+                         hipStream_t st) {
+    if (n <= 0) return 0;
+    double* Z = scratch;
+    double* lag = Z + (size_t)K * s.ld;
+    double* part = lag + (size_t)K * s.ld;
+    double* mean = out;
+    double* m2 = out + K;
+    double* C = out + 2 * (size_t)K;
+    long long* counts = reinterpret_cast<long long*>(C + (size_t)K * K);
+    const size_t KK = (size_t)K * K;
+
+    hipLaunchKernelGGL(ss_colsum_kernel, dim3(s.colsum_blocks), dim3(256), 0, st, V, ldv, n, K, s.rows_per_block, part);
+    FDX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ss_reduce_kernel<double>, dim3(ceil_div(K, 256)), dim3(256), 0, st, part, s.colsum_blocks, (long long)K,
+                       (double)n, mean);
+    FDX_CHECK_LAUNCH();
+
+    const size_t lds = ((size_t)4 * 64 * SS_KS + (size_t)4 * K) * sizeof(double);
+    if (lds > 64 * 1024)
+        FDX_HIP(hipFuncSetAttribute((const void*)ss_centre_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(ss_centre_kernel, dim3(s.centre_blocks), dim3(256), lds, st, V, ldv, mean, perm, n, (int)(s.ld / 64), K, Z,
+                       s.ld, part);
+    FDX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ss_reduce_kernel<double>, dim3(ceil_div(K, 256)), dim3(256), 0, st, part, s.centre_blocks, (long long)K, 1.0,
+                       m2);
+    FDX_CHECK_LAUNCH();
+
+    long long* deg_part = reinterpret_cast<long long*>(part);
+    if (K <= 8) launch_lag<8>(s, Z, ell, slice_off, deg, perm, mean, n, K, lag, nbr_mean, deg_part, st);
+    else if (K <= 16) launch_lag<16>(s, Z, ell, slice_off, deg, perm, mean, n, K, lag, nbr_mean, deg_part, st);
+    else launch_lag<32>(s, Z, ell, slice_off, deg, perm, mean, n, K, lag, nbr_mean, deg_part, st);
+    FDX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ss_reduce_kernel<long long>, dim3(1), dim3(256), 0, st, deg_part, s.lag_blocks, 2LL, 1LL, counts);
+    FDX_CHECK_LAUNCH();
+
+    hipLaunchKernelGGL(ss_cross_kernel, dim3(s.cross_blocks, s.pair_tiles_1d * s.pair_tiles_1d), dim3(256), 0, st, Z, lag, s.ld,
+                       s.n_slices, K, s.pair_tiles_1d, part);
+    FDX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ss_reduce_kernel<double>, dim3(ceil_div((long long)KK, 256)), dim3(256), 0, st, part, s.cross_blocks,
+                       (long long)KK, 1.0, C);
+    FDX_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // namespace fdx

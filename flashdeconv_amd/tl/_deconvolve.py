@@ -5,11 +5,14 @@ forwarding the same keyword arguments to the MI355X ``FlashDeconv``."""
 def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512, lambda_spatial="auto", rho_sparsity=0.01,
                n_hvg=2000, n_markers_per_type=50, spatial_method="knn", k_neighbors=6, radius=None, preprocess="log_cpm",
                layer_st=None, layer_ref=None, spatial_key="spatial", key_added="flashdeconv", random_state=0, copy=False,
-               spot_diagnostics=False):
+               spot_diagnostics=False, spatial_stats=False):
     """Writes ``.obsm[key_added]`` (proportions DataFrame), ``.obs[key_added + '_dominant']`` and
     ``.uns[key_added + '_params']``; returns the modified copy when ``copy=True``, else ``None``.  ``spot_diagnostics=True``
     (additive) also writes ``.obs[key_added + '_residual']`` (relative sketch residual per spot) and
-    ``.obs[key_added + '_roughness']`` (disagreement with the neighbours' abundances, ``neighbor_sq``)."""
+    ``.obs[key_added + '_roughness']`` (disagreement with the neighbours' abundances, ``neighbor_sq``).  ``spatial_stats=True``
+    (additive) also writes ``.uns[key_added + '_moran']`` (DataFrame indexed by cell type: Moran's ``I`` of its proportions over
+    the fit's graph and the ``z_score``) and ``.uns[key_added + '_colocalization']`` (cell type x cell type bivariate Moran
+    matrix)."""
     from ..core.deconv import FlashDeconv
     from ..io import prepare_data, result_to_anndata
 
@@ -44,4 +47,11 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
     }
     if spot_diagnostics:
         adata.uns[f"{key_added}_params"]["spot_diagnostics"] = True
+    if spatial_stats:
+        import pandas as pd
+        stats = model.get_spatial_autocorrelation()
+        types = [str(t) for t in names]
+        adata.uns[f"{key_added}_moran"] = pd.DataFrame({"I": stats["morans_i"], "z_score": stats["z_score"]}, index=types)
+        adata.uns[f"{key_added}_colocalization"] = pd.DataFrame(stats["cross"], index=types, columns=types)
+        adata.uns[f"{key_added}_params"]["spatial_stats"] = True
     return adata if copy else None

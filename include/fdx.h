@@ -552,6 +552,16 @@ int fdx_objective_partials_dev(const fdx_graph* g, const double* beta_dev, int64
 int fdx_spot_diagnostics_dev(const fdx_graph* g, const double* beta_dev, int64_t ld, const double* H_dev, int64_t ldh,
                              const double* XtX_dev, int32_t ldg, int32_t K, const double* row_sq_dev, double* out_dev,
                              void* stream);
+/* Spatial autocorrelation of per-spot values over a whole graph (additive, not in the reference).  V_dev: (g->n, K) row-major with
+ * row stride ldv >= K, rows in the caller's spot order.  With A the graph's symmetric binary adjacency, to HOST memory:
+ *   mean_out[a] = (1/n) sum_i V_ia          m2_out[a] = sum_i Z_ia^2, Z = V - mean          C_out (K, K) row-major = Z' (A Z)
+ *   counts_out  = { n, W = sum_i deg_i, sum_i deg_i^2 }
+ * from which Moran's I is (n / W) C_aa / m2_a and the bivariate Moran matrix (n / W) C_ab / sqrt(m2_a m2_b).  neighbor_mean_dev
+ * (may be NULL): (n, K) row-major DEVICE matrix in the caller's spot order, (sum_j A_ij V_ja) / deg_i, 0 where deg_i = 0.  float64
+ * throughout, no floating-point atomics (two calls return the same bits), one host synchronisation.  A shard's local graph is
+ * refused. */
+int fdx_spatial_autocorr_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, int32_t K, double* mean_out, double* m2_out,
+                             double* C_out, int64_t* counts_out, double* neighbor_mean_dev, void* stream);
 /* beta (K, ld) type-major -> beta_out / prop_out (n, K) row-major in solver order of the own spots. */
 int fdx_normalize_dev(const double* beta_dev, int64_t ld, int64_t n, int32_t K, double* beta_out_dev, double* prop_out_dev,
                       void* stream);
