@@ -146,6 +146,11 @@ SIGNATURES = {
     "fdx_spot_diagnostics_dev": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i32, c_i32, c_void_p, c_void_p,
                                          c_void_p]),
     "fdx_spatial_autocorr_dev": (c_int, [c_void_p, c_void_p, c_i64, c_i32, p_double, p_double, p_double, p_i64, c_void_p, c_void_p]),
+    "fdx_kmeans_assign_dev": (c_int, [c_void_p, c_i64, c_i64, c_i32, c_void_p, c_i32, c_void_p, c_void_p, p_i64, p_double, c_void_p]),
+    "fdx_label_sums_dev": (c_int, [c_void_p, c_i64, c_i64, c_i32, c_void_p, c_i32, p_double, p_i64, c_void_p]),
+    "fdx_kmeans_seed_dist_dev": (c_int, [c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p, p_double, p_i64, p_i32, c_void_p]),
+    "fdx_kmeans_dev": (c_int, [c_void_p, c_i64, c_i64, c_i32, c_i32, c_i32, c_void_p, c_void_p, p_i64, p_double, p_i32, p_i32,
+                               c_void_p]),
     "fdx_normalize_dev": (c_int, [c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_void_p]),
     "fdx_gene_moments_dev": (c_int, [c_void_p, c_i32, c_i64, c_i32, c_i64, p_double, p_double, c_void_p]),
     "fdx_gather_columns_dev": (c_int, [c_void_p, c_i32, c_i64, c_i32, c_i64, p_i32, c_i32, c_void_p, c_void_p]),

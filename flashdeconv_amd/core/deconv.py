@@ -647,6 +647,19 @@ class FlashDeconv:
         from ..utils.spatial_stats import spatial_autocorrelation
         return spatial_autocorrelation(self.proportions_ if what == "proportions" else self.beta_, self, neighbor_mean=neighbor_mean)
 
+    def get_spatial_niches(self, n_niches, what="proportions", features="both", **kw):
+        """Groups the spots into ``n_niches`` spatial niches (tissue domains) by k-means of their composition, of their
+        neighbourhood's composition over the graph the fit used, or of both (additive, not in the reference):
+        ``utils.niches.spatial_niches`` on ``proportions_`` (``what="proportions"``) or ``beta_`` (``what="abundances"``) and the
+        model's device graph; further keywords (``neighbor_weight``, ``init``, ``max_iter``, ``random_state``) go there.  Works for
+        both ``output`` kinds of ``fit``."""
+        self._require_fitted()
+        if what not in ("proportions", "abundances"):
+            raise ValueError(f"Unknown what: {what}. Choose from 'proportions', 'abundances'.")
+        from ..utils.niches import spatial_niches
+        return spatial_niches(self.proportions_ if what == "proportions" else self.beta_, n_niches, graph=self, features=features,
+                              **kw)
+
     def get_dominant_cell_type(self):
         self._require_fitted()
         if hasattr(self.proportions_, "argmax") and not isinstance(self.proportions_, np.ndarray):

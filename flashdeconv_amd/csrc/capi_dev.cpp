@@ -395,6 +395,122 @@ int fdx_spatial_autocorr_dev(const fdx_graph* g, const double* V_dev, int64_t ld
     return 0;
 }
 
+}  // extern "C"
+
+// the shape checks the k-means entries share; `who` names the entry in the message
+static int kmeans_check_shape(const char* who, int64_t ldf, int64_t n, int32_t D, int32_t C, bool centres_are_rows) {
+    const std::string w(who);
+    FDX_REQUIRE(D >= 1, w + ": D must be positive");
+    FDX_REQUIRE(ldf >= D, w + ": ldf must be at least D");
+    FDX_REQUIRE(C >= 1 && C <= 64, w + ": C must be between 1 and 64");
+    FDX_REQUIRE(n >= 0 && n < (1LL << 31) - 128, w + ": too many rows");
+    if (centres_are_rows) FDX_REQUIRE(C <= n, w + ": C must not exceed n");
+    return 0;
+}
+
+extern "C" {
+
+int fdx_kmeans_assign_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, const double* centres_dev, int32_t C,
+                          int32_t* labels_dev, double* min_d2_dev, int64_t* changed_out, double* inertia_out, void* stream) {
+    FDX_REQUIRE(F_dev && centres_dev && labels_dev && changed_out && inertia_out, "fdx_kmeans_assign_dev: null argument");
+    FDX_TRY(kmeans_check_shape("fdx_kmeans_assign_dev", ldf, n, D, C, true));
+    hipStream_t st = (hipStream_t)stream;
+    PoolStream pool_stream(st);
+    const KmeansPlan plan = kmeans_plan(n, D, C);
+    DevBuf part, out;
+    FDX_TRY(part.alloc(plan.dist_part_bytes));
+    FDX_TRY(out.alloc(16));
+    FDX_TRY(launch_kmeans_assign(plan, F_dev, ldf, (int)n, D, centres_dev, C, labels_dev, min_d2_dev, part.p, out.as<long long>(),
+                                 out.as<double>() + 1, st));
+    unsigned char host[16];
+    FDX_TRY(copy_d2h(host, out.p, 16, st));            // the call's one host synchronisation
+    std::memcpy(changed_out, host, 8);
+    std::memcpy(inertia_out, host + 8, 8);
+    return 0;
+}
+
+int fdx_label_sums_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, const int32_t* labels_dev, int32_t C,
+                       double* sums_out, int64_t* counts_out, void* stream) {
+    FDX_REQUIRE(sums_out && counts_out && (n == 0 || (F_dev && labels_dev)), "fdx_label_sums_dev: null argument");
+    FDX_TRY(kmeans_check_shape("fdx_label_sums_dev", ldf, n, D, C, false));
+    const size_t CD = (size_t)C * D;
+    std::fill(sums_out, sums_out + CD, 0.0);
+    std::fill(counts_out, counts_out + C, (int64_t)0);
+    if (n == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    PoolStream pool_stream(st);
+    const KmeansPlan plan = kmeans_plan(n, D, C);
+    DevBuf part, out;
+    FDX_TRY(part.alloc(plan.sums_part_bytes));
+    FDX_TRY(out.alloc((CD + C) * 8));
+    FDX_TRY(launch_label_sums(plan, F_dev, ldf, labels_dev, (int)n, D, C, part.p, out.as<double>(),
+                              reinterpret_cast<long long*>(out.as<double>() + CD), nullptr, st));
+    std::vector<double> host(CD + C);
+    FDX_TRY(copy_d2h(host.data(), out.p, (CD + C) * 8, st));
+    std::copy(host.begin(), host.begin() + CD, sums_out);
+    std::memcpy(counts_out, host.data() + CD, (size_t)C * 8);
+    return 0;
+}
+
+int fdx_kmeans_seed_dist_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, const double* centre_dev, double* d2_dev,
+                             double* block_sums_out, int64_t* block_rows_out, int32_t* n_blocks_out, void* stream) {
+    FDX_REQUIRE(F_dev && centre_dev && d2_dev && block_sums_out && block_rows_out && n_blocks_out,
+                "fdx_kmeans_seed_dist_dev: null argument");
+    FDX_TRY(kmeans_check_shape("fdx_kmeans_seed_dist_dev", ldf, n, D, 1, true));
+    hipStream_t st = (hipStream_t)stream;
+    PoolStream pool_stream(st);
+    const KmeansPlan plan = kmeans_plan(n, D, 1);
+    DevBuf part, out;
+    FDX_TRY(part.alloc(plan.dist_part_bytes));
+    FDX_TRY(out.alloc((size_t)plan.seed_blocks * 8));
+    FDX_TRY(launch_kmeans_seed_dist(plan, F_dev, ldf, (int)n, D, centre_dev, d2_dev, part.p, out.as<double>(), st));
+    FDX_TRY(copy_d2h(block_sums_out, out.p, (size_t)plan.seed_blocks * 8, st));
+    *block_rows_out = plan.seed_rows;
+    *n_blocks_out = plan.seed_blocks;
+    return 0;
+}
+
+int fdx_kmeans_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, int32_t C, int32_t max_iter, double* centres_dev,
+                   int32_t* labels_dev, int64_t* counts_out, double* inertia_out, int32_t* n_iter_out, int32_t* converged_out,
+                   void* stream) {
+    FDX_REQUIRE(F_dev && centres_dev && labels_dev && counts_out && inertia_out && n_iter_out && converged_out,
+                "fdx_kmeans_dev: null argument");
+    FDX_TRY(kmeans_check_shape("fdx_kmeans_dev", ldf, n, D, C, true));
+    FDX_REQUIRE(max_iter >= 1, "fdx_kmeans_dev: max_iter must be positive");
+    hipStream_t st = (hipStream_t)stream;
+    PoolStream pool_stream(st);
+    const KmeansPlan plan = kmeans_plan(n, D, C);
+    const size_t CD = (size_t)C * D;
+    DevBuf dist_part, sums_part, out;
+    FDX_TRY(dist_part.alloc(plan.dist_part_bytes));
+    FDX_TRY(sums_part.alloc(plan.sums_part_bytes));
+    FDX_TRY(out.alloc(16 + (CD + C) * 8));               // [changed | inertia | sums C*D | counts C]
+    long long* changed_d = out.as<long long>();
+    double* inertia_d = out.as<double>() + 1;
+    double* sums_d = out.as<double>() + 2;
+    long long* counts_d = reinterpret_cast<long long*>(sums_d + CD);
+    FDX_HIP(hipMemsetAsync(labels_dev, 0xFF, (size_t)n * sizeof(int32_t), st));      // every label -1
+    int it = 0, converged = 0;
+    unsigned char host[16];
+    for (;;) {
+        ++it;
+        FDX_TRY(launch_kmeans_assign(plan, F_dev, ldf, (int)n, D, centres_dev, C, labels_dev, nullptr, dist_part.p, changed_d,
+                                     inertia_d, st));
+        FDX_TRY(copy_d2h(host, out.p, 16, st));          // 16 bytes per iteration: the loop's only host synchronisation
+        int64_t changed;
+        std::memcpy(&changed, host, 8);
+        if (changed == 0) { converged = 1; break; }
+        if (it == max_iter) break;
+        FDX_TRY(launch_label_sums(plan, F_dev, ldf, labels_dev, (int)n, D, C, sums_part.p, sums_d, counts_d, centres_dev, st));
+    }
+    FDX_TRY(launch_label_sums(plan, nullptr, ldf, labels_dev, (int)n, D, C, sums_part.p, sums_d, counts_d, nullptr, st));
+    FDX_TRY(copy_d2h(counts_out, counts_d, (size_t)C * 8, st));
+    std::memcpy(inertia_out, host + 8, 8);
+    *n_iter_out = it;
+    *converged_out = converged;
+    return 0;
+}
+
 int fdx_normalize_dev(const double* beta_dev, int64_t ld, int64_t n, int32_t K, double* beta_out_dev, double* prop_out_dev,
                       void* stream) {
     FDX_REQUIRE(beta_dev && n >= 0 && K > 0, "fdx_normalize_dev: bad arguments");

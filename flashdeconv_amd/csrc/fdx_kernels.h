@@ -145,6 +145,29 @@ int launch_spatial_stats(const SpatialStatsPlan& s, const double* V, long long l
                          const int* slice_off, const int* deg, const int* perm, double* scratch, double* out, double* nbr_mean,
                          hipStream_t st);
 
+// ---- niche_kernels.cpp
+// Grids and scratch of the k-means kernels on n rows, D columns and C centres (functions of the shapes only).
+struct KmeansPlan {
+    int dist_blocks;             // workgroups of the assign / seed-distance kernel: 256 rows each
+    int seed_per, seed_blocks;   // seed distance: workgroups per block of seed_rows rows, and how many such blocks (<= 1024)
+    long long seed_rows;
+    int sums_blocks, rows_per_block;   // label sums
+    size_t dist_part_bytes;      // scratch of an assign / seed-distance launch
+    size_t sums_part_bytes;      // scratch of a label-sums launch
+};
+KmeansPlan kmeans_plan(long long n, int D, int C);
+// labels[i] = arg-min over c of d2(i, c) (smallest c), min_d2 (may be null); to the device: changed_out[0] = rows whose label
+// differs from the previous content of labels, inertia_out[0] = sum_i d2(i, label_i).
+int launch_kmeans_assign(const KmeansPlan& p, const double* F, long long ldf, int n, int D, const double* M, int C, int* labels,
+                         double* min_d2, void* dist_part, long long* changed_out, double* inertia_out, hipStream_t st);
+// d2[i] = min(d2[i], d2(i, m)); block_sums[b] (device, p.seed_blocks of them) = sum of d2 over rows [b * seed_rows, ...).
+int launch_kmeans_seed_dist(const KmeansPlan& p, const double* F, long long ldf, int n, int D, const double* m, double* d2,
+                            void* dist_part, double* block_sums, hipStream_t st);
+// sums (C, D) and counts (C) per label (device); F null: counts only (sums untouched).  centres (may be null): rows with a
+// positive count become sums / counts.  The plan's C and D must be the ones passed here.
+int launch_label_sums(const KmeansPlan& p, const double* F, long long ldf, const int* labels, int n, int D, int C, void* sums_part,
+                      double* sums, long long* counts, double* centres, hipStream_t st);
+
 // ---- bcd_kernels.cpp
 int launch_bcd_sweep(const BcdSweepArgs& a, double* generic_scratch, size_t scratch_ld, hipStream_t st);
 // More than 64 cell types, no register-resident instantiation: the LDS-resident sweep (bcd_kernels.cpp) while K x 64 doubles fit;

@@ -5,14 +5,16 @@ forwarding the same keyword arguments to the MI355X ``FlashDeconv``."""
 def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512, lambda_spatial="auto", rho_sparsity=0.01,
                n_hvg=2000, n_markers_per_type=50, spatial_method="knn", k_neighbors=6, radius=None, preprocess="log_cpm",
                layer_st=None, layer_ref=None, spatial_key="spatial", key_added="flashdeconv", random_state=0, copy=False,
-               spot_diagnostics=False, spatial_stats=False):
+               spot_diagnostics=False, spatial_stats=False, n_niches=None):
     """Writes ``.obsm[key_added]`` (proportions DataFrame), ``.obs[key_added + '_dominant']`` and
     ``.uns[key_added + '_params']``; returns the modified copy when ``copy=True``, else ``None``.  ``spot_diagnostics=True``
     (additive) also writes ``.obs[key_added + '_residual']`` (relative sketch residual per spot) and
     ``.obs[key_added + '_roughness']`` (disagreement with the neighbours' abundances, ``neighbor_sq``).  ``spatial_stats=True``
     (additive) also writes ``.uns[key_added + '_moran']`` (DataFrame indexed by cell type: Moran's ``I`` of its proportions over
     the fit's graph and the ``z_score``) and ``.uns[key_added + '_colocalization']`` (cell type x cell type bivariate Moran
-    matrix)."""
+    matrix).  ``n_niches=<int>`` (additive) also writes ``.obs[key_added + '_niche']`` (Categorical of niche indices: k-means of
+    each spot's proportions beside its neighbours' mean proportions, ``FlashDeconv.get_spatial_niches``) and
+    ``.uns[key_added + '_niche_composition']`` (DataFrame, niche x cell type: the mean proportions of each niche's spots)."""
     from ..core.deconv import FlashDeconv
     from ..io import prepare_data, result_to_anndata
 
@@ -54,4 +56,12 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
         adata.uns[f"{key_added}_moran"] = pd.DataFrame({"I": stats["morans_i"], "z_score": stats["z_score"]}, index=types)
         adata.uns[f"{key_added}_colocalization"] = pd.DataFrame(stats["cross"], index=types, columns=types)
         adata.uns[f"{key_added}_params"]["spatial_stats"] = True
+    if n_niches is not None:
+        import pandas as pd
+        niches = model.get_spatial_niches(n_niches)
+        index = list(range(int(n_niches)))
+        adata.obs[f"{key_added}_niche"] = pd.Categorical(niches["labels"], categories=index)
+        adata.uns[f"{key_added}_niche_composition"] = pd.DataFrame(niches["composition"], index=index,
+                                                                   columns=[str(t) for t in names])
+        adata.uns[f"{key_added}_params"]["n_niches"] = int(n_niches)
     return adata if copy else None

@@ -562,6 +562,40 @@ int fdx_spot_diagnostics_dev(const fdx_graph* g, const double* beta_dev, int64_t
  * refused. */
 int fdx_spatial_autocorr_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, int32_t K, double* mean_out, double* m2_out,
                              double* C_out, int64_t* counts_out, double* neighbor_mean_dev, void* stream);
+/* k-means of per-spot feature rows (spatial niches; additive, not in the reference).  F_dev: (n, D) row-major DEVICE matrix with
+ * row stride ldf >= D (columns D .. ldf - 1 are never read); centres: (C, D) row-major, contiguous, 1 <= C <= 64.  Everywhere
+ * d2(i, c) = sum_k (F_ik - M_ck)^2 with the difference formed first, accumulated by fma in ascending k.  float64 throughout, no
+ * floating-point atomics, grids and summation orders are functions of the shapes only: two calls return the same bits.  Refused
+ * with a message each: null pointers, D < 1, ldf < D, C outside 1 .. 64, n >= 2^31 - 128, and (where the centres are rows of F)
+ * C > n.
+ *
+ * fdx_kmeans_assign_dev: labels_dev[i] (n int32, DEVICE, in/out) = the smallest c attaining min_c d2(i, c); min_d2_dev (n, DEVICE,
+ *   may be NULL) that minimum; to HOST memory *changed_out = the rows whose label differs from the buffer's previous content
+ *   (exact) and *inertia_out = sum_i d2(i, label_i).  One host synchronisation. */
+int fdx_kmeans_assign_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, const double* centres_dev, int32_t C,
+                          int32_t* labels_dev, double* min_d2_dev, int64_t* changed_out, double* inertia_out, void* stream);
+/* To HOST memory: sums_out (C, D) row-major, sums_out[c][k] = sum of F_ik over the rows with labels_dev[i] == c, and counts_out[c]
+ * how many there are; a label that never occurs gives zero sums and count 0, labels outside 0 .. C - 1 are skipped.  Any n >= 0;
+ * F need not be the matrix the labels came from (a niche's mean composition after clustering on other features). */
+int fdx_label_sums_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, const int32_t* labels_dev, int32_t C,
+                       double* sums_out, int64_t* counts_out, void* stream);
+/* One step of k-means++ seeding: d2_dev[i] (n, DEVICE, in/out; +inf before the first centre) = min(d2_dev[i], d2(i, m)) for the
+ * new centre m = centre_dev (D doubles on the DEVICE: a row of F, say).  To HOST memory: *block_rows_out = R (a multiple of 256
+ * and a function of n only), *n_blocks_out = ceil(n / R) <= 1024 and block_sums_out[b] (room for 1024) = the sum of d2 over rows
+ * [b R, (b + 1) R). */
+int fdx_kmeans_seed_dist_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, const double* centre_dev, double* d2_dev,
+                             double* block_sums_out, int64_t* block_rows_out, int32_t* n_blocks_out, void* stream);
+/* Lloyd's loop on the caller's stream.  centres_dev (C, D) DEVICE, in: the initial centres, out: the final ones; labels_dev (n
+ * int32, DEVICE, out).
+ *     labels = -1
+ *     for it = 1 .. max_iter:  labels, changed, inertia = assign(F, centres);  changed == 0: converged, stop;  it == max_iter: stop;
+ *                              sums, counts = label_sums(F, labels);  centres[c] = sums[c] / counts[c] where counts[c] > 0
+ * (an empty niche keeps its centre).  The labels returned are the arg-min of the centres returned; on convergence the centres are
+ * also the means of their members.  To HOST memory: counts_out (C) of the labels returned, *inertia_out of the last assign pass,
+ * *n_iter_out = assign passes made, *converged_out 1 / 0.  16 bytes are read back per iteration.  max_iter < 1 is refused. */
+int fdx_kmeans_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, int32_t C, int32_t max_iter, double* centres_dev,
+                   int32_t* labels_dev, int64_t* counts_out, double* inertia_out, int32_t* n_iter_out, int32_t* converged_out,
+                   void* stream);
 /* beta (K, ld) type-major -> beta_out / prop_out (n, K) row-major in solver order of the own spots. */
 int fdx_normalize_dev(const double* beta_dev, int64_t ld, int64_t n, int32_t K, double* beta_out_dev, double* prop_out_dev,
                       void* stream);
