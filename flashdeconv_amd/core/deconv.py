@@ -636,16 +636,28 @@ class FlashDeconv:
             return torch.sqrt(res)
         return torch.sqrt(torch.where(sq > 0, res / torch.where(sq > 0, sq, torch.ones_like(sq)), torch.zeros_like(res)))
 
-    def get_spatial_autocorrelation(self, what="proportions", neighbor_mean=False):
+    def get_spatial_autocorrelation(self, what="proportions", neighbor_mean=False, n_permutations=0, random_state=None):
         """Moran's I per cell type, the K x K bivariate Moran matrix (neighbourhood co-localisation) and, with
         ``neighbor_mean=True``, each spot's neighbour-averaged composition, over the graph the fit used (additive, not in the
         reference): ``utils.spatial_stats.spatial_autocorrelation`` on ``proportions_`` (``what="proportions"``) or ``beta_``
-        (``what="abundances"``) and the model's device graph.  Works for both ``output`` kinds of ``fit``."""
+        (``what="abundances"``) and the model's device graph.  Works for both ``output`` kinds of ``fit``.
+
+        ``n_permutations=R`` > 0 adds the permutation test of ``utils.spatial_stats.spatial_permutation_test`` (p values and
+        simulated z scores of I and of every pair, the randomisation variance), seeded by ``random_state`` (None: the model's)."""
         self._require_fitted()
         if what not in ("proportions", "abundances"):
             raise ValueError(f"Unknown what: {what}. Choose from 'proportions', 'abundances'.")
-        from ..utils.spatial_stats import spatial_autocorrelation
-        return spatial_autocorrelation(self.proportions_ if what == "proportions" else self.beta_, self, neighbor_mean=neighbor_mean)
+        from ..utils.spatial_stats import spatial_autocorrelation, spatial_permutation_test, spatial_sums
+        values = self.proportions_ if what == "proportions" else self.beta_
+        if isinstance(n_permutations, (bool, np.bool_)) or not isinstance(n_permutations, (int, np.integer)) or n_permutations < 0:
+            raise ValueError(f"n_permutations must be an int >= 0, got {n_permutations!r}")
+        if n_permutations == 0:
+            return spatial_autocorrelation(values, self, neighbor_mean=neighbor_mean)
+        out = spatial_permutation_test(values, self, n_permutations=n_permutations,
+                                       random_state=self.random_state if random_state is None else random_state)
+        if neighbor_mean:
+            out["neighbor_mean"] = spatial_sums(values, self, neighbor_mean=True)["neighbor_mean"]
+        return out
 
     def get_spatial_niches(self, n_niches, what="proportions", features="both", **kw):
         """Groups the spots into ``n_niches`` spatial niches (tissue domains) by k-means of their composition, of their

@@ -395,6 +395,70 @@ int fdx_spatial_autocorr_dev(const fdx_graph* g, const double* V_dev, int64_t ld
     return 0;
 }
 
+int fdx_spatial_perm_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, int32_t K, uint64_t seed, int64_t first_perm,
+                         int64_t n_perm, int32_t max_batch, double* null_dev, double* mean_out, double* m2_out, double* C_out,
+                         int64_t* counts_out, double* m4_out, int64_t* count_ge_out, int64_t* count_le_out, double* sum_d_out,
+                         double* sumsq_d_out, int32_t* batch_out, void* stream) {
+    FDX_TRY(fdx::graph_meta_sync(g));
+    FDX_REQUIRE(g && V_dev && mean_out && m2_out && C_out && counts_out && m4_out && count_ge_out && count_le_out && sum_d_out &&
+                    sumsq_d_out,
+                "fdx_spatial_perm_dev: null argument");
+    FDX_REQUIRE(K >= 1 && ldv >= K, "fdx_spatial_perm_dev: K must be positive and ldv at least K");
+    FDX_REQUIRE(first_perm >= 0 && n_perm >= 0 && max_batch >= 0,
+                "fdx_spatial_perm_dev: first_perm, n_perm and max_batch must not be negative");
+    FDX_REQUIRE(!g->shard_pending && g->n_total == g->n && g->world_n == 0,
+                "fdx_spatial_perm_dev: a shard's local graph is refused (whole graphs on one GPU only)");
+    FDX_REQUIRE(g->n < (1LL << 31) - 128, "fdx_spatial_perm_dev: too many spots");
+    hipStream_t st = (hipStream_t)stream;
+    PoolStream pool_stream(st);
+    const size_t KK = (size_t)K * K;
+    counts_out[0] = g->n;
+    counts_out[1] = counts_out[2] = 0;
+    std::fill(count_ge_out, count_ge_out + KK, (int64_t)0);
+    std::fill(count_le_out, count_le_out + KK, (int64_t)0);
+    std::fill(sum_d_out, sum_d_out + KK, 0.0);
+    std::fill(sumsq_d_out, sumsq_d_out + KK, 0.0);
+    if (batch_out) *batch_out = 0;
+    if (g->n == 0) {                                    // no spots: no mean, and nothing to permute
+        std::fill(mean_out, mean_out + K, std::nan(""));
+        std::fill(m2_out, m2_out + K, 0.0);
+        std::fill(m4_out, m4_out + K, 0.0);
+        std::fill(C_out, C_out + KK, 0.0);
+        if (null_dev && n_perm > 0) FDX_HIP(hipMemsetAsync(null_dev, 0, (size_t)n_perm * KK * sizeof(double), st));
+        for (size_t i = 0; i < KK; ++i) count_ge_out[i] = count_le_out[i] = n_perm;      // every C_r equals C_obs = 0
+        return 0;
+    }
+    const SpatialPermPlan plan = spatial_perm_plan(g->n, K, n_perm, max_batch, null_dev == nullptr);
+    if (batch_out) *batch_out = n_perm > 0 ? plan.batch : 0;
+    DevBuf scratch, out;
+    FDX_TRY(scratch.alloc(plan.scratch_doubles * sizeof(double)));
+    FDX_TRY(out.alloc(plan.out_doubles * sizeof(double)));
+    const int* perm = (g->identity_order || !g->perm.p) ? nullptr : g->perm.as<int>();
+    FDX_TRY(launch_spatial_perm(plan, V_dev, ldv, (int)g->n, K, g->ell.as<int>(), g->slice_off.as<int>(), g->deg.as<int>(), perm,
+                                seed, first_perm, n_perm, null_dev, scratch.as<double>(), out.as<double>(), st));
+    std::vector<double> host(plan.out_doubles);
+    FDX_TRY(copy_d2h(host.data(), out.p, plan.out_doubles * sizeof(double), st));   // the call's one host synchronisation
+    const double* h = host.data();
+    std::copy(h, h + K, mean_out);
+    std::copy(h + K, h + 2 * (size_t)K, m2_out);
+    std::copy(h + 2 * (size_t)K, h + 2 * (size_t)K + KK, C_out);
+    std::memcpy(counts_out + 1, h + 2 * (size_t)K + KK, 2 * sizeof(int64_t));
+    h += plan.s.out_doubles;
+    std::copy(h, h + K, m4_out);
+    std::memcpy(count_ge_out, h + K, KK * sizeof(int64_t));
+    std::memcpy(count_le_out, h + K + KK, KK * sizeof(int64_t));
+    std::copy(h + K + 2 * KK, h + K + 3 * KK, sum_d_out);
+    std::copy(h + K + 3 * KK, h + K + 4 * KK, sumsq_d_out);
+    return 0;
+}
+
+int fdx_permutation_indices_dev(uint64_t seed, int64_t r, int64_t n, int32_t* out_dev, void* stream) {
+    FDX_REQUIRE(n >= 0 && n < (1LL << 31) - 128, "fdx_permutation_indices_dev: n must be between 0 and 2^31 - 129");
+    FDX_REQUIRE(r >= 0, "fdx_permutation_indices_dev: r must not be negative");
+    FDX_REQUIRE(n == 0 || out_dev, "fdx_permutation_indices_dev: null argument");
+    return launch_permutation_indices(seed, r, (int)n, out_dev, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 // the shape checks the k-means entries share; `who` names the entry in the message

@@ -144,6 +144,26 @@ SpatialStatsPlan spatial_stats_plan(long long n, int K);
 int launch_spatial_stats(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* ell,
                          const int* slice_off, const int* deg, const int* perm, double* scratch, double* out, double* nbr_mean,
                          hipStream_t st);
+// A permutation-null call (fdx_spatial_perm_dev): the observed plan, the batch B of permutations per launch chain - what a scratch
+// budget of 1 GiB holds, 512 at the most, capped by max_batch (0: no cap) and n_perm, one at the least - and its buffers.
+struct SpatialPermPlan {
+    SpatialStatsPlan s;
+    int batch, m4_blocks;
+    size_t plane_doubles;        // K * ld: the Z (and lag) planes of one batch element
+    size_t cross_part_doubles;   // cross partials of one batch element
+    size_t part_doubles;         // partials block: the observed pass's or the batch's cross partials, whichever is larger
+    size_t null_doubles;         // B * K * K when the caller keeps no null (own_null), else 0
+    size_t scratch_doubles;      // [Z B planes | lag B planes | partials | C_r of a batch]
+    size_t out_doubles;          // SpatialStatsPlan's out, then [m4 K | count_ge K*K int64 | count_le K*K int64 | sum_d | sumsq_d]
+};
+SpatialPermPlan spatial_perm_plan(long long n, int K, long long n_perm, int max_batch, bool own_null);
+// The observed pass, m4, then permutations first_perm .. first_perm + n_perm - 1 of `seed` in batches; null_dev (n_perm, K, K)
+// device or null.  Everything is left in out (device) as laid out above.
+int launch_spatial_perm(const SpatialPermPlan& p, const double* V, long long ldv, int n, int K, const int* ell,
+                        const int* slice_off, const int* deg, const int* perm, unsigned long long seed, long long first_perm,
+                        long long n_perm, double* null_dev, double* scratch, double* out, hipStream_t st);
+// out[i] = pi_r(i), i < n: the permutation the kernels above apply
+int launch_permutation_indices(unsigned long long seed, long long r, int n, int* out, hipStream_t st);
 
 // ---- niche_kernels.cpp
 // Grids and scratch of the k-means kernels on n rows, D columns and C centres (functions of the shapes only).

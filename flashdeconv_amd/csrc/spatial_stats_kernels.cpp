@@ -17,6 +17,16 @@
 //   cross         C = Z' lag as a skinny float64 product: a workgroup owns a 32 x 32 tile of the pair space (blockIdx.y; any K),
 //                 stages 64 positions of the 32 + 32 planes in LDS and keeps a 2 x 2 block of C per thread in registers
 // The two-pass centred form is what makes near-constant columns (proportions) safe: sum V^2 - n mean^2 is never formed.
+//
+// Permutation null (fdx_spatial_perm_dev): after the observed pass above, and m4 = sum Z^4 from its planes, B permutations per
+// launch chain recompute C_r = Zpi' (A Zpi) with Zpi[k][p] = V[pi_r(perm[p])][k] - mean[k]: the centre kernel with the row index
+// sent through pi_r (evaluated in the kernel: no index array), the lag and cross kernels as they are, each with the batch as one
+// more grid dimension and per-batch plane offsets.  mean and m2 do not change under a permutation.  One kernel then reduces every
+// C_r in block order and one adds them to the counts and sums against C_obs in permutation order.
+//
+// pi_r is a keyed bijection of [0, n): an unbalanced Feistel network of 8 rounds on b = max(2, bit_length(n - 1)) bits (left half
+// b / 2 bits, right half the rest, the widths swap every round), the round function the splitmix64 finaliser, values >= n walked
+// along their cycle until they fall below n.  utils/spatial_stats.py:permutation_indices is its definition.
 #include "fdx_internal.h"
 #include "fdx_kernels.h"
 
@@ -29,11 +39,56 @@ constexpr int SS_KT = 32;                // centre: types staged at a time
 constexpr int SS_KS = SS_KT + 1;         //         odd row stride of the [spot][type] tile (column reads hit 64 banks)
 constexpr int SS_CT = 32;                // cross: edge of a pair-space tile
 constexpr int SS_CP = 64;                //        positions staged at a time (one slice)
+constexpr size_t SS_PERM_SCRATCH_BYTES = (size_t)1 << 30;   // permutation batches: scratch budget that sizes B (one at the least)
+constexpr int SS_PERM_MAX_BATCH = 512;                      //                      and its cap (a grid dimension)
 
 // same-wave LDS hand-off: a wave's ds operations execute in order; this keeps the compiler from moving them across
 __device__ __forceinline__ void wave_lds_handoff() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
+}
+
+// the splitmix64 finaliser
+__host__ __device__ __forceinline__ unsigned long long ss_mix64(unsigned long long x) {
+    x ^= x >> 30;
+    x *= 0xbf58476d1ce4e5b9ULL;
+    x ^= x >> 27;
+    x *= 0x94d049bb133111ebULL;
+    x ^= x >> 31;
+    return x;
+}
+
+// what identifies the permutations of a launch: permutation r has the key mix64(seed_mixed + (r + 1) * golden)
+struct SsPermArgs {
+    unsigned long long seed_mixed;   // mix64(seed)
+    long long first;                 // r of batch element 0
+    int wl, wr;                      // widths of the Feistel halves: wl = b / 2, wr = b - wl
+    long long plane_stride;          // doubles between the planes of two batch elements (K * ld)
+};
+
+__host__ __device__ __forceinline__ unsigned long long ss_perm_key(unsigned long long seed_mixed, long long r) {
+    return ss_mix64(seed_mixed + ((unsigned long long)r + 1ULL) * 0x9e3779b97f4a7c15ULL);
+}
+
+// pi(i) for i < n < 2^31: x = (L << wr) | R; a round sends (L, R) to (R, L ^ F(R)) and swaps the widths; 8 rounds restore them
+__device__ __forceinline__ int ss_permute_index(unsigned long long key, int i, int n, int wl, int wr) {
+    unsigned x = (unsigned)i;
+    do {
+        unsigned L = x >> wr, R = x & ((1u << wr) - 1u);
+        int a = wl, c = wr;
+#pragma unroll
+        for (unsigned round = 0; round < 8; ++round) {
+            const unsigned f = (unsigned)ss_mix64(key ^ (((unsigned long long)round << 32) | R)) & ((1u << a) - 1u);
+            const unsigned nr = L ^ f;
+            L = R;
+            R = nr;
+            const int t = a;
+            a = c;
+            c = t;
+        }
+        x = (L << wr) | R;
+    } while (x >= (unsigned)n);
+    return (int)x;
 }
 
 // partials[b][c] = sum of V[r][c] over block b's rows [b * rows_per_block, ...): 256 / K rows in flight per pass (consecutive
@@ -73,10 +128,14 @@ __global__ __launch_bounds__(256) void ss_reduce_kernel(const T* __restrict__ pa
 }
 
 // Z[k][p] = V[perm[p]][k] - mean[k] for p < n, 0 for n <= p < ld (n_slices_ld = ld / 64 slices are written);
-// m2_partials[block][k] = the block's share of sum_p Z[k][p]^2
+// m2_partials[block][k] = the block's share of sum_p Z[k][p]^2.
+// PERMUTED: batch element blockIdx.y reads row pi_r(perm[p]) instead, r = pa.first + blockIdx.y, into its own planes; whole rows of
+// V are still read as segments (the type-major planes are never gathered from); no m2 (it does not change) and no m2 tile.
+template <bool PERMUTED>
 __global__ __launch_bounds__(256) void ss_centre_kernel(const double* __restrict__ V, long long ldv, const double* __restrict__ mean,
                                                         const int* __restrict__ perm, int n, int n_slices_ld, int K,
-                                                        double* __restrict__ Z, long long ld, double* __restrict__ m2_partials) {
+                                                        double* __restrict__ Z, long long ld, double* __restrict__ m2_partials,
+                                                        SsPermArgs pa) {
     extern __shared__ __attribute__((aligned(16))) double smem[];   // 4 tiles [64][SS_KS], then m2 [4][K]
     __shared__ int row_s[4][64];
     const int lane = threadIdx.x & 63;
@@ -84,11 +143,20 @@ __global__ __launch_bounds__(256) void ss_centre_kernel(const double* __restrict
     double* tile = smem + (size_t)wib * 64 * SS_KS;
     double* m2_all = smem + (size_t)4 * 64 * SS_KS;
     double* m2w = m2_all + (size_t)wib * K;
-    for (int k = lane; k < K; k += 64) m2w[k] = 0.0;
+    unsigned long long key = 0;
+    if constexpr (PERMUTED) {
+        key = ss_perm_key(pa.seed_mixed, pa.first + blockIdx.y);
+        Z += (size_t)blockIdx.y * pa.plane_stride;
+    } else {
+        for (int k = lane; k < K; k += 64) m2w[k] = 0.0;
+    }
     for (int slice = blockIdx.x * 4 + wib; slice < n_slices_ld; slice += gridDim.x * 4) {
         const long long p = (long long)slice * 64 + lane;
         wave_lds_handoff();                                        // the previous slice's readers of row_s are done
-        row_s[wib][lane] = p < n ? (perm ? perm[p] : (int)p) : -1;
+        int row = p < n ? (perm ? perm[p] : (int)p) : -1;
+        if constexpr (PERMUTED)
+            if (row >= 0) row = ss_permute_index(key, row, n, pa.wl, pa.wr);
+        row_s[wib][lane] = row;
         for (int k0 = 0; k0 < K; k0 += SS_KT) {
             const int kc = K - k0 < SS_KT ? K - k0 : SS_KT;
             wave_lds_handoff();
@@ -99,39 +167,46 @@ __global__ __launch_bounds__(256) void ss_centre_kernel(const double* __restrict
             int sp = lane / kc, k = lane - sp * kc;
 #pragma unroll 4
             for (int f = lane; f < total; f += 64) {
-                const int row = row_s[wib][sp];
-                tile[sp * SS_KS + k] = row >= 0 ? V[(size_t)row * ldv + k0 + k] - mean[k0 + k] : 0.0;
+                const int src = row_s[wib][sp];
+                tile[sp * SS_KS + k] = src >= 0 ? V[(size_t)src * ldv + k0 + k] - mean[k0 + k] : 0.0;
                 sp += ds;
                 k += dk;
                 if (k >= kc) { k -= kc; ++sp; }
             }
             wave_lds_handoff();
             for (int kk = 0; kk < kc; ++kk) Z[(size_t)(k0 + kk) * ld + p] = tile[lane * SS_KS + kk];
-            if (lane < kc) {                                       // lane owns type k0 + lane: its 64 squares in spot order
-                double s = 0.0;
-                for (int q = 0; q < 64; ++q) {
-                    const double z = tile[q * SS_KS + lane];
-                    s = fma(z, z, s);
+            if constexpr (!PERMUTED)
+                if (lane < kc) {                                   // lane owns type k0 + lane: its 64 squares in spot order
+                    double s = 0.0;
+                    for (int q = 0; q < 64; ++q) {
+                        const double z = tile[q * SS_KS + lane];
+                        s = fma(z, z, s);
+                    }
+                    m2w[k0 + lane] += s;
                 }
-                m2w[k0 + lane] += s;
-            }
         }
     }
-    __syncthreads();
-    for (int k = threadIdx.x; k < K; k += 256)
-        m2_partials[(size_t)blockIdx.x * K + k] = ((m2_all[k] + m2_all[K + k]) + m2_all[2 * K + k]) + m2_all[3 * (size_t)K + k];
+    if constexpr (!PERMUTED) {
+        __syncthreads();
+        for (int k = threadIdx.x; k < K; k += 256)
+            m2_partials[(size_t)blockIdx.x * K + k] =
+                ((m2_all[k] + m2_all[K + k]) + m2_all[2 * K + k]) + m2_all[3 * (size_t)K + k];
+    }
 }
 
 // lag[k][p] = sum over the ELL entries of position p of Z[k][entry] (pad entries read the zero column n); positions of the last
 // slice past n get 0.  deg_partials[block] = {sum deg, sum deg^2}.  nbr_mean (may be null): row perm[p] of an (n, K) row-major
-// matrix, lag / deg + mean (the mean of the neighbours' V), 0 without neighbours.
+// matrix, lag / deg + mean (the mean of the neighbours' V), 0 without neighbours.  Batch element blockIdx.y works on the planes
+// batch_stride doubles further on; deg_partials may be null (the permuted passes: the degrees are the observed pass's).
 template <int KC>
 __global__ __launch_bounds__(256) void ss_lag_kernel(const double* __restrict__ Z, long long ld, const int* __restrict__ ell_base,
                                                      const int* __restrict__ slice_off, const int* __restrict__ deg,
                                                      const int* __restrict__ perm, const double* __restrict__ mean, int n,
                                                      int n_slices, int K, double* __restrict__ lag, double* __restrict__ nbr_mean,
-                                                     long long* __restrict__ deg_partials) {
+                                                     long long* __restrict__ deg_partials, long long batch_stride) {
     __shared__ long long red[4][2];
+    Z += (size_t)blockIdx.y * batch_stride;
+    lag += (size_t)blockIdx.y * batch_stride;
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     long long sd = 0, sd2 = 0;
@@ -173,6 +248,7 @@ __global__ __launch_bounds__(256) void ss_lag_kernel(const double* __restrict__ 
         sd += __shfl_xor(sd, off, 64);
         sd2 += __shfl_xor(sd2, off, 64);
     }
+    if (!deg_partials) return;
     if (lane == 0) { red[wib][0] = sd; red[wib][1] = sd2; }
     __syncthreads();
     if (threadIdx.x < 2)
@@ -183,10 +259,15 @@ __global__ __launch_bounds__(256) void ss_lag_kernel(const double* __restrict__ 
 // partials[blockIdx.x][a][b] = sum over the block's 64-position chunks of Z[a][p] * lag[b][p], for the (a, b) of pair-space tile
 // blockIdx.y = tile_a * ntb + tile_b.  Thread (ta, tb) of 16 x 16 owns a in {ta, ta + 16}, b in {tb, tb + 16} of the tile: per
 // position two LDS reads of each operand (the ta reads broadcast) feed four FMAs; the row stride of 65 doubles puts the 16 lag
-// rows a half-wave reads on 16 different bank pairs.
+// rows a half-wave reads on 16 different bank pairs.  Batch element blockIdx.z: planes batch_stride doubles further on, partials
+// gridDim.x * K * K further on.
 __global__ __launch_bounds__(256) void ss_cross_kernel(const double* __restrict__ Z, const double* __restrict__ lag, long long ld,
-                                                       int n_chunks, int K, int ntb, double* __restrict__ partials) {
+                                                       int n_chunks, int K, int ntb, double* __restrict__ partials,
+                                                       long long batch_stride) {
     __shared__ double zs[SS_CT][SS_CP + 1], ls[SS_CT][SS_CP + 1];
+    Z += (size_t)blockIdx.z * batch_stride;
+    lag += (size_t)blockIdx.z * batch_stride;
+    partials += (size_t)blockIdx.z * gridDim.x * K * K;
     const int a_base = (blockIdx.y / ntb) * SS_CT, b_base = (blockIdx.y % ntb) * SS_CT;
     const int ta = threadIdx.x >> 4, tb = threadIdx.x & 15;
     const int sr = threadIdx.x >> 6, sc = threadIdx.x & 63;
@@ -219,6 +300,68 @@ __global__ __launch_bounds__(256) void ss_cross_kernel(const double* __restrict_
     if (a1 < K && b1 < K) out[(size_t)a1 * K + b1] = c11;
 }
 
+// partials[blockIdx.x][k] = the block's share of sum_p Z[k][p]^4 for plane k = blockIdx.y: 256 positions at a time, each thread's
+// running sum, then a fixed tree over the 256 threads
+__global__ __launch_bounds__(256) void ss_m4_kernel(const double* __restrict__ Z, long long ld, int K, double* __restrict__ partials) {
+    __shared__ double red[256];
+    const double* z = Z + (size_t)blockIdx.y * ld;
+    double s = 0.0;
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < ld; p += (long long)gridDim.x * 256) {
+        const double v = z[p], v2 = v * v;
+        s = fma(v2, v2, s);
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[(size_t)blockIdx.x * K + blockIdx.y] = red[0];
+}
+
+// out[j][i] = partials[j][0][i] + partials[j][1][i] + ... for batch element j = blockIdx.y: the order of ss_reduce_kernel, and a
+// permutation's C_r does not depend on the batch it ran in (at 1M spots 1024 partials per output and few threads: latency-bound)
+__global__ __launch_bounds__(256) void ss_reduce_batch_kernel(const double* __restrict__ partials, int nparts, long long width,
+                                                              double* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= width) return;
+    const double* pj = partials + (size_t)blockIdx.y * nparts * width;
+    double s = 0;
+#pragma unroll 16                                                  // sixteen loads in flight; the additions keep their order
+    for (int b = 0; b < nparts; ++b) s += pj[(size_t)b * width + i];
+    out[(size_t)blockIdx.y * width + i] = s;
+}
+
+// the batch's C_r against C_obs, one thread per pair, in permutation order: d = C_r - C_obs
+__global__ __launch_bounds__(256) void ss_perm_accum_kernel(const double* __restrict__ Cr, int B, long long KK,
+                                                            const double* __restrict__ C_obs, long long* __restrict__ count_ge,
+                                                            long long* __restrict__ count_le, double* __restrict__ sum_d,
+                                                            double* __restrict__ sumsq_d) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= KK) return;
+    const double c0 = C_obs[i];
+    long long ge = count_ge[i], le = count_le[i];
+    double s = sum_d[i], q = sumsq_d[i];
+    for (int j = 0; j < B; ++j) {
+        const double c = Cr[(size_t)j * KK + i];
+        const double d = c - c0;
+        ge += c >= c0 ? 1 : 0;
+        le += c <= c0 ? 1 : 0;
+        s += d;
+        q = fma(d, d, q);
+    }
+    count_ge[i] = ge;
+    count_le[i] = le;
+    sum_d[i] = s;
+    sumsq_d[i] = q;
+}
+
+// out[i] = pi_r(i)
+__global__ __launch_bounds__(256) void ss_perm_indices_kernel(unsigned long long key, int n, int wl, int wr, int* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = ss_permute_index(key, (int)i, n, wl, wr);
+}
+
 SpatialStatsPlan spatial_stats_plan(long long n, int K) {
     SpatialStatsPlan s;
     s.ld = round_up(n + 1, 64);
@@ -241,20 +384,25 @@ SpatialStatsPlan spatial_stats_plan(long long n, int K) {
 }
 
 template <int KC>
-static void launch_lag(const SpatialStatsPlan& s, const double* Z, const int* ell, const int* slice_off, const int* deg,
-                       const int* perm, const double* mean, int n, int K, double* lag, double* nbr_mean, long long* deg_part,
-                       hipStream_t st) {
-    hipLaunchKernelGGL(ss_lag_kernel<KC>, dim3(s.lag_blocks), dim3(256), 0, st, Z, s.ld, ell, slice_off, deg, perm, mean, n,
-                       s.n_slices, K, lag, nbr_mean, deg_part);
+static void launch_lag(const SpatialStatsPlan& s, int batch, long long batch_stride, const double* Z, const int* ell,
+                       const int* slice_off, const int* deg, const int* perm, const double* mean, int n, int K, double* lag,
+                       double* nbr_mean, long long* deg_part, hipStream_t st) {
+    hipLaunchKernelGGL(ss_lag_kernel<KC>, dim3(s.lag_blocks, batch), dim3(256), 0, st, Z, s.ld, ell, slice_off, deg, perm, mean, n,
+                       s.n_slices, K, lag, nbr_mean, deg_part, batch_stride);
 }
 
-int launch_spatial_stats(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* ell,
-                         const int* slice_off, const int* deg, const int* perm, double* scratch, double* out, double* nbr_mean,
-                         hipStream_t st) {
-    if (n <= 0) return 0;
-    double* Z = scratch;
-    double* lag = Z + (size_t)K * s.ld;
-    double* part = lag + (size_t)K * s.ld;
+static void launch_lag_for(const SpatialStatsPlan& s, int batch, long long batch_stride, const double* Z, const int* ell,
+                           const int* slice_off, const int* deg, const int* perm, const double* mean, int n, int K, double* lag,
+                           double* nbr_mean, long long* deg_part, hipStream_t st) {
+    if (K <= 8) launch_lag<8>(s, batch, batch_stride, Z, ell, slice_off, deg, perm, mean, n, K, lag, nbr_mean, deg_part, st);
+    else if (K <= 16) launch_lag<16>(s, batch, batch_stride, Z, ell, slice_off, deg, perm, mean, n, K, lag, nbr_mean, deg_part, st);
+    else launch_lag<32>(s, batch, batch_stride, Z, ell, slice_off, deg, perm, mean, n, K, lag, nbr_mean, deg_part, st);
+}
+
+// the four passes of the observed statistics: Z and lag (K, ld) each, part s.partials_doubles
+static int observed_pass(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* ell,
+                         const int* slice_off, const int* deg, const int* perm, double* Z, double* lag, double* part, double* out,
+                         double* nbr_mean, hipStream_t st) {
     double* mean = out;
     double* m2 = out + K;
     double* C = out + 2 * (size_t)K;
@@ -269,27 +417,133 @@ int launch_spatial_stats(const SpatialStatsPlan& s, const double* V, long long l
 
     const size_t lds = ((size_t)4 * 64 * SS_KS + (size_t)4 * K) * sizeof(double);
     if (lds > 64 * 1024)
-        FDX_HIP(hipFuncSetAttribute((const void*)ss_centre_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(ss_centre_kernel, dim3(s.centre_blocks), dim3(256), lds, st, V, ldv, mean, perm, n, (int)(s.ld / 64), K, Z,
-                       s.ld, part);
+        FDX_HIP(hipFuncSetAttribute((const void*)ss_centre_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(ss_centre_kernel<false>, dim3(s.centre_blocks), dim3(256), lds, st, V, ldv, mean, perm, n, (int)(s.ld / 64),
+                       K, Z, s.ld, part, SsPermArgs{});
     FDX_CHECK_LAUNCH();
     hipLaunchKernelGGL(ss_reduce_kernel<double>, dim3(ceil_div(K, 256)), dim3(256), 0, st, part, s.centre_blocks, (long long)K, 1.0,
                        m2);
     FDX_CHECK_LAUNCH();
 
     long long* deg_part = reinterpret_cast<long long*>(part);
-    if (K <= 8) launch_lag<8>(s, Z, ell, slice_off, deg, perm, mean, n, K, lag, nbr_mean, deg_part, st);
-    else if (K <= 16) launch_lag<16>(s, Z, ell, slice_off, deg, perm, mean, n, K, lag, nbr_mean, deg_part, st);
-    else launch_lag<32>(s, Z, ell, slice_off, deg, perm, mean, n, K, lag, nbr_mean, deg_part, st);
+    launch_lag_for(s, 1, 0, Z, ell, slice_off, deg, perm, mean, n, K, lag, nbr_mean, deg_part, st);
     FDX_CHECK_LAUNCH();
     hipLaunchKernelGGL(ss_reduce_kernel<long long>, dim3(1), dim3(256), 0, st, deg_part, s.lag_blocks, 2LL, 1LL, counts);
     FDX_CHECK_LAUNCH();
 
     hipLaunchKernelGGL(ss_cross_kernel, dim3(s.cross_blocks, s.pair_tiles_1d * s.pair_tiles_1d), dim3(256), 0, st, Z, lag, s.ld,
-                       s.n_slices, K, s.pair_tiles_1d, part);
+                       s.n_slices, K, s.pair_tiles_1d, part, 0LL);
     FDX_CHECK_LAUNCH();
     hipLaunchKernelGGL(ss_reduce_kernel<double>, dim3(ceil_div((long long)KK, 256)), dim3(256), 0, st, part, s.cross_blocks,
                        (long long)KK, 1.0, C);
+    FDX_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_spatial_stats(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* ell,
+                         const int* slice_off, const int* deg, const int* perm, double* scratch, double* out, double* nbr_mean,
+                         hipStream_t st) {
+    if (n <= 0) return 0;
+    double* Z = scratch;
+    double* lag = Z + (size_t)K * s.ld;
+    double* part = lag + (size_t)K * s.ld;
+    return observed_pass(s, V, ldv, n, K, ell, slice_off, deg, perm, Z, lag, part, out, nbr_mean, st);
+}
+
+// b = max(2, bit_length(n - 1)), split into the Feistel halves
+static void feistel_widths(long long n, int* wl, int* wr) {
+    int b = 0;
+    for (long long v = n - 1; v > 0; v >>= 1) ++b;
+    b = std::max(2, b);
+    *wl = b / 2;
+    *wr = b - b / 2;
+}
+
+SpatialPermPlan spatial_perm_plan(long long n, int K, long long n_perm, int max_batch, bool own_null) {
+    SpatialPermPlan p;
+    p.s = spatial_stats_plan(n, K);
+    const size_t KK = (size_t)K * K;
+    p.plane_doubles = (size_t)K * p.s.ld;
+    p.cross_part_doubles = (size_t)p.s.cross_blocks * KK;
+    // per permutation in flight: its Z and lag planes, its cross partials and, where the caller keeps no null, its C_r
+    const size_t per_perm = (2 * p.plane_doubles + p.cross_part_doubles + KK) * sizeof(double);
+    long long B = (long long)std::max<size_t>(1, SS_PERM_SCRATCH_BYTES / per_perm);
+    B = std::min<long long>(B, SS_PERM_MAX_BATCH);
+    if (max_batch > 0) B = std::min<long long>(B, max_batch);
+    B = std::max<long long>(1, std::min<long long>(B, std::max<long long>(1, n_perm)));
+    p.batch = (int)B;
+    p.m4_blocks = p.s.centre_blocks;
+    p.part_doubles = std::max(p.s.partials_doubles, (size_t)B * p.cross_part_doubles);
+    p.null_doubles = own_null ? (size_t)B * KK : 0;
+    p.scratch_doubles = 2 * (size_t)B * p.plane_doubles + p.part_doubles + p.null_doubles;
+    p.out_doubles = p.s.out_doubles + K + 4 * KK;
+    return p;
+}
+
+int launch_spatial_perm(const SpatialPermPlan& p, const double* V, long long ldv, int n, int K, const int* ell,
+                        const int* slice_off, const int* deg, const int* perm, unsigned long long seed, long long first_perm,
+                        long long n_perm, double* null_dev, double* scratch, double* out, hipStream_t st) {
+    if (n <= 0) return 0;
+    const SpatialStatsPlan& s = p.s;
+    const size_t KK = (size_t)K * K;
+    const int B = p.batch;
+    double* Zall = scratch;
+    double* lagall = Zall + (size_t)B * p.plane_doubles;
+    double* part = lagall + (size_t)B * p.plane_doubles;
+    double* own_null = part + p.part_doubles;
+    double* mean = out;
+    double* C_obs = out + 2 * (size_t)K;
+    double* m4 = out + s.out_doubles;
+    long long* count_ge = reinterpret_cast<long long*>(m4 + K);
+    long long* count_le = count_ge + KK;
+    double* sum_d = m4 + K + 2 * KK;
+    double* sumsq_d = sum_d + KK;
+
+    // the observed statistics in batch element 0's planes, then m4 from its Z before the permutations overwrite it
+    FDX_TRY(observed_pass(s, V, ldv, n, K, ell, slice_off, deg, perm, Zall, lagall, part, out, nullptr, st));
+    hipLaunchKernelGGL(ss_m4_kernel, dim3(p.m4_blocks, K), dim3(256), 0, st, Zall, s.ld, K, part);
+    FDX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ss_reduce_kernel<double>, dim3(ceil_div(K, 256)), dim3(256), 0, st, part, p.m4_blocks, (long long)K, 1.0,
+                       m4);
+    FDX_CHECK_LAUNCH();
+    FDX_HIP(hipMemsetAsync(count_ge, 0, 4 * KK * sizeof(double), st));
+    if (n_perm <= 0) return 0;
+
+    SsPermArgs pa;
+    pa.seed_mixed = ss_mix64(seed);
+    feistel_widths(n, &pa.wl, &pa.wr);
+    pa.plane_stride = (long long)p.plane_doubles;
+    const size_t lds = (size_t)4 * 64 * SS_KS * sizeof(double);
+    FDX_HIP(hipFuncSetAttribute((const void*)ss_centre_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int tiles = s.pair_tiles_1d * s.pair_tiles_1d;
+    for (long long done = 0; done < n_perm; done += B) {
+        const int b = (int)std::min<long long>(B, n_perm - done);       // the last batch may be ragged
+        pa.first = first_perm + done;
+        hipLaunchKernelGGL(ss_centre_kernel<true>, dim3(s.centre_blocks, b), dim3(256), lds, st, V, ldv, mean, perm, n,
+                           (int)(s.ld / 64), K, Zall, s.ld, (double*)nullptr, pa);
+        FDX_CHECK_LAUNCH();
+        launch_lag_for(s, b, pa.plane_stride, Zall, ell, slice_off, deg, perm, mean, n, K, lagall, nullptr, nullptr, st);
+        FDX_CHECK_LAUNCH();
+        hipLaunchKernelGGL(ss_cross_kernel, dim3(s.cross_blocks, tiles, b), dim3(256), 0, st, Zall, lagall, s.ld, s.n_slices, K,
+                           s.pair_tiles_1d, part, pa.plane_stride);
+        FDX_CHECK_LAUNCH();
+        double* Cr = null_dev ? null_dev + (size_t)done * KK : own_null;
+        hipLaunchKernelGGL(ss_reduce_batch_kernel, dim3(ceil_div((long long)KK, 256), b), dim3(256), 0, st, part, s.cross_blocks,
+                           (long long)KK, Cr);
+        FDX_CHECK_LAUNCH();
+        hipLaunchKernelGGL(ss_perm_accum_kernel, dim3(ceil_div((long long)KK, 256)), dim3(256), 0, st, Cr, b, (long long)KK, C_obs,
+                           count_ge, count_le, sum_d, sumsq_d);
+        FDX_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+int launch_permutation_indices(unsigned long long seed, long long r, int n, int* out, hipStream_t st) {
+    if (n <= 0) return 0;
+    int wl, wr;
+    feistel_widths(n, &wl, &wr);
+    hipLaunchKernelGGL(ss_perm_indices_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, ss_perm_key(ss_mix64(seed), r), n, wl, wr,
+                       out);
     FDX_CHECK_LAUNCH();
     return 0;
 }

@@ -5,14 +5,17 @@ forwarding the same keyword arguments to the MI355X ``FlashDeconv``."""
 def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512, lambda_spatial="auto", rho_sparsity=0.01,
                n_hvg=2000, n_markers_per_type=50, spatial_method="knn", k_neighbors=6, radius=None, preprocess="log_cpm",
                layer_st=None, layer_ref=None, spatial_key="spatial", key_added="flashdeconv", random_state=0, copy=False,
-               spot_diagnostics=False, spatial_stats=False, n_niches=None):
+               spot_diagnostics=False, spatial_stats=False, n_niches=None, spatial_permutations=0):
     """Writes ``.obsm[key_added]`` (proportions DataFrame), ``.obs[key_added + '_dominant']`` and
     ``.uns[key_added + '_params']``; returns the modified copy when ``copy=True``, else ``None``.  ``spot_diagnostics=True``
     (additive) also writes ``.obs[key_added + '_residual']`` (relative sketch residual per spot) and
     ``.obs[key_added + '_roughness']`` (disagreement with the neighbours' abundances, ``neighbor_sq``).  ``spatial_stats=True``
     (additive) also writes ``.uns[key_added + '_moran']`` (DataFrame indexed by cell type: Moran's ``I`` of its proportions over
     the fit's graph and the ``z_score``) and ``.uns[key_added + '_colocalization']`` (cell type x cell type bivariate Moran
-    matrix).  ``n_niches=<int>`` (additive) also writes ``.obs[key_added + '_niche']`` (Categorical of niche indices: k-means of
+    matrix); with ``spatial_permutations=R`` > 0 beside it the rows are reassigned to the spots R times on the GPU
+    (``utils.spatial_stats.spatial_permutation_test``, seeded by ``random_state``): the Moran table gains the columns ``p_value``
+    and ``z_sim`` and ``.uns[key_added + '_colocalization_pvalue']`` holds the two-sided p value of every pair.
+    ``n_niches=<int>`` (additive) also writes ``.obs[key_added + '_niche']`` (Categorical of niche indices: k-means of
     each spot's proportions beside its neighbours' mean proportions, ``FlashDeconv.get_spatial_niches``) and
     ``.uns[key_added + '_niche_composition']`` (DataFrame, niche x cell type: the mean proportions of each niche's spots)."""
     from ..core.deconv import FlashDeconv
@@ -51,9 +54,14 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
         adata.uns[f"{key_added}_params"]["spot_diagnostics"] = True
     if spatial_stats:
         import pandas as pd
-        stats = model.get_spatial_autocorrelation()
+        stats = model.get_spatial_autocorrelation(n_permutations=spatial_permutations)
         types = [str(t) for t in names]
-        adata.uns[f"{key_added}_moran"] = pd.DataFrame({"I": stats["morans_i"], "z_score": stats["z_score"]}, index=types)
+        moran = {"I": stats["morans_i"], "z_score": stats["z_score"]}
+        if spatial_permutations:
+            moran.update({"p_value": stats["p_value"], "z_sim": stats["z_sim"]})
+            adata.uns[f"{key_added}_colocalization_pvalue"] = pd.DataFrame(stats["cross_p_value"], index=types, columns=types)
+            adata.uns[f"{key_added}_params"]["spatial_permutations"] = int(spatial_permutations)
+        adata.uns[f"{key_added}_moran"] = pd.DataFrame(moran, index=types)
         adata.uns[f"{key_added}_colocalization"] = pd.DataFrame(stats["cross"], index=types, columns=types)
         adata.uns[f"{key_added}_params"]["spatial_stats"] = True
     if n_niches is not None:

@@ -15,6 +15,17 @@ The sums (``mean``, ``m2``, ``C``, ``W``, ``sum deg^2``, ``neighbor_mean``) come
 (csrc/spatial_stats_kernels.cpp) on torch's current stream, float64 throughout and in a fixed order: two calls return the same
 bits.  ``assemble`` forms the statistics from them on the host.  Entries whose definition divides by zero (``W == 0``,
 ``m2_a == 0``, ``n < 2``, ``Var <= 0``) are NaN; nothing raises.
+
+Significance without the normality assumption (``spatial_permutation_test``): the rows of ``V`` are reassigned to the spots at
+random, ``V_pi[i] = V[pi_r(i)]``, and ``C_r = Z_pi' (A Z_pi)`` is recomputed for r = 0 .. R - 1 (``fdx_spatial_perm_dev``; mean and
+m2 do not change).  ``pi_r`` is a keyed bijection of [0, n) evaluated inside the kernels - no index array, no host random stream -
+and ``permutation_indices`` below is its definition, in NumPy integer arithmetic::
+
+    p_greater_ab = (1 + #{r: C_r,ab >= C_ab}) / (R + 1)      p_less likewise with <=      p_value = min(1, 2 min(greater, less))
+    z_sim_ab     = (cross_ab - mean_r cross_r,ab) / std_r cross_r,ab                      (std with ddof = 0)
+
+Beside them ``randomization_variance`` gives the exact variance of I over all n! reassignments (Cliff and Ord), which needs
+``m4 = sum_i Z_ia^4`` from the same call.
 """
 import ctypes
 
@@ -22,7 +33,13 @@ import numpy as np
 
 from .. import _lib
 
-__all__ = ["spatial_autocorrelation", "spatial_sums", "assemble"]
+__all__ = ["spatial_autocorrelation", "spatial_sums", "assemble", "spatial_permutation_test", "spatial_permutation_sums",
+           "permutation_indices", "randomization_variance", "assemble_permutation"]
+
+_MASK64 = (1 << 64) - 1
+_GOLDEN = 0x9e3779b97f4a7c15
+_FEISTEL_ROUNDS = 8
+_NULL_CALL_BYTES = 256 << 20          # return_null on host arrays: the device holds this much of the null per call
 
 
 def _is_torch(x):
@@ -69,6 +86,112 @@ def assemble(n, W, sum_deg_sq, m2, C):
         z = np.full(K, nan)
     return {"cross": cross, "morans_i": morans, "expected_i": np.float64(expected), "variance_i": np.float64(variance),
             "z_score": z}
+
+
+def _mix64(x):
+    """The splitmix64 finaliser on a uint64 array (arithmetic modulo 2^64)."""
+    x = x ^ (x >> np.uint64(30))
+    x = x * np.uint64(0xbf58476d1ce4e5b9)
+    x = x ^ (x >> np.uint64(27))
+    x = x * np.uint64(0x94d049bb133111eb)
+    return x ^ (x >> np.uint64(31))
+
+
+def _mix64_int(x):
+    return int(_mix64(np.array([x & _MASK64], dtype=np.uint64))[0])
+
+
+def permutation_indices(seed, r, n):
+    """``pi_r(0 .. n - 1)`` of ``seed`` as an int64 array: the permutation ``fdx_spatial_perm_dev`` applies to the rows of V
+    (``V_pi[i] = V[pi_r(i)]``), defined here in NumPy uint64 arithmetic; the device matches it bit for bit.
+
+    An unbalanced Feistel network on ``b = max(2, bit_length(n - 1))`` bits: ``x = (L << wr) | R`` with ``wl = b // 2`` bits of L
+    and ``wr = b - wl`` of R; each of 8 rounds sends ``(L, R)`` to ``(R, L ^ (F(R) mod 2^width(L)))`` and swaps the two widths,
+    with ``F(R) = mix64(key ^ (round << 32 | R))``, ``mix64`` the splitmix64 finaliser and
+    ``key = mix64(mix64(seed) + (r + 1) * 0x9e3779b97f4a7c15)``.  That is a bijection of [0, 2^b); a value >= n is sent through it
+    again until it falls below n (cycle-walking: a start below n lies on a cycle that returns below n), which makes it a
+    bijection of [0, n).  ``2^b < 2 n`` for n >= 3, so a walk takes under two steps on average."""
+    seed, r, n = int(seed), int(r), int(n)
+    if r < 0 or n < 0 or n >= (1 << 31) - 128:
+        raise ValueError(f"r must not be negative and n must be in [0, 2^31 - 128), got r = {r}, n = {n}")
+    b = max(2, (n - 1).bit_length()) if n > 0 else 2
+    wl0, wr0 = b // 2, b - b // 2
+    key = np.uint64(_mix64_int(_mix64_int(seed) + (r + 1) * _GOLDEN))
+    out = np.arange(n, dtype=np.uint64)
+    todo = np.arange(n)
+    with np.errstate(over="ignore"):
+        while todo.size:
+            x = out[todo]
+            L, R = x >> np.uint64(wr0), x & np.uint64((1 << wr0) - 1)
+            wl, wr = wl0, wr0
+            for rnd in range(_FEISTEL_ROUNDS):
+                f = _mix64(key ^ (np.uint64(rnd << 32) | R)) & np.uint64((1 << wl) - 1)
+                L, R = R, L ^ f
+                wl, wr = wr, wl
+            x = (L << np.uint64(wr0)) | R
+            out[todo] = x
+            todo = todo[x >= np.uint64(n)]
+    return out.astype(np.int64)
+
+
+def randomization_variance(n, W, sum_deg_sq, m2, m4):
+    """The variance of Moran's I over all n! reassignments of the values to the spots (Cliff and Ord), per column: with
+    ``S0 = W``, ``S1 = 2 W``, ``S2 = 4 sum deg^2`` (binary symmetric weights) and ``b2 = n m4 / m2^2``::
+
+        E[I^2] = {n [(n^2 - 3n + 3) S1 - n S2 + 3 S0^2] - b2 [(n^2 - n) S1 - 2n S2 + 6 S0^2]} / [(n - 1)(n - 2)(n - 3) S0^2]
+        Var    = E[I^2] - 1 / (n - 1)^2
+
+    NaN for ``n < 4``, ``W == 0`` and where ``m2`` is not positive."""
+    n, W, sum_deg_sq = int(n), int(W), int(sum_deg_sq)
+    m2 = np.asarray(m2, dtype=np.float64)
+    m4 = np.asarray(m4, dtype=np.float64)
+    if m2.ndim != 1 or m4.shape != m2.shape:
+        raise ValueError(f"m2 and m4 must be (K,), got shapes {m2.shape} and {m4.shape}")
+    if n < 4 or W <= 0:
+        return np.full(m2.shape, np.nan)
+    nf, S0 = float(n), float(W)
+    S1, S2 = 2.0 * S0, 4.0 * float(sum_deg_sq)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        b2 = np.where(m2 > 0, nf * m4 / (m2 * m2), np.nan)
+        e2 = (nf * ((nf * nf - 3.0 * nf + 3.0) * S1 - nf * S2 + 3.0 * S0 * S0)
+              - b2 * ((nf * nf - nf) * S1 - 2.0 * nf * S2 + 6.0 * S0 * S0)) / ((nf - 1.0) * (nf - 2.0) * (nf - 3.0) * S0 * S0)
+    return e2 - 1.0 / ((nf - 1.0) * (nf - 1.0))
+
+
+def assemble_permutation(n, W, m2, C, count_ge, count_le, sum_d, sumsq_d, n_permutations):
+    """The permutation keys of ``spatial_permutation_test`` from the merged counts and sums of R = ``n_permutations`` >= 1
+    permutations (pure host arithmetic): ``count_ge`` / ``count_le`` (K, K) count ``C_r >= C`` / ``C_r <= C``, ``sum_d`` /
+    ``sumsq_d`` are the sums of ``d = C_r - C`` and ``d^2``.  Every entry that is NaN in ``cross`` is NaN here; ``cross_z_sim`` is
+    also NaN where the null standard deviation is 0."""
+    R = int(n_permutations)
+    if R < 1:
+        raise ValueError(f"n_permutations must be at least 1 here, got {n_permutations}")
+    cross = assemble(n, W, 0, m2, C)["cross"]
+    K = cross.shape[0]
+    arrs = [np.asarray(a) for a in (count_ge, count_le, sum_d, sumsq_d)]
+    if any(a.shape != (K, K) for a in arrs):
+        raise ValueError(f"the counts and sums must be (K, K) = {(K, K)}, got shapes {[a.shape for a in arrs]}")
+    ge, le = arrs[0].astype(np.float64), arrs[1].astype(np.float64)
+    sd, sq = arrs[2].astype(np.float64), arrs[3].astype(np.float64)
+    dead = np.isnan(cross)
+    nan = np.float64(np.nan)
+    greater = np.where(dead, nan, (1.0 + ge) / (R + 1.0))
+    less = np.where(dead, nan, (1.0 + le) / (R + 1.0))
+    p = np.where(dead, nan, np.minimum(1.0, 2.0 * np.minimum(greater, less)))
+    m2 = np.asarray(m2, dtype=np.float64)
+    C = np.asarray(C, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        scale = (float(n) / float(W)) / np.sqrt(np.outer(m2, m2)) if W > 0 else np.full((K, K), nan)   # cross = scale * C
+        mean_d = sd / R
+        var_d = np.maximum(sq / R - mean_d * mean_d, 0.0)
+        null_mean = np.where(dead, nan, scale * (C + mean_d))
+        null_std = np.where(dead, nan, scale * np.sqrt(var_d))
+        z_sim = np.where(dead | ~(null_std > 0), nan, -mean_d / np.sqrt(var_d))
+    out = {"n_permutations": R, "cross_p_greater": greater, "cross_p_less": less, "cross_p_value": p, "cross_null_mean": null_mean,
+           "cross_null_std": null_std, "cross_z_sim": z_sim}
+    for name in ("p_value", "p_greater", "p_less", "z_sim"):
+        out[name] = np.diagonal(out["cross_" + name]).copy()
+    return out
 
 
 def _check_adjacency(A, n_rows):
@@ -130,9 +253,8 @@ def _values_on_device(values, device, stream):
     return d, a.shape[1]
 
 
-def spatial_sums(values, graph, neighbor_mean=False):
-    """The device half of ``spatial_autocorrelation``: a dict of ``mean``, ``m2`` (K,), ``C`` (K, K) - numpy - and the integers
-    ``n``, ``W``, ``sum_deg_sq``, plus ``neighbor_mean`` (n, K) on request.  Same arguments and checks."""
+def _check_values(values):
+    """(n, K) of a 2-D, non-empty ``values``; ``ValueError`` otherwise."""
     shape = tuple(values.shape) if _is_torch(values) else np.shape(values)
     if len(shape) != 2:
         raise ValueError(f"values must be a 2-D (n_spots, n_columns) array, got shape {shape}")
@@ -142,6 +264,13 @@ def spatial_sums(values, graph, neighbor_mean=False):
     dtype = str(values.dtype).replace("torch.", "") if hasattr(values, "dtype") else "float64"
     if _is_cuda_tensor(values) and dtype not in ("float32", "float64"):
         raise ValueError(f"values must be float32 or float64, got {dtype}")
+    return n, K
+
+
+def spatial_sums(values, graph, neighbor_mean=False):
+    """The device half of ``spatial_autocorrelation``: a dict of ``mean``, ``m2`` (K,), ``C`` (K, K) - numpy - and the integers
+    ``n``, ``W``, ``sum_deg_sq``, plus ``neighbor_mean`` (n, K) on request.  Same arguments and checks."""
+    n, K = _check_values(values)
     g, owned = _resolve_graph(graph, n)
     try:
         import torch
@@ -181,4 +310,140 @@ def spatial_autocorrelation(values, graph, neighbor_mean=False):
     out.update(assemble(s["n"], s["W"], s["sum_deg_sq"], s["m2"], s["C"]))
     if neighbor_mean:
         out["neighbor_mean"] = s["neighbor_mean"]
+    return out
+
+
+def _check_count(name, v):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0:
+        raise ValueError(f"{name} must be an int >= 0, got {v!r}")
+    return int(v)
+
+
+def _permutation_seed(random_state):
+    """A uint64 seed: a non-negative int as it stands, else one 63-bit draw from the ``RandomState`` that
+    ``utils.check_random_state`` makes of the argument."""
+    if isinstance(random_state, (int, np.integer)) and not isinstance(random_state, (bool, np.bool_)):
+        if not 0 <= int(random_state) <= _MASK64:
+            raise ValueError(f"random_state must be in [0, 2^64) when it is an int, got {random_state}")
+        return int(random_state)
+    from .random import check_random_state
+    rs = check_random_state(random_state)
+    return (int(rs.randint(0, 1 << 31)) << 32) | int(rs.randint(0, 1 << 32, dtype=np.int64))
+
+
+def _permutation_calls(values, g, seed, first_perm, n_perm, max_batch, return_null, chunk):
+    """The calls of ``spatial_permutation_sums`` on a resolved graph: permutations ``first_perm .. first_perm + n_perm - 1`` in
+    calls of at most ``chunk``, counts and sums merged in order."""
+    import torch
+    n, K = _check_values(values)
+    device_out = _is_cuda_tensor(values)
+    device = values.device if device_out else torch.device("cuda", torch.cuda.current_device())
+    mean, m2, m4, C = np.empty(K), np.empty(K), np.empty(K), np.empty((K, K))
+    counts = np.zeros(3, dtype=np.int64)
+    tot_ge, tot_le = np.zeros((K, K), dtype=np.int64), np.zeros((K, K), dtype=np.int64)
+    tot_sd, tot_sq = np.zeros((K, K)), np.zeros((K, K))
+    ge, le, sd, sq = np.empty_like(tot_ge), np.empty_like(tot_le), np.empty_like(tot_sd), np.empty_like(tot_sq)
+    batch = ctypes.c_int32(0)
+    batches, null = [], None
+    with torch.cuda.device(device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        V, ldv = _values_on_device(values, device, stream)
+        if return_null:
+            if device_out:
+                null = torch.empty((n_perm, K, K), dtype=torch.float64, device=device)
+            else:
+                null = np.empty((n_perm, K, K))
+                buf = torch.empty((min(chunk, max(n_perm, 1)), K, K), dtype=torch.float64, device=device)
+        done = 0
+        while True:                                     # (one call even without permutations: the observed sums and m4)
+            cnt = min(chunk, n_perm - done)
+            if return_null and cnt > 0:
+                null_ptr = ctypes.c_void_p((null[done:] if device_out else buf).data_ptr())
+            else:
+                null_ptr = None
+            _lib.check(_lib.load().fdx_spatial_perm_dev(
+                g.handle, ctypes.c_void_p(V.data_ptr()), int(ldv), int(K), ctypes.c_uint64(seed), int(first_perm + done), int(cnt),
+                int(max_batch), null_ptr, _lib.ptr_f64(mean), _lib.ptr_f64(m2), _lib.ptr_f64(C), _lib.ptr_i64(counts),
+                _lib.ptr_f64(m4), _lib.ptr_i64(ge), _lib.ptr_i64(le), _lib.ptr_f64(sd), _lib.ptr_f64(sq), ctypes.byref(batch),
+                stream))
+            if return_null and cnt > 0 and not device_out:
+                null[done:done + cnt] = _lib.tensor_to_host(buf[:cnt])
+            tot_ge += ge
+            tot_le += le
+            tot_sd += sd
+            tot_sq += sq
+            batches.append(int(batch.value))
+            done += cnt
+            if done >= n_perm:
+                break
+    out = {"mean": mean, "m2": m2, "m4": m4, "C": C, "n": int(counts[0]), "W": int(counts[1]), "sum_deg_sq": int(counts[2]),
+           "count_ge": tot_ge, "count_le": tot_le, "sum_d": tot_sd, "sumsq_d": tot_sq, "n_permutations": int(n_perm),
+           "batch": max(batches)}
+    if return_null:
+        out["null"] = null
+    return out
+
+
+def spatial_permutation_sums(values, graph, seed=0, first_perm=0, n_permutations=0, max_batch=0, return_null=False):
+    """The device half of ``spatial_permutation_test`` (``fdx_spatial_perm_dev``): everything ``spatial_sums`` returns, bit for
+    bit, ``m4`` (K,), and over permutations ``first_perm .. first_perm + n_permutations - 1`` of ``seed`` the (K, K) arrays
+    ``count_ge``, ``count_le`` (int64), ``sum_d``, ``sumsq_d`` of ``d = C_r - C``; ``batch`` is the number of permutations the
+    device ran per launch chain (``max_batch`` caps it, 0: chosen from the scratch budget), and with ``return_null=True`` ``null``
+    (n_permutations, K, K) holds every ``C_r`` - a CUDA tensor when ``values`` was one, else numpy.  The counts and the null do
+    not depend on ``max_batch`` or on how a range of permutations is split into calls."""
+    n, K = _check_values(values)
+    n_perm = _check_count("n_permutations", n_permutations)
+    first_perm, max_batch = _check_count("first_perm", first_perm), _check_count("max_batch", max_batch)
+    seed = _permutation_seed(seed)
+    g, owned = _resolve_graph(graph, n)
+    try:
+        chunk = max(1, n_perm)
+        if return_null and not _is_cuda_tensor(values):
+            chunk = max(1, min(chunk, _NULL_CALL_BYTES // (8 * K * K)))
+        return _permutation_calls(values, g, seed, first_perm, n_perm, max_batch, return_null, chunk)
+    finally:
+        if owned:
+            g.close()
+
+
+def spatial_permutation_test(values, graph, n_permutations=999, random_state=0, return_null=False):
+    """``spatial_autocorrelation`` with a permutation test of Moran's I and of every entry of the co-localisation matrix: the
+    rows of ``values`` are reassigned to the spots ``n_permutations`` times on the GPU and the observed statistics ranked against
+    that null (module docstring); no normality is assumed, which matters for proportions (zero-inflated, bounded, summing to one).
+
+    ``values`` and ``graph`` as for ``spatial_autocorrelation``, with the same checks before anything touches the GPU;
+    ``n_permutations``: an int >= 0 (``ValueError`` otherwise); ``random_state``: an int in [0, 2^64) used as the seed as it
+    stands, or None / a ``RandomState`` from which one 63-bit seed is drawn.  The same seed gives the same permutations, on any
+    input of the same length.
+
+    Returns every key of ``spatial_autocorrelation`` and ``m4``, ``variance_i_rand``, ``z_score_rand`` (K,): the variance of I
+    under randomisation (``randomization_variance``) and the z score it gives.  With ``n_permutations`` R >= 1 also
+    ``n_permutations``, the (K, K) arrays ``cross_p_greater = (1 + #{C_r >= C}) / (R + 1)``, ``cross_p_less`` (``<=``),
+    ``cross_p_value = min(1, 2 min(greater, less))``, ``cross_null_mean``, ``cross_null_std`` (ddof = 0; both in the units of
+    ``cross``), ``cross_z_sim``, their diagonals ``p_value``, ``p_greater``, ``p_less``, ``z_sim`` (K,), and with
+    ``return_null=True`` ``cross_null`` (R, K, K), the null in the units of ``cross`` (a CUDA tensor when ``values`` was one, else
+    numpy).  Entries that are NaN in ``cross`` are NaN in all of these, ``z_sim`` also where the null does not vary."""
+    _check_values(values)
+    R = _check_count("n_permutations", n_permutations)
+    s = spatial_permutation_sums(values, graph, seed=_permutation_seed(random_state), n_permutations=R,
+                                 return_null=bool(return_null) and R >= 1)
+    out = {"mean": s["mean"], "m2": s["m2"], "m4": s["m4"], "n": s["n"], "n_edges": s["W"] // 2}
+    out.update(assemble(s["n"], s["W"], s["sum_deg_sq"], s["m2"], s["C"]))
+    var = randomization_variance(s["n"], s["W"], s["sum_deg_sq"], s["m2"], s["m4"])
+    out["variance_i_rand"] = var
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["z_score_rand"] = np.where(var > 0, (out["morans_i"] - out["expected_i"]) / np.sqrt(np.where(var > 0, var, 1.0)), np.nan)
+    if R >= 1:
+        out.update(assemble_permutation(s["n"], s["W"], s["m2"], s["C"], s["count_ge"], s["count_le"], s["sum_d"], s["sumsq_d"], R))
+        if return_null:
+            dead = np.isnan(out["cross"])
+            with np.errstate(divide="ignore", invalid="ignore"):
+                scale = np.where(dead, np.nan, (float(s["n"]) / max(float(s["W"]), 1.0)) / np.sqrt(np.outer(s["m2"], s["m2"])))
+            null = s["null"]
+            if _is_torch(null):
+                import torch
+                null = null * torch.as_tensor(scale, device=null.device)
+            else:
+                null = null * scale
+            out["cross_null"] = null
     return out

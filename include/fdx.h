@@ -562,6 +562,25 @@ int fdx_spot_diagnostics_dev(const fdx_graph* g, const double* beta_dev, int64_t
  * refused. */
 int fdx_spatial_autocorr_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, int32_t K, double* mean_out, double* m2_out,
                              double* C_out, int64_t* counts_out, double* neighbor_mean_dev, void* stream);
+/* Permutation null of the statistics above (additive, not in the reference).  Permutation r of `seed` is the bijection pi_r of
+ * [0, n) that flashdeconv_amd/utils/spatial_stats.py:permutation_indices defines (an 8-round unbalanced Feistel network on
+ * max(2, bit_length(n - 1)) bits with the splitmix64 finaliser as round function, cycle-walked below n), evaluated in the kernels:
+ * V_pi[i] = V[pi_r(i)] in the caller's spot order, C_r = Z_pi' (A Z_pi).  The call runs the observed pass (mean_out, m2_out, C_out,
+ * counts_out as - and bit for bit what - fdx_spatial_autocorr_dev returns), m4_out[a] = sum_i Z_ia^4, then permutations
+ * first_perm .. first_perm + n_perm - 1 in batches of B per launch chain (B from a scratch budget of 1 GiB, at most 512 and at
+ * most max_batch when that is positive; *batch_out, may be NULL, reports it).  To HOST memory, (K, K) row-major each:
+ *   count_ge_out / count_le_out = how many of the call's permutations have C_r >= C_obs / C_r <= C_obs
+ *   sum_d_out / sumsq_d_out     = sum over them of d = C_r - C_obs and of d^2, added in permutation order
+ * null_dev (may be NULL): (n_perm, K, K) DEVICE array that receives every C_r.  A permutation's C_r does not depend on B, on
+ * first_perm or on the call it ran in, so counts of split calls add up exactly.  No floating-point atomics, two calls return the
+ * same bits, one host synchronisation.  Refused: a shard's local graph, n >= 2^31 - 128, null pointers, negative counts. */
+int fdx_spatial_perm_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, int32_t K, uint64_t seed, int64_t first_perm,
+                         int64_t n_perm, int32_t max_batch, double* null_dev, double* mean_out, double* m2_out, double* C_out,
+                         int64_t* counts_out, double* m4_out, int64_t* count_ge_out, int64_t* count_le_out, double* sum_d_out,
+                         double* sumsq_d_out, int32_t* batch_out, void* stream);
+/* out_dev[i] (n int32, DEVICE) = pi_r(i) of `seed` for i < n, by the device function the kernels of fdx_spatial_perm_dev use.
+ * Asynchronous on `stream`. */
+int fdx_permutation_indices_dev(uint64_t seed, int64_t r, int64_t n, int32_t* out_dev, void* stream);
 /* k-means of per-spot feature rows (spatial niches; additive, not in the reference).  F_dev: (n, D) row-major DEVICE matrix with
  * row stride ldf >= D (columns D .. ldf - 1 are never read); centres: (C, D) row-major, contiguous, 1 <= C <= 64.  Everywhere
  * d2(i, c) = sum_k (F_ik - M_ck)^2 with the difference formed first, accumulated by fma in ascending k.  float64 throughout, no
