@@ -134,6 +134,7 @@ SIGNATURES = {
     "fdx_graph_shard_knn_dev": (c_int, [c_void_p, c_i64, c_i32, c_i32, c_i32, p_i64, c_i32, c_void_p, ctypes.POINTER(c_void_p)]),
     "fdx_graph_shard_status": (c_int, [c_void_p, p_i64, p_i64, p_i32, p_i32]),
     "fdx_graph_row_indices": (c_int, [c_void_p, c_i64, p_i32, c_i32, p_i32]),
+    "fdx_graph_tile_info": (c_int, [c_void_p, p_i32, p_i32, p_i32]),
     "fdx_graph_halo_info": (c_int, [c_void_p, p_i64, p_i32, p_i32]),
     "fdx_graph_send_indices_dev": (c_int, [c_void_p, c_void_p, c_void_p]),
     "fdx_prepare_dev": (c_int, [c_void_p, c_i32, c_i64, c_i32, c_i64, c_void_p, p_double, c_i32, p_i32, p_double, p_double,
@@ -155,6 +156,7 @@ SIGNATURES = {
     "fdx_kmeans_dev": (c_int, [c_void_p, c_i64, c_i64, c_i32, c_i32, c_i32, c_void_p, c_void_p, p_i64, p_double, p_i32, p_i32,
                                c_void_p]),
     "fdx_normalize_dev": (c_int, [c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p, c_void_p]),
+    "fdx_export_dev": (c_int, [c_void_p, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p]),
     "fdx_gene_moments_dev": (c_int, [c_void_p, c_i32, c_i64, c_i32, c_i64, p_double, p_double, c_void_p]),
     "fdx_gather_columns_dev": (c_int, [c_void_p, c_i32, c_i64, c_i32, c_i64, p_i32, c_i32, c_void_p, c_void_p]),
     "fdx_version": (c_int, []),
@@ -501,6 +503,12 @@ class Graph:
         t = c_i32(0)
         check(load().fdx_graph_knn_far(self._h, ctypes.byref(t)))
         return int(t.value)
+
+    def tile_info(self):
+        """(n_tiles, halo_max, tiled) of the LDS-tiled sweep and objective; tiled False: the graph takes the generic kernels."""
+        nt, hm, t = c_i32(0), c_i32(0), c_i32(0)
+        check(load().fdx_graph_tile_info(self._h, ctypes.byref(nt), ctypes.byref(hm), ctypes.byref(t)))
+        return int(nt.value), int(hm.value), bool(t.value)
 
     def close(self):
         if self._h is not None and self._h.value:

@@ -417,7 +417,8 @@ int launch_bcd_objective_tiled(const BcdSweepArgs& a0, double* partials, hipStre
     a.it = 0;
     const bool hit = bcd_sweep_dispatch_part0(a, st) || bcd_sweep_dispatch_part1(a, st) || bcd_sweep_dispatch_part2(a, st) ||
                      bcd_sweep_dispatch_part3(a, st) || bcd_sweep_dispatch_part4(a, st) || bcd_sweep_dispatch_part5(a, st) ||
-                     bcd_sweep_dispatch_part6(a, st) || bcd_sweep_dispatch_part7(a, st);
+                     bcd_sweep_dispatch_part6(a, st) || bcd_sweep_dispatch_part7(a, st) || bcd_sweep_dispatch_part8(a, st) ||
+                     bcd_sweep_dispatch_part9(a, st);       // every part of the sweep's own list (launch_bcd_sweep): 60..64 types live in 8 and 9
     if (!hit) return 1;
     FDX_CHECK_LAUNCH();
     return 0;

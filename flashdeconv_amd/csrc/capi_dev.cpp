@@ -210,6 +210,16 @@ int fdx_graph_row_indices(const fdx_graph* g, int64_t row, int32_t* idx_out, int
     return 0;
 }
 
+// test hook: which traversal the sweep and the objective take on this graph (tiled = the LDS-tiled kernels of bcd_sweep_inst.cpp)
+int fdx_graph_tile_info(const fdx_graph* g, int32_t* n_tiles, int32_t* halo_max, int32_t* tiled) {
+    FDX_REQUIRE(g != nullptr, "fdx_graph_tile_info: null graph");
+    FDX_TRY(fdx::graph_meta_sync(g));
+    if (n_tiles) *n_tiles = g->n_tiles;
+    if (halo_max) *halo_max = g->halo_max;
+    if (tiled) *tiled = g->tiled ? 1 : 0;
+    return 0;
+}
+
 int fdx_graph_halo_info(const fdx_graph* local, int64_t* n_halo, int32_t* send_counts, int32_t* recv_counts) {
     FDX_REQUIRE(local != nullptr, "fdx_graph_halo_info: null graph");
     FDX_TRY(fdx::graph_meta_sync(local));
@@ -573,6 +583,18 @@ int fdx_kmeans_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, int32
     *n_iter_out = it;
     *converged_out = converged;
     return 0;
+}
+
+int fdx_export_dev(const fdx_graph* g, const double* beta_dev, int64_t ld, int32_t K, double* beta_out_dev, double* prop_out_dev,
+                   void* stream) {
+    FDX_TRY(fdx::graph_meta_sync(g));
+    FDX_REQUIRE(g && beta_dev && K > 0, "fdx_export_dev: bad arguments");
+    FDX_REQUIRE(ld >= g->n, "fdx_export_dev: ld must cover the own spots");
+    FDX_REQUIRE(g->world_n == 0 && g->n_total == g->n, "fdx_export_dev: a shard's local graph is refused (its perm holds global ids)");
+    if (g->n == 0) return 0;
+    // the export of a fit (fit.cpp): the graph's own perm, null for a graph in the caller's order
+    const int* perm = (g->identity_order || !g->perm.p) ? nullptr : g->perm.as<int>();
+    return launch_normalize_export(beta_dev, ld, perm, (int)g->n, g->n_slices, K, beta_out_dev, prop_out_dev, (hipStream_t)stream);
 }
 
 int fdx_normalize_dev(const double* beta_dev, int64_t ld, int64_t n, int32_t K, double* beta_out_dev, double* prop_out_dev,

@@ -87,8 +87,9 @@ __global__ __launch_bounds__(256) void normalize_export_kernel(const double* __r
         s += v;
         if (use_lds) tile[lane * Ks + k] = v;
     }
-    // normalize_proportions: all-zero rows -> 1/K, otherwise beta / max(rowsum, 1e-10)   (solver.py:445-451)
-    const double den = fmax(s, 1e-10);
+    // normalize_proportions: all-zero rows -> 1/K, otherwise beta / max(rowsum, 1e-10)   (solver.py:445-451).  np.maximum hands a
+    // NaN sum on (fmax would answer 1e-10): a row that holds a NaN comes out all NaN, and a NaN sum is neither 0 nor negative below
+    const double den = (s < 1e-10) ? 1e-10 : s;
     const int orow = perm ? perm[ii] : ii;
     if (!use_lds) {
         if (active)

@@ -509,6 +509,10 @@ int fdx_graph_shard_status(const fdx_graph* local, int64_t* own_nnz, int64_t* kn
 /* test hook: the stored neighbour indices of one row as the sweeps read them (positions in this graph's own order; local graph:
  * own rows 0..n-1, halo slots n..n_total-1); at most cap are written, *deg_out is the row's degree */
 int fdx_graph_row_indices(const fdx_graph* g, int64_t row, int32_t* idx_out, int32_t cap, int32_t* deg_out);
+/* test hook: the workgroup tiles of the LDS-tiled sweep and objective (tile = 256 consecutive solver positions): their number, the
+ * largest halo of a tile, and whether the graph takes the tiled kernels at all (0: every traversal gathers from global memory).
+ * Waits for a deferred build.  Any output may be NULL. */
+int fdx_graph_tile_info(const fdx_graph* g, int32_t* n_tiles, int32_t* halo_max, int32_t* tiled);
 int fdx_graph_halo_info(const fdx_graph* local, int64_t* n_halo, int32_t* send_counts, int32_t* recv_counts);
 /* Own local indices to send, grouped by destination rank ascending (sum(send_counts) int32 entries, device). */
 int fdx_graph_send_indices_dev(const fdx_graph* local, int32_t* idx_out_dev, void* stream);
@@ -618,6 +622,12 @@ int fdx_kmeans_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, int32
 /* beta (K, ld) type-major -> beta_out / prop_out (n, K) row-major in solver order of the own spots. */
 int fdx_normalize_dev(const double* beta_dev, int64_t ld, int64_t n, int32_t K, double* beta_out_dev, double* prop_out_dev,
                       void* stream);
+/* The export pass of a fit on its own (core/solver.py:431-452 fused with the layout change): beta (K, ld) type-major in the solver
+ * order of the whole graph `g` -> beta_out / prop_out (g->n, K) row-major at row perm[i] of fdx_graph_perm_dev, i.e. in the caller's
+ * spot order (a graph in the caller's order: row i).  Either output may be NULL (not written).  A shard's local graph is refused:
+ * fdx_normalize_dev serves it.  Asynchronous on `stream`. */
+int fdx_export_dev(const fdx_graph* g, const double* beta_dev, int64_t ld, int32_t K, double* beta_out_dev, double* prop_out_dev,
+                   void* stream);
 
 /* ---- native sharded solve: the per-iteration loop on RCCL directly (csrc/comm.cpp) -------------------------- *
  * The reference has no distributed code; sharding spots is legal because the sweep is Jacobi across spots
