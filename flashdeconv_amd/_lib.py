@@ -127,6 +127,7 @@ SIGNATURES = {
                             p_double, ctypes.POINTER(FitInfo), c_void_p]),
     "fdx_fit_carry_free": (c_int, [c_void_p]),
     "fdx_graph_build_dev": (c_int, [c_void_p, c_i64, c_i32, c_i32, c_i32, c_double, c_void_p, ctypes.POINTER(c_void_p)]),
+    "fdx_graph_cache_stats": (c_int, [p_i64]),
     "fdx_graph_perm_dev": (c_int, [c_void_p, c_void_p, c_void_p]),
     "fdx_side_stream": (c_int, [ctypes.POINTER(c_void_p)]),
     "fdx_stream_wait_stream": (c_int, [c_void_p, c_void_p]),

@@ -78,7 +78,8 @@ int fdx_free(void* dev_ptr) {
 }
 
 int fdx_trim(void) {
-    leverage_cache_clear();          // the X caches first: their device blocks go back to the pool, and from there to the driver
+    graph_cache_clear();             // the caches first: their device blocks go back to the pool, and from there to the driver
+    leverage_cache_clear();          // (a graph that a handle still holds lives on with it)
     x_side_cache_clear();
     pool_trim();
     return 0;
@@ -236,7 +237,7 @@ int fdx_graph_export_csr(const fdx_graph* g, int64_t* indptr, int32_t* indices) 
 }
 
 int fdx_graph_destroy(fdx_graph* g) {
-    delete g;
+    graph_release(g);                // this handle's reference: a graph the cache (or another handle) still holds lives on
     return 0;
 }
 

@@ -17,20 +17,60 @@ using namespace fdx;
 
 extern "C" {
 
+// The graph depends on the coordinates, the method and k / radius and on nothing else of a fit, and one slide is fitted more than
+// once: the build is looked up by content first (graph_cache.cpp).  Hit: the entry's graph with one more holder - no binning, no
+// k-NN, no symmetrise / ELL / tile kernels, no allocations.  Miss: built as before - with the bounding box in hand if the lookup
+// had to compare - and an own copy of the coordinates queued on the way, published once the graph is complete.
 int fdx_graph_build_dev(const double* coords_dev, int64_t n, int32_t dim, int32_t method, int32_t k, double radius,
                         void* stream, fdx_graph** out) {
-    PoolStream pool_stream((hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    PoolStream pool_stream(st);
     FDX_REQUIRE(out != nullptr, "fdx_graph_build_dev: null output");
     *out = nullptr;
     FDX_REQUIRE(n == 0 || coords_dev != nullptr, "fdx_graph_build_dev: null coords");
+    FDX_REQUIRE(method == FDX_GRAPH_KNN || method == FDX_GRAPH_RADIUS, "fdx_graph_build_dev: unknown method");
+    hipEvent_t begin = nullptr;                                  // the fit's prologue timer (fdx_fit_info.prologue_ms) starts here
+    if (hipEventCreate(&begin) != hipSuccess || hipEventRecord(begin, st) != hipSuccess) {
+        if (begin) (void)hipEventDestroy(begin);
+        begin = nullptr;
+        (void)hipGetLastError();
+    }
+    struct BeginGuard { hipEvent_t* e; ~BeginGuard() { if (*e) (void)hipEventDestroy(*e); } } begin_guard{&begin};   // until a graph takes it
+    const bool cached = n > 0 && dim >= 1 && dim <= 8 && graph_cache_enabled();
+    GraphCacheKey key;
+    double box[6];
+    bool have_box = false;
+    if (cached) {
+        key = graph_cache_key(n, dim, method, k, radius);
+        fdx_graph* hit = nullptr;
+        FDX_TRY(graph_cache_lookup(key, coords_dev, st, &hit, box, &have_box));
+        if (hit) {
+            std::lock_guard<std::mutex> lk(hit->mu);            // re-recorded on every hit: prologue_ms keeps its meaning (build call -> sketch)
+            if (hit->begin_event) (void)hipEventDestroy(hit->begin_event);
+            hit->begin_event = begin;
+            hit->begin_stream = begin ? st : nullptr;
+            begin = nullptr;
+            *out = hit;
+            return 0;
+        }
+    }
+    std::shared_ptr<GraphCacheEntry> entry;
+    if (cached) FDX_TRY(graph_cache_entry_new(key, &entry));
+    // the entry's copy of the coordinates: queued under the host's wait for the bounding box (no host time on the build's path)
+    const std::function<int()> copy = [&]() -> int { return entry ? graph_cache_queue_copy(entry.get(), coords_dev, st) : 0; };
+    GraphBuildHooks hooks;
+    hooks.box = have_box ? box : nullptr;
+    hooks.under_wait = &copy;
     fdx_graph* g = new fdx_graph();
-    if (hipEventCreate(&g->begin_event) == hipSuccess && hipEventRecord(g->begin_event, (hipStream_t)stream) == hipSuccess)
-        g->begin_stream = (hipStream_t)stream;                  // the fit's prologue timer (fdx_fit_info.prologue_ms) starts here
+    g->begin_event = begin;
+    g->begin_stream = begin ? st : nullptr;
+    begin = nullptr;
     int rc;
-    if (method == FDX_GRAPH_KNN) rc = graph_build_knn(coords_dev, n, dim, k, g, (hipStream_t)stream);
-    else if (method == FDX_GRAPH_RADIUS) rc = graph_build_radius(coords_dev, n, dim, radius, 0, n, g, (hipStream_t)stream);
-    else rc = fail(FDX_ERR_INVALID, "fdx_graph_build_dev: unknown method");
-    if (rc) { delete g; return rc; }
+    if (method == FDX_GRAPH_KNN) rc = graph_build_knn(coords_dev, n, dim, k, g, st, &hooks);
+    else rc = graph_build_radius(coords_dev, n, dim, radius, 0, n, g, st, &hooks);
+    if (rc) { delete g; return rc; }                             // (fail() has drained the device: the copy can go)
+    g->cache_pending = std::move(entry);
+    if (!g->meta_pending) graph_cache_publish(g);                // built to the end here; a queued build: graph_meta_sync publishes
     *out = g;
     return 0;
 }

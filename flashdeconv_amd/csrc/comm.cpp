@@ -176,6 +176,7 @@ __global__ void halo_unpack_kernel(double* __restrict__ beta, long long ld, int 
 
 // tiles (256 rows) that hold a row some peer needs, and the others
 int build_tile_lists(const fdx_graph& g, hipStream_t st) {
+    std::lock_guard<std::mutex> first_use(g.mu);    // (a graph may have several holders: fdx_graph.h)
     if (g.n_tiles_boundary >= 0) return 0;
     const int total = g.send_off.empty() ? 0 : g.send_off.back();
     std::vector<int> idx((size_t)total);
@@ -672,6 +673,7 @@ static int sharded_solve_impl(fdx_comm* c, const fdx_graph* g, const double* H_d
     // from the rows are made once per graph
     const bool fused_pack = tiled && total_send > 0 && g->n > 0 && bcd_sweep_uses_tiles(a) && !fdx::env("FDX_NO_FUSED_PACK");
     if (fused_pack) {
+        std::lock_guard<std::mutex> first_use(g->mu);
         if (!g->send_head.p) {
             FDX_TRY(g->send_head.alloc((size_t)g->n * 4));
             FDX_TRY(g->send_ent.alloc((size_t)total_send * sizeof(int4)));

@@ -46,7 +46,7 @@ Switch g_switches[] = {
     {"FDX_KDTREE_HOST_QUERIES", "tie remedy: cKDTree queries on host threads instead of kd_query_kernel"},
     {"FDX_KDTREE_THREADS", "host threads of the restated cKDTree (build forks, host queries)"},
     {"FDX_KDTREE_PAR_DEPTH", "fork depth of the restated cKDTree build"},
-    {"FDX_NO_PLAN_CACHE", "sketch plans / tile schedules, leverage scores and the X side recomputed every fit (bench.py: cold_ms)"},
+    {"FDX_NO_PLAN_CACHE", "sketch plans / tile schedules, leverage scores, the X side and the spatial graph recomputed every fit (bench.py: cold_ms)"},
     {"FDX_NO_SIDE_STREAM", "everything on the caller's stream"},
     {"FDX_CSR_KEEP_CAP", "entries per wave of the fused CSR sketch's keep buffer (tests: rows that overflow it)"},
 };

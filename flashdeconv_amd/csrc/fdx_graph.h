@@ -1,8 +1,13 @@
 // Device-resident spatial graph in the layout the BCD sweep consumes (internal).
 #pragma once
+#include <memory>
+#include <mutex>
 #include <vector>
 
 #include "fdx_internal.h"
+#include "graph_cache.h"
+
+namespace fdx { struct GraphCacheEntry; }
 
 #define FDX_TILE_HALO_CAP 1024
 
@@ -81,11 +86,28 @@ struct fdx_graph {
     fdx::DevBuf send_off_dev, recv_off_dev;
     fdx::DevBuf counts_dev;                                  // 4 doubles behind meta_event: own nnz, tied own rows, far, overflow (all-reduced by fdx_shard_fit_dev)
     // recorded by fdx_graph_build_dev ahead of the first kernel of the build, on begin_stream: the fit's prologue timer starts here
+    // (a fit takes the event over when it starts - under `mu`: a cached graph has several holders, see below)
     hipEvent_t begin_event = nullptr;
     hipStream_t begin_stream = nullptr;
+    // Holders: every handle handed out is one, the cache's entry (graph_cache.cpp) is one; fdx_graph_destroy drops one and the last
+    // deletes.  Only complete graphs are shared (published by graph_meta_sync), so their arrays and counts are read-only for
+    // every holder; what is still written after publication - begin_event, the members built on first use - is guarded by `mu`.
+    fdx::RefCount refs;
+    mutable std::mutex mu;
+    // a build that missed the cache: its entry-to-be (the copy of the coordinates), published once the graph is complete
+    mutable std::shared_ptr<fdx::GraphCacheEntry> cache_pending;
     ~fdx_graph();
 };
 
 namespace fdx {
 int graph_meta_sync(const fdx_graph* g);         // no-op unless a deferred build is outstanding
+void graph_release(fdx_graph* g);                // one holder less; the last one deletes
+// ---- graph_cache.cpp: whole graphs by content of the coordinates (FDX_NO_PLAN_CACHE bypasses, fdx_trim drops)
+bool graph_cache_enabled();
+GraphCacheKey graph_cache_key(long long n, int dim, int method, int k, double radius);
+int graph_cache_lookup(const GraphCacheKey& key, const double* d_coords, hipStream_t st, fdx_graph** out, double box[6], bool* have_box);
+int graph_cache_entry_new(const GraphCacheKey& key, std::shared_ptr<GraphCacheEntry>* out);
+int graph_cache_queue_copy(GraphCacheEntry* e, const double* d_coords, hipStream_t st);
+void graph_cache_publish(fdx_graph* g);          // no-op unless g carries an unpublished entry
+void graph_cache_clear();
 }

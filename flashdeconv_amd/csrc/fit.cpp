@@ -368,6 +368,17 @@ int fit_impl(const YSource& ysrc, int64_t n, int32_t G, const double* X, int32_t
         if (rc) { delete g; return rc; }
         *graph_inout = g;
     }
+    // the build's start event serves this one fit (a later fit on the same handle starts its own clock; a cached graph gets a
+    // new one with every hit): taken over here, under the graph's lock - the graph may have other holders
+    Event build_begin(true);
+    if (prm->graph_method == FDX_GRAPH_GIVEN) {
+        std::lock_guard<std::mutex> lk(g->mu);
+        if (g->begin_event && g->begin_stream == st) {
+            build_begin.e = g->begin_event;
+            g->begin_event = nullptr;
+            g->begin_stream = nullptr;
+        }
+    }
     // a deferred build (graph_ell.cpp) queued on ANOTHER stream: everything below reads the graph's arrays (perm first)
     if (g->meta_pending && g->meta_event && g->meta_stream != st) FDX_HIP(hipStreamWaitEvent(st, g->meta_event, 0));
     FDX_TRY(t_graph.record(st));
@@ -554,15 +565,9 @@ int fit_impl(const YSource& ysrc, int64_t n, int32_t G, const double* X, int32_t
     info->graph_ms = t_graph.ms_since(t_begin.e);
     info->sketch_ms = rows.fused ? eS1.ms_since(eS0.e) : rows.sketch_ms;   // the chunked path keeps its per-chunk split of the same interval
     info->gram_ms = rows.gram_ms;
-    const bool from_build = g->begin_event && g->begin_stream == st && prm->graph_method == FDX_GRAPH_GIVEN;
-    const hipEvent_t t0 = from_build ? g->begin_event : t_begin.e;
+    const hipEvent_t t0 = build_begin ? build_begin.e : t_begin.e;
     info->prologue_ms = eS0.ms_since(t0);
     info->span_ms = t_end.ms_since(t0);
-    if (from_build) {       // the build's start event has served its one fit: a later fit on the same handle starts its own clock
-        (void)hipEventDestroy(g->begin_event);
-        g->begin_event = nullptr;
-        g->begin_stream = nullptr;
-    }
     info->solve_ms = t_solved.ms_since(eS1.e);
     info->finish_ms = t_end.ms_since(t_solved.e);
     info->diag_ms = t_diag1.ms_since(t_diag0.e);

@@ -6,12 +6,25 @@ struct fdx_graph_plan;   // binned points of a two-phase k-NN build (graph_inter
 
 namespace fdx {
 
+// What fdx_graph_build_dev hands a build after its cache lookup (graph_cache.cpp).  box: mn[3], mx[3] of d_coords already in hand
+// (the lookup waited for it together with its compare kernels) - the build queues no box kernels and waits for nothing.
+// under_wait: queued while the host waits for the box (the entry's copy of the coordinates), or at once when the box is in hand.
+struct GraphBuildHooks {
+    const double* box = nullptr;
+    const std::function<int()>* under_wait = nullptr;
+};
+inline int graph_hook_under_wait(const GraphBuildHooks* h) { return (h && h->under_wait && *h->under_wait) ? (*h->under_wait)() : 0; }
+// The bounding box of d_coords (with_box; dim <= 3) and whatever `also` queues behind its kernels, given the device address of
+// four zeroed 64-bit words of the job's pinned block: ONE host wait, then box[6] = mn[3], mx[3] and words[4] as the device left them.
+int coords_box(const double* d_coords, long long n, int dim, hipStream_t st, bool with_box, const std::function<int(long long*)>& also,
+               double box[6], long long words[4]);
+
 // coords: device (n, dim) row-major float64, dim in {1,2,3}
-int graph_build_knn(const double* d_coords, long long n, int dim, int k, fdx_graph* g, hipStream_t st);
+int graph_build_knn(const double* d_coords, long long n, int dim, int k, fdx_graph* g, hipStream_t st, const GraphBuildHooks* hooks = nullptr);
 // two-phase k-NN build for spot shards (see graph_knn.cpp): lists of rows [lo, hi) -> caller all-gathers -> own rows
 // band: also the lists of the rows outside [lo, hi) in cells next to a cell with an own row; every other row of cnt reads 0
 int graph_knn_lists(const double* d_coords, long long n, int dim, int k, long long lo, long long hi, int* nbr, int* cnt,
-                    fdx_graph_plan** out, hipStream_t st, bool band = false);
+                    fdx_graph_plan** out, hipStream_t st, bool band = false, const GraphBuildHooks* hooks = nullptr);
 int graph_from_knn_lists(fdx_graph_plan* plan, const int* nbr, const int* cnt, long long lo, long long hi, fdx_graph* g,
                          hipStream_t st);
 void graph_plan_destroy(fdx_graph_plan* plan);
@@ -29,7 +42,7 @@ int ckdtree_lists_device(const double* coords_host, const double* coords_dev, lo
 int graph_plan_order(const fdx_graph_plan* plan, int* d_perm_out, int* d_rank_out, hipStream_t st);   // device copies of perm / rank (either may be NULL)
 // rows [lo, hi) (solver positions) of the radius graph, the others left empty; [0, n) = the whole graph
 int graph_build_radius(const double* d_coords, long long n, int dim, double radius, long long lo, long long hi, fdx_graph* g,
-                       hipStream_t st);
+                       hipStream_t st, const GraphBuildHooks* hooks = nullptr);
 // distance of every point to its nearest other point (caller's order); used by the "grid" method (graph.py:163-167)
 int graph_nearest_distance(const double* d_coords, long long n, int dim, double* d_out, hipStream_t st);
 // CSR in the caller's labels; device outputs indptr (n+1) int64, indices (nnz) int32 ascending per row

@@ -628,21 +628,27 @@ int graph_meta_sync(const fdx_graph* gc) {
     g->knn_ties = g->meta_host[4] & 0xffffffffLL;
     if (rows > g->ell_cap_rows) {                     // the bound was too small (hubs): build the ELL again with its exact size
         trace_host("meta: ELL bound too small, rebuilding");
-        return finish_ell(g, g->rows.as<int>(), g->row_stride, g->row_extra.as<int>(), g->meta_stream, false);
+        FDX_TRY(finish_ell(g, g->rows.as<int>(), g->row_stride, g->row_extra.as<int>(), g->meta_stream, false));
+        graph_cache_publish(g);                       // complete (the rebuild ends synchronously)
+        return 0;
     }
     g->ell_rows = rows;
     g->halo_max = (int)(g->meta_host[3] & 0xffffffffLL);
     g->tiled = g->n_tiles > 0 && rows > 0 && (g->meta_host[3] >> 32) == 0;
     if (fdx::env("FDX_TRACE_HOST")) std::fprintf(stderr, "[fdx-host] meta: rows %lld of %lld, nnz %lld, largest halo %d, tiled %d\n", rows, g->ell_cap_rows, g->nnz, g->halo_max, (int)g->tiled);
+    graph_cache_publish(g);                           // complete: a build that missed the cache becomes an entry (graph_cache.cpp)
     return 0;
 }
 
-int graph_build_knn(const double* d_coords, long long n, int dim, int k, fdx_graph* g, hipStream_t st) {
+int graph_build_knn(const double* d_coords, long long n, int dim, int k, fdx_graph* g, hipStream_t st, const GraphBuildHooks* hooks) {
     FDX_REQUIRE(dim >= 1 && dim <= FDX_KNN_MAX_DIM, "graph: k-NN graphs take coordinates of 1 to 8 dimensions");
     FDX_REQUIRE(n >= 0 && n < 0x7fffff00LL, "graph: n out of range");
     FDX_REQUIRE(k >= 0, "graph: k must be non-negative");
     const int k_act = (int)std::min<long long>(k, n - 1);           // graph.py:51
-    if (k_act <= 0) return empty_graph(n, g, st);                   // graph.py:53-57
+    if (k_act <= 0) {                                               // graph.py:53-57
+        FDX_TRY(graph_hook_under_wait(hooks));
+        return empty_graph(n, g, st);
+    }
     const int kk = k_act + 1;
     FDX_REQUIRE(kk <= 64, "graph: k_neighbors above 63 is not supported");
     FDX_REQUIRE((long long)n * kk < 0x7fffff00LL, "graph: n*k too large");
@@ -650,7 +656,7 @@ int graph_build_knn(const double* d_coords, long long n, int dim, int k, fdx_gra
     FDX_TRY(nbr.alloc((size_t)n * kk * 4));
     FDX_TRY(cnt.alloc((size_t)n * 4));
     fdx_graph_plan* plan = nullptr;
-    FDX_TRY(graph_knn_lists(d_coords, n, dim, k, 0, n, nbr.as<int>(), cnt.as<int>(), &plan, st));
+    FDX_TRY(graph_knn_lists(d_coords, n, dim, k, 0, n, nbr.as<int>(), cnt.as<int>(), &plan, st, false, hooks));
     // Whole graph in one piece: the rest is queued without a host round trip (FDX_GRAPH_SYNC=1: built to the end here); the
     // lists and the binned points stay with the graph until graph_meta_sync has seen the kernels finish.
     const bool defer = !fdx::env("FDX_GRAPH_SYNC");
@@ -668,15 +674,19 @@ int graph_build_knn(const double* d_coords, long long n, int dim, int k, fdx_gra
 // Rows [lo, hi) (solver positions) of the radius graph; the other rows are left empty.  A radius graph is symmetric by
 // construction (graph.py:115-121), so a shard's own rows need nothing from the other shards.
 int graph_build_radius(const double* d_coords, long long n, int dim, double radius, long long lo, long long hi, fdx_graph* g,
-                       hipStream_t st) {
+                       hipStream_t st, const GraphBuildHooks* hooks) {
     FDX_REQUIRE(dim >= 1 && dim <= 3, "graph: coordinate dimension must be 1, 2 or 3");
     FDX_REQUIRE(n >= 0 && n < 0x7fffff00LL, "graph: n out of range");
     FDX_REQUIRE(radius > 0.0 && std::isfinite(radius), "graph: radius must be positive");
     FDX_REQUIRE(0 <= lo && lo <= hi && hi <= n, "graph: bad row range");
     FDX_REQUIRE(lo % 64 == 0, "graph: a shard must start on a 64-row slice boundary");
-    if (n <= 1) return empty_graph(n, g, st);
+    if (n <= 1) {
+        FDX_TRY(graph_hook_under_wait(hooks));
+        return empty_graph(n, g, st);
+    }
     BinnedPoints b;
-    FDX_TRY(bin_points(d_coords, n, dim, 1.0, radius, &b, st));   // cell edge >= radius: one shell suffices
+    FDX_TRY(bin_points(d_coords, n, dim, 1.0, radius, &b, st, 0, 0, 0, hooks ? hooks->under_wait : nullptr,
+                       hooks ? hooks->box : nullptr));   // cell edge >= radius: one shell suffices
     const int R = (int)std::ceil(radius / b.gp.h[0] * (1.0 + 1e-12));
     g->n = n; g->n_total = n; g->identity_order = false;
     g->perm.take(b.perm);

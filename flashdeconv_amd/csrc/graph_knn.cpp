@@ -479,7 +479,7 @@ int graph_nearest_distance(const double* d_coords, long long n, int dim, double*
 // Single GPU: [lo, hi) = [0, n), no exchange - the same code.
 
 int graph_knn_lists(const double* d_coords, long long n, int dim, int k, long long lo, long long hi, int* nbr, int* cnt,
-                    fdx_graph_plan** out, hipStream_t st, bool band) {
+                    fdx_graph_plan** out, hipStream_t st, bool band, const GraphBuildHooks* hooks) {
     FDX_REQUIRE(dim >= 1 && dim <= FDX_KNN_MAX_DIM, "graph: k-NN graphs take coordinates of 1 to 8 dimensions");
     FDX_REQUIRE(dim <= 3 || n <= (1 << 18), "graph: coordinates of more than 3 dimensions are searched exhaustively: at most 262144 spots");
     FDX_REQUIRE(n >= 2 && n < 0x7fffff00LL, "graph: n out of range");
@@ -502,6 +502,7 @@ int graph_knn_lists(const double* d_coords, long long n, int dim, int k, long lo
         // solver order from the first three coordinates, exhaustive search in all of them
         DevBuf c3;
         rc = c3.alloc((size_t)n * 3 * sizeof(double));
+        if (!rc) rc = graph_hook_under_wait(hooks);   // (no box of d_coords is used here)
         if (!rc) {
             hipLaunchKernelGGL(take3_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, d_coords, n, dim, c3.as<double>());
             rc = bin_points(c3.as<double>(), n, 3, tpc, 0.0, &plan->b, st);
@@ -539,10 +540,12 @@ int graph_knn_lists(const double* d_coords, long long n, int dim, int k, long lo
         }
         FDX_TRY(plan->ties.alloc(8));
         FDX_HIP(hipMemsetAsync(plan->ties.p, 0, 8, st));
+        FDX_TRY(graph_hook_under_wait(hooks));
         return 0;
     };
-    rc = shard_band ? bin_points(d_coords, n, dim, tpc, 0.0, &plan->b, st, lo, hi, BAND_R, &fills)
-                    : bin_points(d_coords, n, dim, tpc, 0.0, &plan->b, st, 0, 0, 0, &fills);
+    const double* box = hooks ? hooks->box : nullptr;
+    rc = shard_band ? bin_points(d_coords, n, dim, tpc, 0.0, &plan->b, st, lo, hi, BAND_R, &fills, box)
+                    : bin_points(d_coords, n, dim, tpc, 0.0, &plan->b, st, 0, 0, 0, &fills, box);
     if (rc) { delete plan; return rc; }
     const BinnedPoints& b = plan->b;
     const int* perm = b.perm.as<int>();

@@ -61,8 +61,8 @@ int fdx_device_name(char* buf, int buflen);
 /* ---- plain device memory helpers (so a ctypes-only binding needs no other GPU runtime) ---------------- */
 int fdx_malloc(void** dev_ptr, size_t bytes);
 int fdx_free(void* dev_ptr);
-/* Device scratch is recycled through a caching pool; fdx_trim() returns every cached block to the driver (and drops the two
- * caches below, whose entries own device blocks). */
+/* Device scratch is recycled through a caching pool; fdx_trim() returns every cached block to the driver (and drops the
+ * caches below and the graph cache of fdx_graph_build_dev, whose entries own device blocks). */
 int fdx_trim(void);
 /* What depends on the signature matrix X alone is kept by content, at most 4 entries each: the leverage scores (fdx_leverage_*)
  * and the X side of a fit (X_sketch, XtX: fdx_fit_dev, fdx_fit_csr_dev, fdx_prepare_dev, fdx_shard_fit_dev).  A hit returns what
@@ -428,6 +428,15 @@ int fdx_metrics_evaluate_dev(const void* pred_dev, const void* true_dev, int32_t
  * own stream behind the build when it differs). */
 int fdx_graph_build_dev(const double* coords_dev, int64_t n, int32_t dim, int32_t method, int32_t k, double radius,
                         void* stream, fdx_graph** out);
+/* The graph depends on the coordinates, the method and k / radius alone, and one slide is fitted more than once: whole graphs are
+ * kept by CONTENT of the coordinates (compared on the device as bytes: one ulp, or -0.0 for 0.0, is another slide; never by
+ * pointer), at most 2 per device, least recently used out.  fdx_graph_build_dev looks there first: a hit returns the graph the
+ * first build produced - the same bits - and queues no build; a miss builds as before and publishes the graph, with an own copy
+ * of the coordinates, once it is complete.  Handles are counted: fdx_graph_destroy drops one reference, the cache holds one, and
+ * an entry that is evicted or trimmed dies with its last handle.  FDX_NO_PLAN_CACHE bypasses the cache, fdx_trim() drops it.
+ * Graphs of spot shards and of fdx_graph_from_csr never enter it.
+ * fdx_graph_cache_stats: {hits, misses, entries, device bytes the entries hold}; bypassed calls count as neither hit nor miss. */
+int fdx_graph_cache_stats(int64_t out[4]);
 /* The library's own non-blocking side stream of the current device (hipStream_t): a graph build queued there runs beside whatever
  * the caller's stream is doing (FlashDeconv.fit with gene selection: beside the gene statistics and the host's ranking). */
 int fdx_side_stream(void** stream_out);
