@@ -143,6 +143,8 @@ SIGNATURES = {
     "fdx_init_beta_dev": (c_int, [c_void_p, c_i64, c_i64, c_i32, c_void_p]),
     "fdx_bcd_sweep_dev": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_double, c_double,
                                   c_double, c_i32, c_void_p, c_void_p, c_void_p]),
+    "fdx_bcd_sweep_ex_dev": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_double, c_double,
+                                     c_double, c_i32, c_void_p, c_void_p, c_double, c_void_p, c_i32, c_void_p]),
     "fdx_bcd_fold_dev": (c_int, [c_void_p, c_void_p, c_i32, c_void_p]),
     "fdx_objective_partials_dev": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i32, p_double, c_void_p]),
     "fdx_spot_diagnostics_dev": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i32, c_i32, c_void_p, c_void_p,

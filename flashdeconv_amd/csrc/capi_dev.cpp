@@ -352,6 +352,16 @@ int fdx_init_beta_dev(double* beta_dev, int64_t ld, int64_t n_fill, int32_t K, v
 int fdx_bcd_sweep_dev(const fdx_graph* g, const double* H_dev, int64_t ldh, const double* XtX_dev, const double* beta_in,
                       double* beta_out, int64_t ld, int32_t K, double lambda, double rho_eff, double tol, int32_t it,
                       void* stats_dev, double* rel_change_dev, void* stream) {
+    return fdx_bcd_sweep_ex_dev(g, H_dev, ldh, XtX_dev, beta_in, beta_out, ld, K, lambda, rho_eff, tol, it, stats_dev, rel_change_dev,
+                                0.0, nullptr, 0, stream);
+}
+
+// test hook: the same sweep with the two forms of the tiled kernel that only whole solves reach otherwise - the first sweep from a
+// constant start (INIT) and the sweep over a list of tiles
+int fdx_bcd_sweep_ex_dev(const fdx_graph* g, const double* H_dev, int64_t ldh, const double* XtX_dev, const double* beta_in,
+                         double* beta_out, int64_t ld, int32_t K, double lambda, double rho_eff, double tol, int32_t it,
+                         void* stats_dev, double* rel_change_dev, double init_uniform, const int32_t* tile_list_dev, int32_t n_list,
+                         void* stream) {
     FDX_TRY(fdx::graph_meta_sync(g));
     FDX_REQUIRE(g && H_dev && XtX_dev && beta_in && beta_out && stats_dev && rel_change_dev, "fdx_bcd_sweep_dev: null argument");
     FDX_REQUIRE(ld >= g->n_total + 1, "fdx_bcd_sweep_dev: ld must cover own + halo + zero row");
@@ -369,6 +379,14 @@ int fdx_bcd_sweep_dev(const fdx_graph* g, const double* H_dev, int64_t ldh, cons
     a.H = H_dev; a.XtX = XtX_dev; a.beta_in = beta_in; a.beta_out = beta_out;
     a.stats = (unsigned long long*)stats_dev; a.rel_change = rel_change_dev;
     a.lambda = lambda; a.rho = rho_eff; a.tol = tol; a.ldh = (int)ldh; a.ld = (int)ld; a.K = K; a.it = it;
+    if (init_uniform != 0.0 || tile_list_dev != nullptr || n_list != 0) {
+        // only the tiled kernel knows these forms (launch_k): elsewhere the launch would sweep every spot from beta_in, or not run
+        FDX_REQUIRE(bcd_sweep_uses_tiles(a), "fdx_bcd_sweep_ex_dev: init_uniform and tile lists need the tiled sweep");
+        FDX_REQUIRE(init_uniform == 0.0 || K <= FDX_MAX_K_FAST, "fdx_bcd_sweep_ex_dev: init_uniform needs K <= 64");
+        FDX_REQUIRE((tile_list_dev != nullptr) == (n_list > 0) && (init_uniform == 0.0 || tile_list_dev == nullptr),
+                    "fdx_bcd_sweep_ex_dev: a tile list comes with its length, and not together with init_uniform");
+        a.init_uniform = init_uniform; a.tile_list = tile_list_dev; a.n_list = n_list;
+    }
     return launch_bcd_sweep(a, scratch.as<double>(), scratch_ld, (hipStream_t)stream);
 }
 

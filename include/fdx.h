@@ -549,6 +549,15 @@ int fdx_init_beta_dev(double* beta_dev, int64_t ld, int64_t n_fill, int32_t K, v
 int fdx_bcd_sweep_dev(const fdx_graph* g, const double* H_dev, int64_t ldh, const double* XtX_dev, const double* beta_in,
                       double* beta_out, int64_t ld, int32_t K, double lambda, double rho_eff, double tol, int32_t it,
                       void* stats_dev, double* rel_change_dev, void* stream);
+/* test hook: fdx_bcd_sweep_dev with the two forms of the tiled sweep that otherwise only whole solves reach.  init_uniform != 0: every
+ * old abundance IS that constant and beta_in is not read (the first sweep of a solve; K <= 64).  tile_list_dev (n_list int32 tile
+ * numbers, device): only those tiles of 256 solver positions are swept and add to the statistics.  FDX_ERR_INVALID where the graph and
+ * K do not take the tiled sweep (fdx_graph_tile_info), for init_uniform above 64 types, and for both extras at once.  With
+ * (0, NULL, 0) it is fdx_bcd_sweep_dev. */
+int fdx_bcd_sweep_ex_dev(const fdx_graph* g, const double* H_dev, int64_t ldh, const double* XtX_dev, const double* beta_in,
+                         double* beta_out, int64_t ld, int32_t K, double lambda, double rho_eff, double tol, int32_t it,
+                         void* stats_dev, double* rel_change_dev, double init_uniform, const int32_t* tile_list_dev, int32_t n_list,
+                         void* stream);
 int fdx_bcd_fold_dev(void* stats_dev, double* rel_change_dev, int32_t it, void* stream);
 /* (cross, quad, spatial, l1) partial sums of the objective over the own spots (core/solver.py:269-284), to host. */
 int fdx_objective_partials_dev(const fdx_graph* g, const double* beta_dev, int64_t ld, const double* H_dev, int64_t ldh,
