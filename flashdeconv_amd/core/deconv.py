@@ -659,6 +659,22 @@ class FlashDeconv:
             out["neighbor_mean"] = spatial_sums(values, self, neighbor_mean=True)["neighbor_mean"]
         return out
 
+    def get_local_spatial_statistics(self, what="proportions", n_permutations=0, random_state=None):
+        """Where a cell type is spatially clustered (additive, not in the reference): local Moran's I with its HH / LH / LL / HL
+        quadrant and the Getis-Ord Gi* hot-spot score per spot and cell type, over the graph the fit used -
+        ``utils.local_stats.local_spatial_statistics`` on ``proportions_`` (``what="proportions"``) or ``beta_``
+        (``what="abundances"``) and the model's device graph.  Works for both ``output`` kinds of ``fit``.
+
+        ``n_permutations=R`` > 0 adds the conditional-permutation p values and simulated z scores per spot, seeded by
+        ``random_state`` (None: the model's)."""
+        self._require_fitted()
+        if what not in ("proportions", "abundances"):
+            raise ValueError(f"Unknown what: {what}. Choose from 'proportions', 'abundances'.")
+        from ..utils.local_stats import local_spatial_statistics
+        return local_spatial_statistics(self.proportions_ if what == "proportions" else self.beta_, self,
+                                        n_permutations=n_permutations,
+                                        random_state=self.random_state if random_state is None else random_state)
+
     def get_spatial_niches(self, n_niches, what="proportions", features="both", **kw):
         """Groups the spots into ``n_niches`` spatial niches (tissue domains) by k-means of their composition, of their
         neighbourhood's composition over the graph the fit used, or of both (additive, not in the reference):

@@ -34,7 +34,7 @@ using namespace fdx;
 
 extern "C" {
 
-int fdx_version(void) { return 201; }  // 0.2.1: fdx_fit_params / fdx_fit_info grew (per-spot diagnostics)
+int fdx_version(void) { return 202; }  // 0.2.2: fdx_local_stats_dev and fdx_conditional_indices_dev added (nothing else changed)
 
 const char* fdx_last_error(void) { return g_last_error.c_str(); }
 

@@ -527,6 +527,56 @@ int fdx_permutation_indices_dev(uint64_t seed, int64_t r, int64_t n, int32_t* ou
     return launch_permutation_indices(seed, r, (int)n, out_dev, (hipStream_t)stream);
 }
 
+int fdx_local_stats_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, int32_t K, uint64_t seed, int64_t first_perm,
+                        int64_t n_perm, double* nbr_sum_dev, int32_t* deg_dev, int32_t* count_ge_dev, int32_t* count_le_dev,
+                        double* sum_d_dev, double* sumsq_d_dev, double* mean_out, double* m2_out, int64_t* counts_out,
+                        void* stream) {
+    FDX_REQUIRE(g && V_dev && nbr_sum_dev && deg_dev && mean_out && m2_out && counts_out, "fdx_local_stats_dev: null argument");
+    FDX_TRY(fdx::graph_meta_sync(g));
+    FDX_REQUIRE(K >= 1 && ldv >= K, "fdx_local_stats_dev: K must be positive and ldv at least K");
+    FDX_REQUIRE(first_perm >= 0 && n_perm >= 0, "fdx_local_stats_dev: first_perm and n_perm must not be negative");
+    FDX_REQUIRE(n_perm < (1LL << 31), "fdx_local_stats_dev: n_perm must be below 2^31");
+    FDX_REQUIRE(n_perm == 0 || (count_ge_dev && count_le_dev && sum_d_dev && sumsq_d_dev),
+                "fdx_local_stats_dev: null argument (the permutation outputs may be null only with n_perm == 0)");
+    FDX_REQUIRE(!g->shard_pending && g->n_total == g->n && g->world_n == 0,
+                "fdx_local_stats_dev: a shard's local graph is refused (whole graphs on one GPU only)");
+    FDX_REQUIRE(g->n < (1LL << 31) - 128, "fdx_local_stats_dev: too many spots");
+    FDX_REQUIRE(g->n == 0 || (g->ell.p && g->slice_off.p && g->deg.p), "fdx_local_stats_dev: the graph has no device tables");
+    hipStream_t st = (hipStream_t)stream;
+    PoolStream pool_stream(st);
+    counts_out[0] = g->n;
+    counts_out[1] = counts_out[2] = 0;
+    if (g->n == 0) {                                    // no spots: no mean, and no row to write
+        std::fill(mean_out, mean_out + K, std::nan(""));
+        std::fill(m2_out, m2_out + K, 0.0);
+        return 0;
+    }
+    const SpatialStatsPlan plan = spatial_stats_plan(g->n, K);
+    DevBuf scratch, out;
+    FDX_TRY(scratch.alloc(plan.scratch_doubles * sizeof(double)));
+    FDX_TRY(out.alloc(plan.out_doubles * sizeof(double)));
+    const int* perm = (g->identity_order || !g->perm.p) ? nullptr : g->perm.as<int>();
+    FDX_TRY(launch_local_stats(plan, V_dev, ldv, (int)g->n, K, g->ell.as<int>(), g->slice_off.as<int>(), g->deg.as<int>(), perm,
+                               seed, first_perm, (int)n_perm, scratch.as<double>(), out.as<double>(), nbr_sum_dev, deg_dev,
+                               count_ge_dev, count_le_dev, sum_d_dev, sumsq_d_dev, st));
+    std::vector<double> host(plan.out_doubles);
+    FDX_TRY(copy_d2h(host.data(), out.p, plan.out_doubles * sizeof(double), st));   // the call's one host synchronisation
+    const size_t KK = (size_t)K * K;
+    std::copy(host.begin(), host.begin() + K, mean_out);
+    std::copy(host.begin() + K, host.begin() + 2 * (size_t)K, m2_out);
+    std::memcpy(counts_out + 1, host.data() + 2 * (size_t)K + KK, 2 * sizeof(int64_t));
+    return 0;
+}
+
+int fdx_conditional_indices_dev(uint64_t seed, int64_t r, int64_t spot, int64_t n, int64_t count, int32_t* out_dev, void* stream) {
+    FDX_REQUIRE(n >= 1 && n < (1LL << 31) - 128, "fdx_conditional_indices_dev: n must be between 1 and 2^31 - 129");
+    FDX_REQUIRE(r >= 0, "fdx_conditional_indices_dev: r must not be negative");
+    FDX_REQUIRE(spot >= 0 && spot < n, "fdx_conditional_indices_dev: spot must be in [0, n)");
+    FDX_REQUIRE(count >= 0 && count <= n - 1, "fdx_conditional_indices_dev: count must be between 0 and n - 1");
+    FDX_REQUIRE(count == 0 || out_dev, "fdx_conditional_indices_dev: null argument");
+    return launch_conditional_indices(seed, r, (int)spot, (int)n, (int)count, out_dev, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 // the shape checks the k-means entries share; `who` names the entry in the message

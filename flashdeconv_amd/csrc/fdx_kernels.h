@@ -165,6 +165,18 @@ int launch_spatial_perm(const SpatialPermPlan& p, const double* V, long long ldv
 // out[i] = pi_r(i), i < n: the permutation the kernels above apply
 int launch_permutation_indices(unsigned long long seed, long long r, int n, int* out, hipStream_t st);
 
+// ---- local_stats_kernels.cpp
+// Per-spot neighbour sums and their conditional-permutation null (fdx_local_stats_dev), behind the observed pass of
+// launch_spatial_stats on the same scratch and out (mean, m2 and the counts are that pass's).  nbr_sum (n, K) float64 and
+// deg_out (n) int32 in the caller's spot order; with n_perm > 0 count_ge, count_le (n, K) int32 and sum_d, sumsq_d (n, K)
+// float64 over conditional permutations first_perm .. first_perm + n_perm - 1 of `seed`, overwritten.
+int launch_local_stats(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* ell,
+                       const int* slice_off, const int* deg, const int* perm, unsigned long long seed, long long first_perm,
+                       int n_perm, double* scratch, double* out, double* nbr_sum, int* deg_out, int* count_ge, int* count_le,
+                       double* sum_d, double* sumsq_d, hipStream_t st);
+// out[t] = the t-th of the `count` spots drawn for `spot` in conditional permutation r (0 <= count <= n - 1)
+int launch_conditional_indices(unsigned long long seed, long long r, int spot, int n, int count, int* out, hipStream_t st);
+
 // ---- niche_kernels.cpp
 // Grids and scratch of the k-means kernels on n rows, D columns and C centres (functions of the shapes only).
 struct KmeansPlan {

@@ -1,0 +1,202 @@
+// Local indicators of spatial association (not in the reference): per spot i and column a of V (n, K) the neighbour sum
+//   S_ia = sum_{j in N(i)} V_ja
+// over the model's graph, and its conditional-permutation null: spot i keeps its value and its deg_i neighbours are replaced by
+// deg_i other spots drawn without replacement, S_ia,r their sum, for r = first_perm .. first_perm + n_perm - 1.  Kept per (i, a):
+//   count_ge = #{S_r >= S}    count_le = #{S_r <= S}    sum_d, sumsq_d of d = S_r - S
+// Local Moran's I, Gi*, the quadrants and the p values are assembled from these (flashdeconv_amd/utils/local_stats.py).
+// Everything is ranked on the raw sums: with deg_i fixed S_r >= S is the event lag_r >= lag, zeros add exactly (the ties of
+// zero-inflated data stay ties), and the device's rounding of the mean does not enter.
+//
+// The draw is a function, as the permutations of spatial_stats_kernels.cpp are (perm_device.h): with F_key the keyed bijection of
+// [0, n), key = mix64(key_r + (i + 1) * golden) and key_r the key of permutation r, the drawn spots are the first deg_i values
+// other than i among F_key(0), ..., F_key(deg_i) - a bijection meets i at most once, so deg_i + 1 evaluations always suffice.
+// utils/local_stats.py:conditional_indices is the definition; ls_draw below is the one device copy, which the kernel and
+// fdx_conditional_indices_dev both call.
+//
+// Two kernels behind the observed pass of spatial_stats_kernels.cpp (which gives mean, m2 and the degree sums):
+//   neighbour sums   one lane per position of the sliced ELL, LS_KC columns of register accumulators per walk of the list; rows of
+//                    V are read in the caller's order through perm, S and deg are written in the caller's order
+//   conditional null one wave per spot, the lanes take 64 permutations at a time: deg_i is uniform across the wave, so the draw
+//                    loop is, and each lane reads whole row segments of V (LS_KC contiguous doubles).  Columns go in chunks of
+//                    LS_KC (the draws are evaluated again per chunk: a few hundred integer operations against a row gather); a lane keeps
+//                    its running sum_d / sumsq_d over its permutations r = first + lane, first + lane + 64, ... in ascending
+//                    order and the 64 lanes are added by a fixed butterfly at the end; the comparisons against the broadcast S
+//                    are counted by ballot and popcount.  No floating-point atomics, no LDS, no per-lane array indexed at run
+//                    time, any degree (a hub of degree n - 1 just loops longer).  The grid is a function of n only and no
+//                    result depends on it.
+#include "fdx_internal.h"
+#include "fdx_kernels.h"
+#include "perm_device.h"
+
+#include <algorithm>
+
+namespace fdx {
+
+constexpr int LS_KC = 8;                 // columns per walk of a list / per evaluation of the draws
+constexpr int LS_CAP_BLOCKS = 1 << 18;   // cap of the null kernel's grid (4 spots per workgroup per stride)
+
+// what identifies the conditional permutations of a launch
+struct LsPermArgs {
+    unsigned long long seed_mixed;   // mix64(seed)
+    long long first;                 // r of the launch's first permutation
+    int n_perm;
+    int wl, wr;                      // widths of the Feistel halves
+};
+
+__host__ __device__ __forceinline__ unsigned long long ls_cond_key(unsigned long long key_r, int spot) {
+    return ss_mix64(key_r + ((unsigned long long)spot + 1ULL) * 0x9e3779b97f4a7c15ULL);
+}
+
+// take(slot, c) for the `count` spots c drawn for `spot`, slot = 0 .. count - 1 in order; 0 <= count <= n - 1
+template <class Take>
+__device__ __forceinline__ void ls_draw(unsigned long long key, int spot, int n, int count, int wl, int wr, Take&& take) {
+    if (count <= 0) return;
+    bool skipped = false;
+    for (int t = 0; t <= count; ++t) {
+        const int c = ss_permute_index(key, t, n, wl, wr);
+        const bool self = c == spot;
+        if (!self && (skipped || t < count)) take(skipped ? t - 1 : t, c);
+        skipped = skipped || self;
+    }
+}
+
+// nbr_sum[perm[p]][k] = sum over the ELL entries j of position p of V[perm[j]][k] (pad entries skipped), in list order;
+// deg_out[perm[p]] = deg[p]
+__global__ __launch_bounds__(256) void ls_nbr_sum_kernel(const double* __restrict__ V, long long ldv,
+                                                         const int* __restrict__ ell_base, const int* __restrict__ slice_off,
+                                                         const int* __restrict__ deg, const int* __restrict__ perm, int n,
+                                                         int n_slices, int K, double* __restrict__ nbr_sum,
+                                                         int* __restrict__ deg_out) {
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int slice = blockIdx.x * 4 + wib; slice < n_slices; slice += gridDim.x * 4) {
+        const long long p = (long long)slice * 64 + lane;
+        const bool active = p < n;
+        const int w0 = slice_off[slice];
+        const int w = slice_off[slice + 1] - w0;
+        const int* ell = ell_base + (size_t)w0 * 64 + lane;
+        const size_t orow = active ? (perm ? (size_t)perm[p] : (size_t)p) : 0;
+        if (active) deg_out[orow] = deg[p];
+        for (int k0 = 0; k0 < K; k0 += LS_KC) {
+            double acc[LS_KC];
+#pragma unroll
+            for (int kk = 0; kk < LS_KC; ++kk) acc[kk] = 0.0;
+            for (int m = 0; m < w; ++m) {
+                const int j = active ? ell[(size_t)m * 64] : n;
+                if (j >= 0 && j < n) {
+                    const double* row = V + (size_t)(perm ? perm[j] : j) * ldv;
+#pragma unroll
+                    for (int kk = 0; kk < LS_KC; ++kk) acc[kk] += row[k0 + kk < K ? k0 + kk : K - 1];   // past K - 1: loaded, not kept
+                }
+            }
+            if (active) {
+#pragma unroll
+                for (int kk = 0; kk < LS_KC; ++kk)
+                    if (k0 + kk < K) nbr_sum[orow * K + k0 + kk] = acc[kk];
+            }
+        }
+    }
+}
+
+// the conditional null of spot blockIdx.x * 4 + wave (grid-stride), in the caller's order: deg_out and nbr_sum as written above
+__global__ __launch_bounds__(256) void ls_cond_null_kernel(const double* __restrict__ V, long long ldv, int n, int K,
+                                                           const int* __restrict__ deg_out, const double* __restrict__ nbr_sum,
+                                                           LsPermArgs pa, int* __restrict__ count_ge, int* __restrict__ count_le,
+                                                           double* __restrict__ sum_d, double* __restrict__ sumsq_d) {
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (long long sp = (long long)blockIdx.x * 4 + wib; sp < n; sp += (long long)gridDim.x * 4) {
+        const int spot = (int)sp;
+        const int dg = __builtin_amdgcn_readfirstlane(deg_out[spot]);
+        const size_t obase = (size_t)spot * K;
+        for (int k0 = 0; k0 < K; k0 += LS_KC) {
+            double s_obs[LS_KC], sd[LS_KC], sq[LS_KC];
+            int ge[LS_KC], le[LS_KC];
+#pragma unroll
+            for (int kk = 0; kk < LS_KC; ++kk) {
+                s_obs[kk] = nbr_sum[obase + (k0 + kk < K ? k0 + kk : K - 1)];
+                sd[kk] = sq[kk] = 0.0;
+                ge[kk] = le[kk] = 0;
+            }
+            for (long long r0 = 0; r0 < pa.n_perm; r0 += 64) {                     // 64-bit: n_perm may be 2^31 - 1
+                const bool valid = r0 + lane < pa.n_perm;
+                double acc[LS_KC];
+#pragma unroll
+                for (int kk = 0; kk < LS_KC; ++kk) acc[kk] = 0.0;
+                if (valid) {
+                    const unsigned long long key = ls_cond_key(ss_perm_key(pa.seed_mixed, pa.first + r0 + lane), spot);
+                    ls_draw(key, spot, n, dg, pa.wl, pa.wr, [&](int, int c) {
+                        const double* row = V + (size_t)c * ldv;
+#pragma unroll
+                        for (int kk = 0; kk < LS_KC; ++kk) acc[kk] += row[k0 + kk < K ? k0 + kk : K - 1];
+                    });
+                }
+#pragma unroll
+                for (int kk = 0; kk < LS_KC; ++kk) {
+                    const double d = acc[kk] - s_obs[kk];
+                    ge[kk] += __popcll(__ballot(valid && acc[kk] >= s_obs[kk]));
+                    le[kk] += __popcll(__ballot(valid && acc[kk] <= s_obs[kk]));
+                    if (valid) {
+                        sd[kk] += d;
+                        sq[kk] = fma(d, d, sq[kk]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int kk = 0; kk < LS_KC; ++kk) {
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) {
+                    sd[kk] += __shfl_xor(sd[kk], off, 64);
+                    sq[kk] += __shfl_xor(sq[kk], off, 64);
+                }
+                if (lane == 0 && k0 + kk < K) {
+                    count_ge[obase + k0 + kk] = ge[kk];
+                    count_le[obase + k0 + kk] = le[kk];
+                    sum_d[obase + k0 + kk] = sd[kk];
+                    sumsq_d[obase + k0 + kk] = sq[kk];
+                }
+            }
+        }
+    }
+}
+
+// out[slot] = the slot-th spot drawn for `spot` under `key`: one lane runs the kernel's own draw
+__global__ __launch_bounds__(64) void ls_cond_indices_kernel(unsigned long long key, int spot, int n, int count, int wl, int wr,
+                                                             int* __restrict__ out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    ls_draw(key, spot, n, count, wl, wr, [&](int slot, int c) { out[slot] = c; });
+}
+
+int launch_local_stats(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* ell,
+                       const int* slice_off, const int* deg, const int* perm, unsigned long long seed, long long first_perm,
+                       int n_perm, double* scratch, double* out, double* nbr_sum, int* deg_out, int* count_ge, int* count_le,
+                       double* sum_d, double* sumsq_d, hipStream_t st) {
+    if (n <= 0) return 0;
+    FDX_TRY(launch_spatial_stats(s, V, ldv, n, K, ell, slice_off, deg, perm, scratch, out, nullptr, st));
+    hipLaunchKernelGGL(ls_nbr_sum_kernel, dim3(s.lag_blocks), dim3(256), 0, st, V, ldv, ell, slice_off, deg, perm, n, s.n_slices, K,
+                       nbr_sum, deg_out);
+    FDX_CHECK_LAUNCH();
+    if (n_perm <= 0) return 0;
+    LsPermArgs pa;
+    pa.seed_mixed = ss_mix64(seed);
+    pa.first = first_perm;
+    pa.n_perm = n_perm;
+    ss_feistel_widths(n, &pa.wl, &pa.wr);
+    const int blocks = std::min(LS_CAP_BLOCKS, ceil_div(n, 4));
+    hipLaunchKernelGGL(ls_cond_null_kernel, dim3(blocks), dim3(256), 0, st, V, ldv, n, K, deg_out, nbr_sum, pa, count_ge, count_le,
+                       sum_d, sumsq_d);
+    FDX_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_conditional_indices(unsigned long long seed, long long r, int spot, int n, int count, int* out, hipStream_t st) {
+    if (count <= 0) return 0;
+    int wl, wr;
+    ss_feistel_widths(n, &wl, &wr);
+    hipLaunchKernelGGL(ls_cond_indices_kernel, dim3(1), dim3(64), 0, st, ls_cond_key(ss_perm_key(ss_mix64(seed), r), spot), spot, n,
+                       count, wl, wr, out);
+    FDX_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // namespace fdx

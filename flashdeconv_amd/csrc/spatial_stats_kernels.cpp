@@ -26,9 +26,10 @@
 //
 // pi_r is a keyed bijection of [0, n): an unbalanced Feistel network of 8 rounds on b = max(2, bit_length(n - 1)) bits (left half
 // b / 2 bits, right half the rest, the widths swap every round), the round function the splitmix64 finaliser, values >= n walked
-// along their cycle until they fall below n.  utils/spatial_stats.py:permutation_indices is its definition.
+// along their cycle until they fall below n (perm_device.h).  utils/spatial_stats.py:permutation_indices is its definition.
 #include "fdx_internal.h"
 #include "fdx_kernels.h"
+#include "perm_device.h"
 
 #include <algorithm>
 
@@ -48,16 +49,6 @@ __device__ __forceinline__ void wave_lds_handoff() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// the splitmix64 finaliser
-__host__ __device__ __forceinline__ unsigned long long ss_mix64(unsigned long long x) {
-    x ^= x >> 30;
-    x *= 0xbf58476d1ce4e5b9ULL;
-    x ^= x >> 27;
-    x *= 0x94d049bb133111ebULL;
-    x ^= x >> 31;
-    return x;
-}
-
 // what identifies the permutations of a launch: permutation r has the key mix64(seed_mixed + (r + 1) * golden)
 struct SsPermArgs {
     unsigned long long seed_mixed;   // mix64(seed)
@@ -65,31 +56,6 @@ struct SsPermArgs {
     int wl, wr;                      // widths of the Feistel halves: wl = b / 2, wr = b - wl
     long long plane_stride;          // doubles between the planes of two batch elements (K * ld)
 };
-
-__host__ __device__ __forceinline__ unsigned long long ss_perm_key(unsigned long long seed_mixed, long long r) {
-    return ss_mix64(seed_mixed + ((unsigned long long)r + 1ULL) * 0x9e3779b97f4a7c15ULL);
-}
-
-// pi(i) for i < n < 2^31: x = (L << wr) | R; a round sends (L, R) to (R, L ^ F(R)) and swaps the widths; 8 rounds restore them
-__device__ __forceinline__ int ss_permute_index(unsigned long long key, int i, int n, int wl, int wr) {
-    unsigned x = (unsigned)i;
-    do {
-        unsigned L = x >> wr, R = x & ((1u << wr) - 1u);
-        int a = wl, c = wr;
-#pragma unroll
-        for (unsigned round = 0; round < 8; ++round) {
-            const unsigned f = (unsigned)ss_mix64(key ^ (((unsigned long long)round << 32) | R)) & ((1u << a) - 1u);
-            const unsigned nr = L ^ f;
-            L = R;
-            R = nr;
-            const int t = a;
-            a = c;
-            c = t;
-        }
-        x = (L << wr) | R;
-    } while (x >= (unsigned)n);
-    return (int)x;
-}
 
 // partials[b][c] = sum of V[r][c] over block b's rows [b * rows_per_block, ...): 256 / K rows in flight per pass (consecutive
 // threads read consecutive addresses of a row), their running sums added in a fixed order at the end
@@ -450,15 +416,6 @@ int launch_spatial_stats(const SpatialStatsPlan& s, const double* V, long long l
     return observed_pass(s, V, ldv, n, K, ell, slice_off, deg, perm, Z, lag, part, out, nbr_mean, st);
 }
 
-// b = max(2, bit_length(n - 1)), split into the Feistel halves
-static void feistel_widths(long long n, int* wl, int* wr) {
-    int b = 0;
-    for (long long v = n - 1; v > 0; v >>= 1) ++b;
-    b = std::max(2, b);
-    *wl = b / 2;
-    *wr = b - b / 2;
-}
-
 SpatialPermPlan spatial_perm_plan(long long n, int K, long long n_perm, int max_batch, bool own_null) {
     SpatialPermPlan p;
     p.s = spatial_stats_plan(n, K);
@@ -511,7 +468,7 @@ int launch_spatial_perm(const SpatialPermPlan& p, const double* V, long long ldv
 
     SsPermArgs pa;
     pa.seed_mixed = ss_mix64(seed);
-    feistel_widths(n, &pa.wl, &pa.wr);
+    ss_feistel_widths(n, &pa.wl, &pa.wr);
     pa.plane_stride = (long long)p.plane_doubles;
     const size_t lds = (size_t)4 * 64 * SS_KS * sizeof(double);
     FDX_HIP(hipFuncSetAttribute((const void*)ss_centre_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -541,7 +498,7 @@ int launch_spatial_perm(const SpatialPermPlan& p, const double* V, long long ldv
 int launch_permutation_indices(unsigned long long seed, long long r, int n, int* out, hipStream_t st) {
     if (n <= 0) return 0;
     int wl, wr;
-    feistel_widths(n, &wl, &wr);
+    ss_feistel_widths(n, &wl, &wr);
     hipLaunchKernelGGL(ss_perm_indices_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, ss_perm_key(ss_mix64(seed), r), n, wl, wr,
                        out);
     FDX_CHECK_LAUNCH();

@@ -5,7 +5,7 @@ forwarding the same keyword arguments to the MI355X ``FlashDeconv``."""
 def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512, lambda_spatial="auto", rho_sparsity=0.01,
                n_hvg=2000, n_markers_per_type=50, spatial_method="knn", k_neighbors=6, radius=None, preprocess="log_cpm",
                layer_st=None, layer_ref=None, spatial_key="spatial", key_added="flashdeconv", random_state=0, copy=False,
-               spot_diagnostics=False, spatial_stats=False, n_niches=None, spatial_permutations=0):
+               spot_diagnostics=False, spatial_stats=False, n_niches=None, spatial_permutations=0, local_stats=False):
     """Writes ``.obsm[key_added]`` (proportions DataFrame), ``.obs[key_added + '_dominant']`` and
     ``.uns[key_added + '_params']``; returns the modified copy when ``copy=True``, else ``None``.  ``spot_diagnostics=True``
     (additive) also writes ``.obs[key_added + '_residual']`` (relative sketch residual per spot) and
@@ -17,7 +17,11 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
     and ``z_sim`` and ``.uns[key_added + '_colocalization_pvalue']`` holds the two-sided p value of every pair.
     ``n_niches=<int>`` (additive) also writes ``.obs[key_added + '_niche']`` (Categorical of niche indices: k-means of
     each spot's proportions beside its neighbours' mean proportions, ``FlashDeconv.get_spatial_niches``) and
-    ``.uns[key_added + '_niche_composition']`` (DataFrame, niche x cell type: the mean proportions of each niche's spots)."""
+    ``.uns[key_added + '_niche_composition']`` (DataFrame, niche x cell type: the mean proportions of each niche's spots).
+    ``local_stats=True`` (additive) also writes ``.obsm[key_added + '_local_moran']`` (local Moran's I) and
+    ``.obsm[key_added + '_hotspot']`` (Getis-Ord Gi*), DataFrames over ``obs_names`` x cell types
+    (``FlashDeconv.get_local_spatial_statistics``); with ``spatial_permutations=R`` > 0 beside it also
+    ``.obsm[key_added + '_hotspot_pvalue']``, the two-sided conditional-permutation p value of every spot and cell type."""
     from ..core.deconv import FlashDeconv
     from ..io import prepare_data, result_to_anndata
 
@@ -72,4 +76,14 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
         adata.uns[f"{key_added}_niche_composition"] = pd.DataFrame(niches["composition"], index=index,
                                                                    columns=[str(t) for t in names])
         adata.uns[f"{key_added}_params"]["n_niches"] = int(n_niches)
+    if local_stats:
+        import pandas as pd
+        local = model.get_local_spatial_statistics(n_permutations=spatial_permutations)
+        types = [str(t) for t in names]
+        adata.obsm[f"{key_added}_local_moran"] = pd.DataFrame(local["local_i"], index=adata.obs_names, columns=types)
+        adata.obsm[f"{key_added}_hotspot"] = pd.DataFrame(local["gi_star"], index=adata.obs_names, columns=types)
+        if spatial_permutations:
+            adata.obsm[f"{key_added}_hotspot_pvalue"] = pd.DataFrame(local["p_value"], index=adata.obs_names, columns=types)
+            adata.uns[f"{key_added}_params"]["spatial_permutations"] = int(spatial_permutations)
+        adata.uns[f"{key_added}_params"]["local_stats"] = True
     return adata if copy else None

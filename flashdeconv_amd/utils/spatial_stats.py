@@ -114,11 +114,17 @@ def permutation_indices(seed, r, n):
     seed, r, n = int(seed), int(r), int(n)
     if r < 0 or n < 0 or n >= (1 << 31) - 128:
         raise ValueError(f"r must not be negative and n must be in [0, 2^31 - 128), got r = {r}, n = {n}")
+    return _keyed_bijection(_mix64_int(_mix64_int(seed) + (r + 1) * _GOLDEN), np.arange(n, dtype=np.uint64), n)
+
+
+def _keyed_bijection(key, x, n):
+    """``F_key(x)`` for a uint64 array ``x`` of values below ``n``: the Feistel network of ``permutation_indices`` under ``key``
+    (a Python int below 2^64), cycle-walked below ``n``; int64."""
     b = max(2, (n - 1).bit_length()) if n > 0 else 2
     wl0, wr0 = b // 2, b - b // 2
-    key = np.uint64(_mix64_int(_mix64_int(seed) + (r + 1) * _GOLDEN))
-    out = np.arange(n, dtype=np.uint64)
-    todo = np.arange(n)
+    key = np.uint64(key)
+    out = np.array(x, dtype=np.uint64)
+    todo = np.arange(out.size)
     with np.errstate(over="ignore"):
         while todo.size:
             x = out[todo]

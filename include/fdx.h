@@ -603,6 +603,28 @@ int fdx_spatial_perm_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, i
 /* out_dev[i] (n int32, DEVICE) = pi_r(i) of `seed` for i < n, by the device function the kernels of fdx_spatial_perm_dev use.
  * Asynchronous on `stream`. */
 int fdx_permutation_indices_dev(uint64_t seed, int64_t r, int64_t n, int32_t* out_dev, void* stream);
+/* Local indicators of spatial association over a whole graph (additive, not in the reference): per spot and column the observed
+ * neighbour sum and its conditional-permutation null.  V_dev as for fdx_spatial_autocorr_dev.  DEVICE outputs, rows in the
+ * caller's spot order, overwritten:
+ *   nbr_sum_dev (n, K) float64 = S_ia = sum_{j in N(i)} V_ja          deg_dev (n) int32 = deg_i
+ * and over conditional permutations r = first_perm .. first_perm + n_perm - 1 of `seed`, in which spot i keeps its value and its
+ * neighbours are replaced by the deg_i spots flashdeconv_amd/utils/local_stats.py:conditional_indices(seed, r, i, n, deg_i)
+ * defines (the bijection of fdx_permutation_indices_dev under the key mix64(key_r + (i + 1) * 0x9e3779b97f4a7c15), the spot
+ * itself skipped), S_ia,r their sum added in slot order:
+ *   count_ge_dev / count_le_dev (n, K) int32 = #{r: S_r >= S} / #{r: S_r <= S}
+ *   sum_d_dev / sumsq_d_dev (n, K) float64   = sum_r d and sum_r d^2, d = S_r - S
+ * These four may be NULL if and only if n_perm == 0; n_perm < 2^31.  To HOST memory mean_out, m2_out (K) and counts_out =
+ * { n, W, sum_i deg_i^2 }: bit for bit what fdx_spatial_autocorr_dev returns.  No floating-point atomics, no scratch memory, any
+ * degree; the counts and sums do not depend on a launch parameter, and those of split calls add up (exactly where the sums are
+ * exact).  One host synchronisation.  Refused: null pointers, K < 1, ldv < K, negative counts, a shard's local graph, a graph
+ * without device tables, n >= 2^31 - 128. */
+int fdx_local_stats_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, int32_t K, uint64_t seed, int64_t first_perm,
+                        int64_t n_perm, double* nbr_sum_dev, int32_t* deg_dev, int32_t* count_ge_dev, int32_t* count_le_dev,
+                        double* sum_d_dev, double* sumsq_d_dev, double* mean_out, double* m2_out, int64_t* counts_out,
+                        void* stream);
+/* out_dev[t] (count int32, DEVICE) = the t-th spot conditional permutation r of `seed` draws for `spot` among n, by the device
+ * function the kernel of fdx_local_stats_dev uses; 0 <= spot < n, 0 <= count <= n - 1.  Asynchronous on `stream`. */
+int fdx_conditional_indices_dev(uint64_t seed, int64_t r, int64_t spot, int64_t n, int64_t count, int32_t* out_dev, void* stream);
 /* k-means of per-spot feature rows (spatial niches; additive, not in the reference).  F_dev: (n, D) row-major DEVICE matrix with
  * row stride ldf >= D (columns D .. ldf - 1 are never read); centres: (C, D) row-major, contiguous, 1 <= C <= 64.  Everywhere
  * d2(i, c) = sum_k (F_ik - M_ck)^2 with the difference formed first, accumulated by fma in ascending k.  float64 throughout, no
