@@ -120,6 +120,7 @@ SIGNATURES = {
     "fdx_graph_from_knn_lists_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, ctypes.POINTER(c_void_p)]),
     "fdx_leverage_begin": (c_int, [p_double, c_i32, c_i32, c_double, ctypes.POINTER(c_void_p)]),
     "fdx_leverage_begin_opt": (c_int, [p_double, c_i32, c_i32, c_double, c_i32, ctypes.POINTER(c_void_p)]),
+    "fdx_leverage_scores_route": (c_int, [p_double, c_i32, c_i32, c_double, c_i32, p_double, p_i32]),
     "fdx_leverage_end": (c_int, [c_void_p, p_double]),
     "fdx_leverage_end_keep": (c_int, [c_void_p, p_double, ctypes.POINTER(c_void_p)]),
     "fdx_fit_dev": (c_int, [c_void_p, c_i32, c_i64, c_i32, c_i64, p_double, c_i32, p_i32, p_double, p_double, c_void_p,

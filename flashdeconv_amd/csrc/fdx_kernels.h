@@ -225,8 +225,16 @@ namespace fdx {
 size_t leverage_scratch_doubles(int K, int G);
 // route: the Jacobi SVD passes, or the Cholesky-QR route (no SVD; sweeps[7] = 1 when it stands, 2 when its pivots refused
 // the matrix and the caller must run the SVD route)
-constexpr int LEV_ROUTE_SVD = 0, LEV_ROUTE_QR = 1;
-bool leverage_qr_applies(int K, int G);
+// LEV_ROUTE_SVD takes the streaming passes for 2 <= K <= 64 and the one-workgroup kernel otherwise; LEV_ROUTE_SVD_STREAM and
+// LEV_ROUTE_SVD_ONE_WG name one of the two (FDX_LEV_ONE_WG maps onto the latter in fit.cpp: launch_leverage reads no switch)
+constexpr int LEV_ROUTE_SVD = 0, LEV_ROUTE_QR = 1, LEV_ROUTE_SVD_STREAM = 2, LEV_ROUTE_SVD_ONE_WG = 3;
+constexpr int LEV_ONE_WG_MAX_SWEEPS = 60;   // the one-workgroup kernel reports its sweeps in sweeps[0]: fewer than this = converged
+bool leverage_qr_applies(int K, int G);     // by shape alone
+inline bool leverage_stream_applies(int K) { return K >= 2 && K <= 64; }
+// which Jacobi form launch_leverage runs for a route other than LEV_ROUTE_QR
+inline int leverage_svd_form(int K, int route) {
+    return route != LEV_ROUTE_SVD_ONE_WG && leverage_stream_applies(K) ? LEV_ROUTE_SVD_STREAM : LEV_ROUTE_SVD_ONE_WG;
+}
 int launch_leverage(const double* X, int K, int G, double reg, double* work, double* sig2, double* lev, int* sweeps,
                     double* scratch, hipStream_t st, int route = LEV_ROUTE_SVD);
 }  // namespace fdx

@@ -90,6 +90,7 @@ struct fdx_leverage_job {
     std::shared_ptr<LevEntry> hit;               // a cached X: the job was complete when begin returned, nothing above is in use
     bool cacheable = false;                      // a miss: end inserts the entry (route0: the route the key names)
     int route0 = LEV_ROUTE_SVD;
+    bool fallback = true;                        // a refusal of the Cholesky-QR route is answered with the Jacobi SVD passes
 };
 
 namespace fdx {
@@ -118,16 +119,29 @@ extern "C" int fdx_leverage_begin(const double* X, int32_t K, int32_t G, double 
 
 // queue_async = 0: the launches are queued by the calling thread (a caller that collects the scores at once gains nothing from the
 // helper thread - and in the gene-selection flow of FlashDeconv.fit the hand-over measurably cost ~3 ms of wait on some boxes)
+static int leverage_begin_impl(const double* X, int32_t K, int32_t G, double regularization, int32_t queue_async, int route,
+                               bool use_cache, fdx_leverage_job** out);
 extern "C" int fdx_leverage_begin_opt(const double* X, int32_t K, int32_t G, double regularization, int32_t queue_async,
                                       fdx_leverage_job** out) {
+    return leverage_begin_impl(X, K, G, regularization, queue_async, -1, true, out);
+}
+// route < 0: the route a fit starts on (Cholesky-QR where it applies; FDX_LEV_ONE_WG: the one-workgroup Jacobi kernel), with the
+// fallback; a LEV_ROUTE_* value: that route and nothing else (fdx_leverage_scores_route)
+static int leverage_begin_impl(const double* X, int32_t K, int32_t G, double regularization, int32_t queue_async, int route,
+                               bool use_cache, fdx_leverage_job** out) {
     FDX_REQUIRE(X && out && K > 0 && G > 0, "fdx_leverage_begin: bad arguments");
     *out = nullptr;
     auto* job = new fdx_leverage_job();
     job->K = K;
     job->G = G;
     job->reg = regularization;
-    job->route0 = leverage_qr_applies(K, G) ? LEV_ROUTE_QR : LEV_ROUTE_SVD;
-    if (!fdx::env("FDX_NO_PLAN_CACHE")) {
+    if (route < 0)
+        job->route0 = fdx::env("FDX_LEV_ONE_WG") ? LEV_ROUTE_SVD_ONE_WG : leverage_qr_applies(K, G) ? LEV_ROUTE_QR : LEV_ROUTE_SVD;
+    else {
+        job->route0 = route;
+        job->fallback = false;
+    }
+    if (use_cache && !fdx::env("FDX_NO_PLAN_CACHE")) {
         XCacheKey key;
         key.K = K; key.G = G; key.reg = regularization; key.route = job->route0; key.X = X;
         job->hit = lev_cache().find(key);
@@ -177,14 +191,14 @@ extern "C" int fdx_leverage_begin_opt(const double* X, int32_t K, int32_t G, dou
     return 0;
 }
 
-static int leverage_end_impl(fdx_leverage_job* job, double* lev_out, double** x_dev_out);
+static int leverage_end_impl(fdx_leverage_job* job, double* lev_out, double** x_dev_out, int32_t* info = nullptr);
 extern "C" int fdx_leverage_end(fdx_leverage_job* job, double* lev_out) { return leverage_end_impl(job, lev_out, nullptr); }
 extern "C" int fdx_leverage_end_keep(fdx_leverage_job* job, double* lev_out, double** x_dev_out) {
     FDX_REQUIRE(x_dev_out != nullptr, "fdx_leverage_end_keep: null output");
     *x_dev_out = nullptr;
     return leverage_end_impl(job, lev_out, x_dev_out);
 }
-static int leverage_end_impl(fdx_leverage_job* job, double* lev_out, double** x_dev_out) {
+static int leverage_end_impl(fdx_leverage_job* job, double* lev_out, double** x_dev_out, int32_t* info) {
     FDX_REQUIRE(job != nullptr, "fdx_leverage_end: null job");
     if (job->hit) {
         std::unique_ptr<fdx_leverage_job> owner(job);
@@ -238,7 +252,8 @@ static int leverage_end_impl(fdx_leverage_job* job, double* lev_out, double** x_
         if (!rc) rc = run();
         e = hipStreamSynchronize(job->st);          // always drain before the buffers go back to the pool
     }
-    if (!rc && e == hipSuccess && job->route == LEV_ROUTE_QR && dbg[7] != 1) {
+    const bool refused = !rc && e == hipSuccess && job->route == LEV_ROUTE_QR && dbg[7] != 1;
+    if (refused && job->fallback) {
         // the Cholesky-QR route refused the matrix (rank-deficient or cond above ~3e4): the Jacobi SVD passes, as before
         PoolStream pool_stream(job->st);
         job->route = LEV_ROUTE_SVD;
@@ -255,6 +270,13 @@ static int leverage_end_impl(fdx_leverage_job* job, double* lev_out, double** x_
         *x_dev_out = job->dX.as<double>();
         job->dX.p = nullptr;
         job->dX.bytes = job->dX.cap = 0;
+    }
+    if (!rc && e == hipSuccess && info) {
+        // {route that produced the scores (fdx.h numbering), refused, passes or sweeps, done / converged, fell back, 0, 0, 0}
+        const int form = job->route == LEV_ROUTE_QR ? LEV_ROUTE_QR : leverage_svd_form(job->K, job->route);
+        const int settled = form == LEV_ROUTE_QR ? dbg[7] == 1 : form == LEV_ROUTE_SVD_STREAM ? dbg[6] != 0 : dbg[0] < LEV_ONE_WG_MAX_SWEEPS;
+        const int32_t v[8] = {form, refused ? 1 : 0, dbg[0], settled, refused && job->fallback ? 1 : 0, 0, 0, 0};
+        std::memcpy(info, v, sizeof(v));
     }
     if (!rc && e == hipSuccess && job->cacheable && job->hX) {
         // the scores have arrived and the route has settled
@@ -278,6 +300,17 @@ extern "C" int fdx_leverage_scores(const double* X, int32_t K, int32_t G, double
     fdx_leverage_job* job = nullptr;
     FDX_TRY(fdx_leverage_begin(X, K, G, regularization, &job));
     return fdx_leverage_end(job, lev_out);
+}
+
+extern "C" int fdx_leverage_scores_route(const double* X, int32_t K, int32_t G, double regularization, int32_t route, double* lev_out,
+                                         int32_t* info) {
+    FDX_REQUIRE(X && lev_out && info && K > 0 && G > 0, "fdx_leverage_scores_route: bad arguments");
+    FDX_REQUIRE(route >= 0 && route <= 3, "fdx_leverage_scores_route: route must be 0 .. 3");
+    FDX_REQUIRE(route != LEV_ROUTE_QR || leverage_qr_applies(K, G), "fdx_leverage_scores_route: the Cholesky-QR route needs 2 <= K <= 272");
+    FDX_REQUIRE(route != LEV_ROUTE_SVD_STREAM || leverage_stream_applies(K), "fdx_leverage_scores_route: the streaming Jacobi passes need 2 <= K <= 64");
+    fdx_leverage_job* job = nullptr;
+    FDX_TRY(leverage_begin_impl(X, K, G, regularization, 0, route == 0 ? -1 : route, false, &job));
+    return leverage_end_impl(job, lev_out, nullptr, info);
 }
 
 extern "C" int fdx_column_sums_dev(const void* Y_dev, int32_t dtype, int64_t n, int32_t G, int64_t ldy,

@@ -25,6 +25,15 @@
 
 namespace fdx {
 
+// A column whose squared norm is below this fraction of the matrix's squared Frobenius norm (1e-14 in norm) is rounding noise:
+// the direction that centring annihilates, and every further one of a rank-deficient matrix.  Such columns are not rotated
+// (against each other in the streaming passes, whose criterion has an absolute floor for the rest; at all in the one-workgroup
+// kernel, whose criterion is purely relative: it never settles on noise, and once a column is 1e-150 of its partner the
+// rotation rounds to the identity and is still counted - rank-deficient signatures ran all 60 sweeps / all 4 passes and were
+// reported as not converged) and carry no weight in the scores (the reference's s^2 / (s^2 + reg) of a noise s is
+// (u |X|)^2 G K / reg - 4e-12 of every score for signatures of order 1e5 at reg = 1e-6; the exact value is 0).
+constexpr double LEV_NULL_TOL = 1e-28;
+
 __device__ __forceinline__ double wsum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -42,14 +51,24 @@ __global__ __launch_bounds__(512) void leverage_jacobi_kernel(const double* __re
     __shared__ double s_red[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // centre over cell types (genes.py:264)
+    double f2 = 0.0;
     for (int g = tid; g < G; g += 512) {
         double m = 0.0;
         for (int k = 0; k < K; ++k) m += X[(size_t)k * G + g];
         m /= (double)K;
-        for (int k = 0; k < K; ++k) A[(size_t)k * G + g] = X[(size_t)k * G + g] - m;
+        for (int k = 0; k < K; ++k) {
+            const double d = X[(size_t)k * G + g] - m;
+            A[(size_t)k * G + g] = d;
+            f2 = fma(d, d, f2);
+        }
     }
+    f2 = wsum(f2);
+    if (lane == 0) s_red[8 + wave] = f2;
     long long t_dbg0 = wall_clock64();
     __syncthreads();
+    double null2 = 0.0;                   // LEV_NULL_TOL x |A|_F^2 (rotations keep the Frobenius norm)
+    for (int w = 0; w < 8; ++w) null2 += s_red[8 + w];
+    null2 *= LEV_NULL_TOL;
     // ---- preconditioning (K <= 64): rotate the columns by the eigenvectors of the K x K Gram matrix, A <- A V.
     // V is a product of plane rotations (orthogonal to machine precision), so A V has exactly A's singular values and
     // left vectors, but nearly orthogonal columns: the one-sided sweeps below then converge in 2-3 instead of ~13.
@@ -93,7 +112,7 @@ __global__ __launch_bounds__(512) void leverage_jacobi_kernel(const double* __re
                         double c = 1.0, sn = 0.0;
                         if (q < K) {
                             const double cpq = C[p][q], cpp = C[p][p], cqq = C[q][q];
-                            if (fabs(cpq) > 1e-15 * sqrt(fabs(cpp * cqq)) && cpq != 0.0) {
+                            if (fabs(cpq) > 1e-15 * sqrt(fabs(cpp * cqq)) && cpq != 0.0 && fmin(fabs(cpp), fabs(cqq)) > null2) {
                                 const double theta = (cqq - cpp) / (2.0 * cpq);
                                 const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(1.0 + theta * theta));
                                 c = 1.0 / sqrt(1.0 + t * t);
@@ -158,7 +177,7 @@ __global__ __launch_bounds__(512) void leverage_jacobi_kernel(const double* __re
     const int Kp = (K + 1) & ~1;          // even number of players (one dummy if K is odd)
     const int n_pairs = Kp / 2, n_rounds = Kp - 1;
     int sweep = 0;
-    for (; sweep < 60; ++sweep) {
+    for (; sweep < LEV_ONE_WG_MAX_SWEEPS; ++sweep) {
         if (tid == 0) s_rot = 0;
         __syncthreads();
         for (int r = 0; r < n_rounds; ++r) {
@@ -189,7 +208,7 @@ __global__ __launch_bounds__(512) void leverage_jacobi_kernel(const double* __re
                         gamma = fma(x[u], y[u], gamma);
                     }
                     alpha = wsum(alpha); beta = wsum(beta); gamma = wsum(gamma);
-                    if (fabs(gamma) > 1e-15 * sqrt(alpha * beta) && gamma != 0.0) {
+                    if (fabs(gamma) > 1e-15 * sqrt(alpha * beta) && gamma != 0.0 && fmin(alpha, beta) > null2) {
                         const double zeta = (beta - alpha) / (2.0 * gamma);
                         const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
                         const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
@@ -222,7 +241,7 @@ __global__ __launch_bounds__(512) void leverage_jacobi_kernel(const double* __re
                     }
                 }
                 alpha = wsum(alpha); beta = wsum(beta); gamma = wsum(gamma);
-                if (fabs(gamma) > 1e-15 * sqrt(alpha * beta) && gamma != 0.0) {
+                if (fabs(gamma) > 1e-15 * sqrt(alpha * beta) && gamma != 0.0 && fmin(alpha, beta) > null2) {
                     const double zeta = (beta - alpha) / (2.0 * gamma);
                     const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
                     const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
@@ -265,7 +284,10 @@ __global__ __launch_bounds__(512) void leverage_jacobi_kernel(const double* __re
     double part = 0.0;
     for (int g = tid; g < G; g += 512) {
         double l = 0.0;
-        for (int j = 0; j < K; ++j) { const double x = A[(size_t)j * G + g]; l += x * x / (sig2[j] + reg); }
+        for (int j = 0; j < K; ++j) {
+            const double x = A[(size_t)j * G + g];
+            if (sig2[j] > null2) l += x * x / (sig2[j] + reg);
+        }
         lev[g] = l;
         part += l;
     }
@@ -362,6 +384,10 @@ __global__ __launch_bounds__(512) void lev_eigen_kernel(const double* __restrict
     const int Kq = (K + 1) & ~1, npair = Kq / 2, M = Kq - 1;
     int cur = 0;
     const int j = tid & 63, w8 = tid >> 6;
+    __syncthreads();
+    double null2 = 0.0;                                                     // LEV_NULL_TOL x |A|_F^2 = the trace of C
+    for (int i = 0; i < K; ++i) null2 += cs[128 + i];
+    null2 *= LEV_NULL_TOL;
     for (int sw = 0; sw < 12; ++sw) {
         if (tid == 0) s_rot = 0;
         __syncthreads();
@@ -388,7 +414,8 @@ __global__ __launch_bounds__(512) void lev_eigen_kernel(const double* __restrict
                     // First sweep of a pass: C is fresh from the columns, accurate to a few eps - floor 1e-15.  Later sweeps
                     // carry the rounding of ~K updates per entry - floor 1e-13.
                     const double big = fmax(fabs(cpp), fabs(cqq));
-                    if (cpq * cpq > 1e-28 * fabs(cpp * cqq) && fabs(cpq) > (sw == 0 ? 1e-15 : 1e-13) * big) {
+                    // A pair of noise columns (both below LEV_NULL_TOL of the whole) is left alone.
+                    if (cpq * cpq > 1e-28 * fabs(cpp * cqq) && fabs(cpq) > (sw == 0 ? 1e-15 : 1e-13) * big && big > null2) {
                         const double theta = (cqq - cpp) / (2.0 * cpq);
                         const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(1.0 + theta * theta));
                         c = 1.0 / sqrt(1.0 + t * t);
@@ -473,7 +500,7 @@ __global__ __launch_bounds__(256) void lev_rotate_kernel(double* __restrict__ A,
     }
 }
 
-// not converged within LEV_PASSES (never seen): take the column norms of the last pass's Gram diagonal anyway
+// not converged within LEV_PASSES: take the column norms of the last pass's Gram diagonal anyway
 __global__ __launch_bounds__(64) void lev_diag_kernel(const double* __restrict__ part, int n_blocks, int K,
                                                       double* __restrict__ sig2, const int* __restrict__ done) {
     if (*done) return;
@@ -490,7 +517,13 @@ __global__ __launch_bounds__(256) void lev_scores_kernel(const double* __restric
     const int g = blockIdx.x * 256 + threadIdx.x;
     double l = 0.0;
     if (g < G) {
-        for (int j = 0; j < K; ++j) { const double x = A[(size_t)j * G + g]; l += x * x / (sig2[j] + reg); }
+        double null2 = 0.0;
+        for (int j = 0; j < K; ++j) null2 += sig2[j];
+        null2 *= LEV_NULL_TOL;
+        for (int j = 0; j < K; ++j) {
+            const double x = A[(size_t)j * G + g];
+            if (sig2[j] > null2) l += x * x / (sig2[j] + reg);
+        }
         lev[g] = l;
     }
     sh[threadIdx.x] = l;
@@ -968,7 +1001,7 @@ static int launch_leverage_qr_big(const double* X, int K, int G, double reg, dou
 }
 
 bool leverage_qr_applies(int K, int G) {
-    return K >= 2 && K <= LEV_BIG_MAX_K && G >= 1 && !fdx::env("FDX_LEV_ONE_WG");
+    return K >= 2 && K <= LEV_BIG_MAX_K && G >= 1;
 }
 
 size_t leverage_scratch_doubles(int K, int G) {
@@ -1013,7 +1046,11 @@ int launch_leverage(const double* X, int K, int G, double reg, double* work, dou
         if (K > 128) return launch_leverage_qr_big(X, K, G, reg, lev, sweeps, scratch, st);
         return launch_leverage_qr(X, K, G, reg, work, lev, sweeps, scratch, st);
     }
-    if (K <= 64 && K >= 2 && scratch && !fdx::env("FDX_LEV_ONE_WG"))
+    if (route != LEV_ROUTE_SVD && route != LEV_ROUTE_SVD_STREAM && route != LEV_ROUTE_SVD_ONE_WG)
+        return fail(FDX_ERR_INVALID, "leverage: unknown route");
+    if (route == LEV_ROUTE_SVD_STREAM && (!leverage_stream_applies(K) || !scratch))
+        return fail(FDX_ERR_INVALID, "leverage: the streaming Jacobi passes need 2 <= K <= 64");
+    if (leverage_svd_form(K, route) == LEV_ROUTE_SVD_STREAM && scratch)
         return launch_leverage_multi(X, K, G, reg, work, sig2, lev, sweeps, scratch, st);
     constexpr size_t kLevLds = (2 * 64 * 65 + 64) * sizeof(double);   // Gram matrix, rotations, per-round (c, s) pairs
     FDX_HIP(hipFuncSetAttribute((const void*)leverage_jacobi_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLevLds));

@@ -162,6 +162,17 @@ int fdx_leverage_end_keep(fdx_leverage_job* job, double* lev_out, double** x_dev
  * caller returns at once and has ~75 us more for its own launches: fdx_leverage_begin does this); 0 - the calling thread (for a caller
  * that collects the scores right away). */
 int fdx_leverage_begin_opt(const double* X, int32_t K, int32_t G, double regularization, int32_t queue_async, fdx_leverage_job** job);
+/* fdx_leverage_scores on a chosen kernel route (for tests and measurements; neither reads nor fills the content cache):
+ *   0  what fdx_leverage_begin + fdx_leverage_end do: Cholesky-QR where it applies, the Jacobi SVD when it refuses the matrix
+ *   1  Cholesky-QR alone (2 <= K <= 272); when it refuses, info says so and lev_out is unspecified
+ *   2  the streaming Jacobi passes (2 <= K <= 64)
+ *   3  the one-workgroup Jacobi kernel (any K)
+ * A route that does not apply to K is FDX_ERR_INVALID.  info (8 ints): [0] the route (1, 2 or 3) that produced the scores,
+ * [1] 1 when Cholesky-QR refused the matrix, [2] Jacobi passes (route 2) or sweeps (route 3), 0 for Cholesky-QR, [3] 1 when that
+ * route finished (Cholesky-QR stood / the passes found nothing left to rotate / the sweeps converged), [4] 1 when route 0 fell back
+ * to the Jacobi SVD, [5..7] 0. */
+int fdx_leverage_scores_route(const double* X, int32_t K, int32_t G, double regularization, int32_t route, double* lev_out,
+                              int32_t* info);
 
 /* ---- spatial graph (replaces utils/graph.py:25-212 and the CSR handling of core/solver.py:363-365) ---- */
 typedef struct fdx_graph fdx_graph;
