@@ -675,6 +675,19 @@ class FlashDeconv:
                                         n_permutations=n_permutations,
                                         random_state=self.random_state if random_state is None else random_state)
 
+    def get_spatial_correlogram(self, coords, radii=None, n_bands=10, what="proportions"):
+        """Over what range cell types are clustered and co-localised (additive, not in the reference): Moran's I per cell type and
+        the K x K bivariate Moran matrix in every distance band of ``radii`` (None: ``n_bands`` multiples of the grid radius) -
+        ``utils.correlogram.spatial_correlogram`` on ``proportions_`` (``what="proportions"``) or ``beta_``
+        (``what="abundances"``).  The model does not keep the coordinates: pass the ones the fit was given.  Works for both
+        ``output`` kinds of ``fit``."""
+        self._require_fitted()
+        if what not in ("proportions", "abundances"):
+            raise ValueError(f"Unknown what: {what}. Choose from 'proportions', 'abundances'.")
+        from ..utils.correlogram import spatial_correlogram
+        return spatial_correlogram(self.proportions_ if what == "proportions" else self.beta_, coords, radii=radii,
+                                   n_bands=n_bands)
+
     def get_spatial_niches(self, n_niches, what="proportions", features="both", **kw):
         """Groups the spots into ``n_niches`` spatial niches (tissue domains) by k-means of their composition, of their
         neighbourhood's composition over the graph the fit used, or of both (additive, not in the reference):

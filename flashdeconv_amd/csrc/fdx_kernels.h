@@ -148,7 +148,7 @@ int launch_spatial_stats(const SpatialStatsPlan& s, const double* V, long long l
 // budget of 1 GiB holds, 512 at the most, capped by max_batch (0: no cap) and n_perm, one at the least - and its buffers.
 struct SpatialPermPlan {
     SpatialStatsPlan s;
-    int batch, m4_blocks;
+    int batch;
     size_t plane_doubles;        // K * ld: the Z (and lag) planes of one batch element
     size_t cross_part_doubles;   // cross partials of one batch element
     size_t part_doubles;         // partials block: the observed pass's or the batch's cross partials, whichever is larger
@@ -164,6 +164,32 @@ int launch_spatial_perm(const SpatialPermPlan& p, const double* V, long long ldv
                         long long n_perm, double* null_dev, double* scratch, double* out, hipStream_t st);
 // out[i] = pi_r(i), i < n: the permutation the kernels above apply
 int launch_permutation_indices(unsigned long long seed, long long r, int n, int* out, hipStream_t st);
+
+// What correlogram_kernels.cpp takes from the kernels above (they stay in spatial_stats_kernels.cpp).
+size_t spatial_scratch_budget_bytes();       // the permutation batches' scratch budget (1 GiB)
+// column sums -> mean, centre -> Z (K, s.ld) in the order `perm` gives (null: the caller's) and m2, m4 (null: not computed) from Z;
+// part: s.partials_doubles doubles.  mean, m2, m4 on the device.
+int launch_spatial_moments(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* perm, double* Z,
+                           double* part, double* mean, double* m2, double* m4, hipStream_t st);
+// C[j] (K, K) = Z' lag_j for j < batch, lag_j the planes lag + j * lag_stride, Z the same for every j; part: batch *
+// s.cross_blocks * K * K doubles.  The sums are the cross kernel's and the fixed-order reduction's of the other entries.
+int launch_spatial_cross_batch(const SpatialStatsPlan& s, const double* Z, const double* lag, long long lag_stride, int batch, int K,
+                               double* part, double* C, hipStream_t st);
+// out[i] = partials[0][i] + partials[1][i] + ... over nparts rows of `width` int64
+int launch_reduce_i64(const long long* partials, int nparts, long long width, long long* out, hipStream_t st);
+
+// ---- correlogram_kernels.cpp
+// Sums of the spatial correlogram (fdx_spatial_correlogram_dev): ordered pairs within radii[B - 1], by distance band.
+struct CorrelogramPlan {
+    SpatialStatsPlan s;
+    int bands_per_pass;          // bands whose lag planes are in flight at once: from the scratch budget, capped by max_bands_per_pass
+    int kc;                      // columns per walk of the candidates: what the band accumulators leave room for in LDS
+    int walk_blocks;             // workgroups of the band-lag kernel (one wave each), a function of n
+    size_t lds_bytes;
+    size_t part_doubles;         // partials: the moments', the chunk's cross partials or the degree partials, whichever is largest
+    size_t scratch_doubles;      // [Z K planes | lag bands_per_pass * K planes | partials]
+};
+CorrelogramPlan correlogram_plan(long long n, int K, int B, int max_bands_per_pass);
 
 // ---- local_stats_kernels.cpp
 // Per-spot neighbour sums and their conditional-permutation null (fdx_local_stats_dev), behind the observed pass of

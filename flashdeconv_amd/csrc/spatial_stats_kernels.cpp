@@ -24,6 +24,9 @@
 // more grid dimension and per-batch plane offsets.  mean and m2 do not change under a permutation.  One kernel then reduces every
 // C_r in block order and one adds them to the counts and sums against C_obs in permutation order.
 //
+// The spatial correlogram (correlogram_kernels.cpp) runs the column-sum, centre, m4, cross and reduce kernels of this file on its
+// own binning and lag planes: launch_spatial_moments, launch_spatial_cross_batch and launch_reduce_i64 are what crosses.
+//
 // pi_r is a keyed bijection of [0, n): an unbalanced Feistel network of 8 rounds on b = max(2, bit_length(n - 1)) bits (left half
 // b / 2 bits, right half the rest, the widths swap every round), the round function the splitmix64 finaliser, values >= n walked
 // along their cycle until they fall below n (perm_device.h).  utils/spatial_stats.py:permutation_indices is its definition.
@@ -225,14 +228,14 @@ __global__ __launch_bounds__(256) void ss_lag_kernel(const double* __restrict__ 
 // partials[blockIdx.x][a][b] = sum over the block's 64-position chunks of Z[a][p] * lag[b][p], for the (a, b) of pair-space tile
 // blockIdx.y = tile_a * ntb + tile_b.  Thread (ta, tb) of 16 x 16 owns a in {ta, ta + 16}, b in {tb, tb + 16} of the tile: per
 // position two LDS reads of each operand (the ta reads broadcast) feed four FMAs; the row stride of 65 doubles puts the 16 lag
-// rows a half-wave reads on 16 different bank pairs.  Batch element blockIdx.z: planes batch_stride doubles further on, partials
-// gridDim.x * K * K further on.
+// rows a half-wave reads on 16 different bank pairs.  Batch element blockIdx.z: Z planes z_stride and lag planes lag_stride doubles
+// further on (z_stride 0: every element's lag against the same Z - the bands of a correlogram), partials gridDim.x * K * K further on.
 __global__ __launch_bounds__(256) void ss_cross_kernel(const double* __restrict__ Z, const double* __restrict__ lag, long long ld,
                                                        int n_chunks, int K, int ntb, double* __restrict__ partials,
-                                                       long long batch_stride) {
+                                                       long long z_stride, long long lag_stride) {
     __shared__ double zs[SS_CT][SS_CP + 1], ls[SS_CT][SS_CP + 1];
-    Z += (size_t)blockIdx.z * batch_stride;
-    lag += (size_t)blockIdx.z * batch_stride;
+    Z += (size_t)blockIdx.z * z_stride;
+    lag += (size_t)blockIdx.z * lag_stride;
     partials += (size_t)blockIdx.z * gridDim.x * K * K;
     const int a_base = (blockIdx.y / ntb) * SS_CT, b_base = (blockIdx.y % ntb) * SS_CT;
     const int ta = threadIdx.x >> 4, tb = threadIdx.x & 15;
@@ -365,22 +368,16 @@ static void launch_lag_for(const SpatialStatsPlan& s, int batch, long long batch
     else launch_lag<32>(s, batch, batch_stride, Z, ell, slice_off, deg, perm, mean, n, K, lag, nbr_mean, deg_part, st);
 }
 
-// the four passes of the observed statistics: Z and lag (K, ld) each, part s.partials_doubles
-static int observed_pass(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* ell,
-                         const int* slice_off, const int* deg, const int* perm, double* Z, double* lag, double* part, double* out,
-                         double* nbr_mean, hipStream_t st) {
-    double* mean = out;
-    double* m2 = out + K;
-    double* C = out + 2 * (size_t)K;
-    long long* counts = reinterpret_cast<long long*>(C + (size_t)K * K);
-    const size_t KK = (size_t)K * K;
+size_t spatial_scratch_budget_bytes() { return SS_PERM_SCRATCH_BYTES; }
 
+// the passes that do not look at the graph: mean, Z in the order of `perm`, m2 and (m4 != null) m4
+int launch_spatial_moments(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* perm, double* Z,
+                           double* part, double* mean, double* m2, double* m4, hipStream_t st) {
     hipLaunchKernelGGL(ss_colsum_kernel, dim3(s.colsum_blocks), dim3(256), 0, st, V, ldv, n, K, s.rows_per_block, part);
     FDX_CHECK_LAUNCH();
     hipLaunchKernelGGL(ss_reduce_kernel<double>, dim3(ceil_div(K, 256)), dim3(256), 0, st, part, s.colsum_blocks, (long long)K,
                        (double)n, mean);
     FDX_CHECK_LAUNCH();
-
     const size_t lds = ((size_t)4 * 64 * SS_KS + (size_t)4 * K) * sizeof(double);
     if (lds > 64 * 1024)
         FDX_HIP(hipFuncSetAttribute((const void*)ss_centre_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -391,6 +388,45 @@ static int observed_pass(const SpatialStatsPlan& s, const double* V, long long l
                        m2);
     FDX_CHECK_LAUNCH();
 
+    if (m4) {
+        hipLaunchKernelGGL(ss_m4_kernel, dim3(s.centre_blocks, K), dim3(256), 0, st, Z, s.ld, K, part);
+        FDX_CHECK_LAUNCH();
+        hipLaunchKernelGGL(ss_reduce_kernel<double>, dim3(ceil_div(K, 256)), dim3(256), 0, st, part, s.centre_blocks, (long long)K,
+                           1.0, m4);
+        FDX_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+int launch_spatial_cross_batch(const SpatialStatsPlan& s, const double* Z, const double* lag, long long lag_stride, int batch, int K,
+                               double* part, double* C, hipStream_t st) {
+    const long long KK = (long long)K * K;
+    hipLaunchKernelGGL(ss_cross_kernel, dim3(s.cross_blocks, s.pair_tiles_1d * s.pair_tiles_1d, batch), dim3(256), 0, st, Z, lag, s.ld,
+                       s.n_slices, K, s.pair_tiles_1d, part, 0LL, lag_stride);
+    FDX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ss_reduce_batch_kernel, dim3(ceil_div(KK, 256), batch), dim3(256), 0, st, part, s.cross_blocks, KK, C);
+    FDX_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_reduce_i64(const long long* partials, int nparts, long long width, long long* out, hipStream_t st) {
+    hipLaunchKernelGGL(ss_reduce_kernel<long long>, dim3(ceil_div(width, 256)), dim3(256), 0, st, partials, nparts, width, 1LL, out);
+    FDX_CHECK_LAUNCH();
+    return 0;
+}
+
+// the four passes of the observed statistics: Z and lag (K, ld) each, part s.partials_doubles; m4 (may be null) = sum Z^4
+static int observed_pass(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* ell,
+                         const int* slice_off, const int* deg, const int* perm, double* Z, double* lag, double* part, double* out,
+                         double* nbr_mean, double* m4, hipStream_t st) {
+    double* mean = out;
+    double* m2 = out + K;
+    double* C = out + 2 * (size_t)K;
+    long long* counts = reinterpret_cast<long long*>(C + (size_t)K * K);
+    const size_t KK = (size_t)K * K;
+
+    FDX_TRY(launch_spatial_moments(s, V, ldv, n, K, perm, Z, part, mean, m2, m4, st));
+
     long long* deg_part = reinterpret_cast<long long*>(part);
     launch_lag_for(s, 1, 0, Z, ell, slice_off, deg, perm, mean, n, K, lag, nbr_mean, deg_part, st);
     FDX_CHECK_LAUNCH();
@@ -398,7 +434,7 @@ static int observed_pass(const SpatialStatsPlan& s, const double* V, long long l
     FDX_CHECK_LAUNCH();
 
     hipLaunchKernelGGL(ss_cross_kernel, dim3(s.cross_blocks, s.pair_tiles_1d * s.pair_tiles_1d), dim3(256), 0, st, Z, lag, s.ld,
-                       s.n_slices, K, s.pair_tiles_1d, part, 0LL);
+                       s.n_slices, K, s.pair_tiles_1d, part, 0LL, 0LL);
     FDX_CHECK_LAUNCH();
     hipLaunchKernelGGL(ss_reduce_kernel<double>, dim3(ceil_div((long long)KK, 256)), dim3(256), 0, st, part, s.cross_blocks,
                        (long long)KK, 1.0, C);
@@ -413,7 +449,7 @@ int launch_spatial_stats(const SpatialStatsPlan& s, const double* V, long long l
     double* Z = scratch;
     double* lag = Z + (size_t)K * s.ld;
     double* part = lag + (size_t)K * s.ld;
-    return observed_pass(s, V, ldv, n, K, ell, slice_off, deg, perm, Z, lag, part, out, nbr_mean, st);
+    return observed_pass(s, V, ldv, n, K, ell, slice_off, deg, perm, Z, lag, part, out, nbr_mean, nullptr, st);
 }
 
 SpatialPermPlan spatial_perm_plan(long long n, int K, long long n_perm, int max_batch, bool own_null) {
@@ -429,7 +465,6 @@ SpatialPermPlan spatial_perm_plan(long long n, int K, long long n_perm, int max_
     if (max_batch > 0) B = std::min<long long>(B, max_batch);
     B = std::max<long long>(1, std::min<long long>(B, std::max<long long>(1, n_perm)));
     p.batch = (int)B;
-    p.m4_blocks = p.s.centre_blocks;
     p.part_doubles = std::max(p.s.partials_doubles, (size_t)B * p.cross_part_doubles);
     p.null_doubles = own_null ? (size_t)B * KK : 0;
     p.scratch_doubles = 2 * (size_t)B * p.plane_doubles + p.part_doubles + p.null_doubles;
@@ -456,13 +491,8 @@ int launch_spatial_perm(const SpatialPermPlan& p, const double* V, long long ldv
     double* sum_d = m4 + K + 2 * KK;
     double* sumsq_d = sum_d + KK;
 
-    // the observed statistics in batch element 0's planes, then m4 from its Z before the permutations overwrite it
-    FDX_TRY(observed_pass(s, V, ldv, n, K, ell, slice_off, deg, perm, Zall, lagall, part, out, nullptr, st));
-    hipLaunchKernelGGL(ss_m4_kernel, dim3(p.m4_blocks, K), dim3(256), 0, st, Zall, s.ld, K, part);
-    FDX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ss_reduce_kernel<double>, dim3(ceil_div(K, 256)), dim3(256), 0, st, part, p.m4_blocks, (long long)K, 1.0,
-                       m4);
-    FDX_CHECK_LAUNCH();
+    // the observed statistics in batch element 0's planes, m4 from its Z among them (the permutations overwrite it)
+    FDX_TRY(observed_pass(s, V, ldv, n, K, ell, slice_off, deg, perm, Zall, lagall, part, out, nullptr, m4, st));
     FDX_HIP(hipMemsetAsync(count_ge, 0, 4 * KK * sizeof(double), st));
     if (n_perm <= 0) return 0;
 
@@ -482,7 +512,7 @@ int launch_spatial_perm(const SpatialPermPlan& p, const double* V, long long ldv
         launch_lag_for(s, b, pa.plane_stride, Zall, ell, slice_off, deg, perm, mean, n, K, lagall, nullptr, nullptr, st);
         FDX_CHECK_LAUNCH();
         hipLaunchKernelGGL(ss_cross_kernel, dim3(s.cross_blocks, tiles, b), dim3(256), 0, st, Zall, lagall, s.ld, s.n_slices, K,
-                           s.pair_tiles_1d, part, pa.plane_stride);
+                           s.pair_tiles_1d, part, pa.plane_stride, pa.plane_stride);
         FDX_CHECK_LAUNCH();
         double* Cr = null_dev ? null_dev + (size_t)done * KK : own_null;
         hipLaunchKernelGGL(ss_reduce_batch_kernel, dim3(ceil_div((long long)KK, 256), b), dim3(256), 0, st, part, s.cross_blocks,

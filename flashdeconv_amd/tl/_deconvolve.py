@@ -5,7 +5,8 @@ forwarding the same keyword arguments to the MI355X ``FlashDeconv``."""
 def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512, lambda_spatial="auto", rho_sparsity=0.01,
                n_hvg=2000, n_markers_per_type=50, spatial_method="knn", k_neighbors=6, radius=None, preprocess="log_cpm",
                layer_st=None, layer_ref=None, spatial_key="spatial", key_added="flashdeconv", random_state=0, copy=False,
-               spot_diagnostics=False, spatial_stats=False, n_niches=None, spatial_permutations=0, local_stats=False):
+               spot_diagnostics=False, spatial_stats=False, n_niches=None, spatial_permutations=0, local_stats=False,
+               correlogram=False):
     """Writes ``.obsm[key_added]`` (proportions DataFrame), ``.obs[key_added + '_dominant']`` and
     ``.uns[key_added + '_params']``; returns the modified copy when ``copy=True``, else ``None``.  ``spot_diagnostics=True``
     (additive) also writes ``.obs[key_added + '_residual']`` (relative sketch residual per spot) and
@@ -21,9 +22,15 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
     ``local_stats=True`` (additive) also writes ``.obsm[key_added + '_local_moran']`` (local Moran's I) and
     ``.obsm[key_added + '_hotspot']`` (Getis-Ord Gi*), DataFrames over ``obs_names`` x cell types
     (``FlashDeconv.get_local_spatial_statistics``); with ``spatial_permutations=R`` > 0 beside it also
-    ``.obsm[key_added + '_hotspot_pvalue']``, the two-sided conditional-permutation p value of every spot and cell type."""
+    ``.obsm[key_added + '_hotspot_pvalue']``, the two-sided conditional-permutation p value of every spot and cell type.
+    ``correlogram`` (additive): ``True`` (ten bands of the grid radius), an int (that many bands) or a sequence (the radii) also
+    writes ``.uns[key_added + '_correlogram']``, a dict of ``radii``, ``n_pairs`` (unordered pairs per band), ``morans_i`` and
+    ``z_score`` (DataFrames, band x cell type) and ``cross`` (band x cell type x cell type): Moran's I and the co-localisation
+    matrix by distance band (``FlashDeconv.get_spatial_correlogram``)."""
     from ..core.deconv import FlashDeconv
     from ..io import prepare_data, result_to_anndata
+    from ..utils.correlogram import correlogram_request
+    correlogram_kw = correlogram_request(correlogram)          # a bad request fails here, not behind the fit
 
     adata = adata_st.copy() if copy else adata_st
     Y, X, coords, names, _ = prepare_data(adata, adata_ref, cell_type_key=cell_type_key, layer_st=layer_st,
@@ -86,4 +93,16 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
             adata.obsm[f"{key_added}_hotspot_pvalue"] = pd.DataFrame(local["p_value"], index=adata.obs_names, columns=types)
             adata.uns[f"{key_added}_params"]["spatial_permutations"] = int(spatial_permutations)
         adata.uns[f"{key_added}_params"]["local_stats"] = True
+    if correlogram_kw is not None:
+        import pandas as pd
+        cg = model.get_spatial_correlogram(coords, **correlogram_kw)
+        types = [str(t) for t in names]
+        bands = list(range(len(cg["radii"])))
+        adata.uns[f"{key_added}_correlogram"] = {
+            "radii": cg["radii"], "n_pairs": cg["n_pairs"],
+            "morans_i": pd.DataFrame(cg["morans_i"], index=bands, columns=types),
+            "z_score": pd.DataFrame(cg["z_score"], index=bands, columns=types),
+            "cross": cg["cross"]}
+        adata.uns[f"{key_added}_params"]["correlogram"] = (True if not correlogram_kw else
+                                                            correlogram_kw.get("n_bands", correlogram_kw.get("radii")))
     return adata if copy else None

@@ -633,6 +633,29 @@ int fdx_local_stats_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, in
                         int64_t n_perm, double* nbr_sum_dev, int32_t* deg_dev, int32_t* count_ge_dev, int32_t* count_le_dev,
                         double* sum_d_dev, double* sumsq_d_dev, double* mean_out, double* m2_out, int64_t* counts_out,
                         void* stream);
+/* Spatial correlogram (additive, not in the reference): the sums of fdx_spatial_autocorr_dev per distance band, in one walk over
+ * the pairs within the largest radius and with no graph built.  coords_dev: (n, dim) row-major DEVICE, 1 <= dim <= 3; V_dev as
+ * for fdx_spatial_autocorr_dev, rows in the order of coords_dev; radii: B HOST values, 0 < r_1 < ... < r_B finite, 1 <= B <= 32.
+ * With d_ij = sqrt((dx*dx + dy*dy) + dz*dz), every operation rounded, ordered pairs i != j fall into band 1 where d_ij <= r_1
+ * (coincident spots among them) and into band b where r_{b-1} < d_ij <= r_b: the union of bands 1 .. b is the adjacency of the
+ * radius graph of r_b, entry for entry.  To HOST memory: mean, m2, m4 (K; m4 may be NULL) as the other entries define them, and
+ * per band b with adjacency A_b
+ *   C (B, K, K) row-major = Z' A_b Z        W[b] = sum_i deg_{b,i}        sum_deg_sq[b] = sum_i deg_{b,i}^2
+ * degree_dev (may be NULL): (n, B) int32 DEVICE, deg_{b,i} in the caller's spot order.  The lag planes of
+ * *bands_per_pass_out (may be NULL) bands are in flight at once: what a scratch budget of 1 GiB holds, at most
+ * max_bands_per_pass when that is positive; no output depends on it.  The walk examines sum over the grid cells (edge >= r_B)
+ * of count(cell) * count(its 3^dim block) candidate pairs: that number is computed first, returned in *candidates_out (may be
+ * NULL), and a call where it exceeds max_candidates fails with FDX_ERR_INVALID before any pair is walked.  The candidates are
+ * walked once per group of columns and per chunk of bands (ceil(K / KC) * ceil(B / bands per pass) walks; KC columns fit the
+ * 16 KB of LDS accumulators of bands-per-pass bands, 16 at the most), so max_candidates = 0 stands for
+ * FDX_CORRELOGRAM_MAX_CANDIDATE_WALKS / walks: about ten seconds of walking whatever K and B are.  float64 throughout, no
+ * floating-point atomics, grids are functions of the shapes only, two calls return the same bits.  Two host synchronisations
+ * behind the binning's: the candidate count and the results. */
+#define FDX_CORRELOGRAM_MAX_CANDIDATE_WALKS 1600000000000LL   /* measured: 1.5e11 candidate walks per second at 1M x 30 x 6 */
+int fdx_spatial_correlogram_dev(const double* coords_dev, int64_t n, int32_t dim, const double* V_dev, int64_t ldv, int32_t K,
+                                const double* radii, int32_t B, int32_t max_bands_per_pass, int64_t max_candidates, double* mean,
+                                double* m2, double* m4, double* C, int64_t* W, int64_t* sum_deg_sq, int32_t* degree_dev,
+                                int32_t* bands_per_pass_out, int64_t* candidates_out, void* stream);
 /* out_dev[t] (count int32, DEVICE) = the t-th spot conditional permutation r of `seed` draws for `spot` among n, by the device
  * function the kernel of fdx_local_stats_dev uses; 0 <= spot < n, 0 <= count <= n - 1.  Asynchronous on `stream`. */
 int fdx_conditional_indices_dev(uint64_t seed, int64_t r, int64_t spot, int64_t n, int64_t count, int32_t* out_dev, void* stream);
