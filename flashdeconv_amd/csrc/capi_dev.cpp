@@ -19,8 +19,8 @@ extern "C" {
 
 // The graph depends on the coordinates, the method and k / radius and on nothing else of a fit, and one slide is fitted more than
 // once: the build is looked up by content first (graph_cache.cpp).  Hit: the entry's graph with one more holder - no binning, no
-// k-NN, no symmetrise / ELL / tile kernels, no allocations.  Miss: built as before - with the bounding box in hand if the lookup
-// had to compare - and an own copy of the coordinates queued on the way, published once the graph is complete.
+// k-NN, no symmetrise / ELL / tile kernels, no allocations and no bounding box: the compare kernel is all that runs.  Miss: built
+// as before, with an own copy of the coordinates queued on the way and published once the graph is complete.
 int fdx_graph_build_dev(const double* coords_dev, int64_t n, int32_t dim, int32_t method, int32_t k, double radius,
                         void* stream, fdx_graph** out) {
     hipStream_t st = (hipStream_t)stream;
@@ -38,12 +38,10 @@ int fdx_graph_build_dev(const double* coords_dev, int64_t n, int32_t dim, int32_
     struct BeginGuard { hipEvent_t* e; ~BeginGuard() { if (*e) (void)hipEventDestroy(*e); } } begin_guard{&begin};   // until a graph takes it
     const bool cached = n > 0 && dim >= 1 && dim <= 8 && graph_cache_enabled();
     GraphCacheKey key;
-    double box[6];
-    bool have_box = false;
     if (cached) {
         key = graph_cache_key(n, dim, method, k, radius);
         fdx_graph* hit = nullptr;
-        FDX_TRY(graph_cache_lookup(key, coords_dev, st, &hit, box, &have_box));
+        FDX_TRY(graph_cache_lookup(key, coords_dev, st, &hit));
         if (hit) {
             std::lock_guard<std::mutex> lk(hit->mu);            // re-recorded on every hit: prologue_ms keeps its meaning (build call -> sketch)
             if (hit->begin_event) (void)hipEventDestroy(hit->begin_event);
@@ -59,7 +57,6 @@ int fdx_graph_build_dev(const double* coords_dev, int64_t n, int32_t dim, int32_
     // the entry's copy of the coordinates: queued under the host's wait for the bounding box (no host time on the build's path)
     const std::function<int()> copy = [&]() -> int { return entry ? graph_cache_queue_copy(entry.get(), coords_dev, st) : 0; };
     GraphBuildHooks hooks;
-    hooks.box = have_box ? box : nullptr;
     hooks.under_wait = &copy;
     fdx_graph* g = new fdx_graph();
     g->begin_event = begin;

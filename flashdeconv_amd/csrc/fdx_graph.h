@@ -105,7 +105,7 @@ void graph_release(fdx_graph* g);                // one holder less; the last on
 // ---- graph_cache.cpp: whole graphs by content of the coordinates (FDX_NO_PLAN_CACHE bypasses, fdx_trim drops)
 bool graph_cache_enabled();
 GraphCacheKey graph_cache_key(long long n, int dim, int method, int k, double radius);
-int graph_cache_lookup(const GraphCacheKey& key, const double* d_coords, hipStream_t st, fdx_graph** out, double box[6], bool* have_box);
+int graph_cache_lookup(const GraphCacheKey& key, const double* d_coords, hipStream_t st, fdx_graph** out);
 int graph_cache_entry_new(const GraphCacheKey& key, std::shared_ptr<GraphCacheEntry>* out);
 int graph_cache_queue_copy(GraphCacheEntry* e, const double* d_coords, hipStream_t st);
 void graph_cache_publish(fdx_graph* g);          // no-op unless g carries an unpublished entry

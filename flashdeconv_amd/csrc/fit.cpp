@@ -446,49 +446,78 @@ int fit_impl(const YSource& ysrc, int64_t n, int32_t G, const double* X, int32_t
     const bool beta0_virtual = side && KP == K && K <= FDX_MAX_K_FAST && prm->max_iter > 0 && !prm->verbose && !fdx::env("FDX_NO_INIT_SWEEP");
     {
         PoolStream pool_xs(xs);
-        FDX_TRY(dB0.alloc((size_t)KP * ld * sizeof(double)));
-        FDX_TRY(dB1.alloc((size_t)KP * ld * sizeof(double)));
-        if (side) {
-            // no pad types: the uniform start vector is a constant of the first sweep and is not written (solver.cpp: beta0_virtual)
-            if (beta0_virtual) FDX_TRY(solver_zero_pad(dB0.as<double>(), ld, g->n_total, KP, xs));
-            else FDX_TRY(solver_init_beta(dB0.as<double>(), ld, g->n_total, K, xs, KP));
-            FDX_TRY(solver_zero_pad(dB1.as<double>(), ld, g->n_total, KP, xs));
-        }
         FDX_TRY(tables.build(ysrc, G, d, K, bucket, weight_y, xs, "fdx_fit_csr_dev"));
     }
     if (weight_x == weight_y) x.plan = tables.plan;   // (a CSR source has none)
     FDX_TRY(queue_x_side(&x, X, nullptr, K, KP, G, d, prm->mode_x, bucket, weight_x, nullptr, Gh, &evG, xs));
-    if (side) {
-        FDX_TRY(evInit.record(side));
-        FDX_TRY(evInit.wait_on(st));             // tables, X_sketch, XtX, beta0: all behind this one
-    }
+    // A repeated fit: the X side came from its cache (no event: nothing was queued for it) and is complete, and the Y side's plan
+    // is the one that entry was computed with, so its tables were uploaded before the entry was published.  The sketch then reads
+    // nothing that is in flight on the side stream: it is launched first, and what it does not read - the abundance buffers with
+    // their pad fills - is queued while it runs instead of ahead of it (~35 us of host path per fit).  In every other case the
+    // sketch waits for evInit as ever.  Not for a call that may stop on ties (counts still pending, or known ties): the pad fills
+    // find no free compute unit until the sketch ends, and the stopped call would wait for them where it returns at once today.
+    const bool may_stop = prm->stop_on_ties && (g->meta_pending || g->knn_ties > 0);
+    const bool sketch_first = side && !carry_in && !may_stop && !evG && x.b->published && tables.plan && tables.plan == x.plan;
     const double* XtX_dev = x.XtX(K, KP);
-
-    // ---- Y_sketch in solver order, contracted into H (K, ld) as it is produced - or a carry: the sketch -> H stage of a call
-    // that stopped on ties for these inputs (the rebuilt graph keeps the spot order)
-    if (carry_in) {
-        FDX_REQUIRE(carry_in->n == n && carry_in->ld == ld && carry_in->K == K && carry_in->KP == KP && carry_in->d == d &&
-                        carry_in->G == G && carry_in->mode_y == prm->mode_y && carry_in->y_id == ysrc.id(),
-                    "fdx_fit_dev: the carry belongs to a different problem");
-    } else {
+    const int* row_map = g->identity_order ? nullptr : g->perm.as<int>();
+    // the abundance buffers (beta0 = 1/K, core/solver.py:372, and the cleared pad rows); on the side stream everything queued there
+    // so far is behind evInit, which the caller's stream waits for
+    auto queue_solver_buffers = [&]() -> int {
+        {
+            PoolStream pool_xs(xs);
+            FDX_TRY(dB0.alloc((size_t)KP * ld * sizeof(double)));
+            FDX_TRY(dB1.alloc((size_t)KP * ld * sizeof(double)));
+            if (side) {
+                // no pad types: the uniform start vector is a constant of the first sweep and is not written (solver.cpp: beta0_virtual)
+                if (beta0_virtual) FDX_TRY(solver_zero_pad(dB0.as<double>(), ld, g->n_total, KP, xs));
+                else FDX_TRY(solver_init_beta(dB0.as<double>(), ld, g->n_total, K, xs, KP));
+                FDX_TRY(solver_zero_pad(dB1.as<double>(), ld, g->n_total, KP, xs));
+            }
+        }
+        if (side) {
+            FDX_TRY(evInit.record(side));
+            // tables, X_sketch, XtX, beta0: all behind this one.  (Behind a sketch launched first only the solve needs it, and the
+            // solve waits for it itself, below: a second barrier between the sketch and the first sweep costs the device ~7 us.)
+            if (!sketch_first) FDX_TRY(evInit.wait_on(st));
+        }
+        return 0;
+    };
+    // Y_sketch in solver order, contracted into H (K, ld) as it is produced
+    auto queue_sketch = [&]() -> int {
         FDX_TRY(dH.alloc((size_t)KP * ld * sizeof(double)));
         if (KP != K) FDX_HIP(hipMemsetAsync(dH.as<double>() + (size_t)K * ld, 0, (size_t)(KP - K) * ld * sizeof(double), st));   // pad types
         FDX_TRY(solver_zero_pad(dH.as<double>(), ld, n, K, st));   // columns of real spots are all written by the sketch -> H stage
-    }
-    FDX_TRY(dSum.alloc(sizeof(double)));
-    const int* row_map = g->identity_order ? nullptr : g->perm.as<int>();
-    trace_host("fit", "side-stream preamble queued, buffers allocated");
-    FDX_TRY(eS0.record(st));                      // the prologue (graph chain, X-side preamble) ends here
-    if (carry_in) {                               // H and the rows' squared norms as the stopped call left them, behind its event
-        FDX_TRY(carry_in->done.wait_on(st));
-        dH.take(carry_in->dH);
-        rows.dRowSq.take(carry_in->dRowSq);
-        rows.fused = carry_in->fused;
-        rows.gram_ms = carry_in->gram_ms;
-    } else {
+        FDX_TRY(eS0.record(st));                  // the prologue (graph chain, X-side preamble) ends here
         FDX_TRY(queue_rows_to_h(ysrc, tables, n, G, d, K, prm->mode_y, row_map, x.Xs(), dH.as<double>(), ld, true, &rows, st));
+        return eS1.record(st);                    // read at the end of the fit, no wait here
+    };
+    if (sketch_first) {
+        FDX_TRY(queue_sketch());
+        trace_host("fit", "sketch queued ahead of the side-stream preamble");
+        FDX_TRY(queue_solver_buffers());
+        FDX_TRY(dSum.alloc(sizeof(double)));
+    } else {
+        FDX_TRY(queue_solver_buffers());
+        // ---- ... or a carry: the sketch -> H stage of a call that stopped on ties for these inputs (the rebuilt graph keeps the
+        // spot order)
+        if (carry_in)
+            FDX_REQUIRE(carry_in->n == n && carry_in->ld == ld && carry_in->K == K && carry_in->KP == KP && carry_in->d == d &&
+                            carry_in->G == G && carry_in->mode_y == prm->mode_y && carry_in->y_id == ysrc.id(),
+                        "fdx_fit_dev: the carry belongs to a different problem");
+        FDX_TRY(dSum.alloc(sizeof(double)));
+        trace_host("fit", "side-stream preamble queued, buffers allocated");
+        if (carry_in) {                           // H and the rows' squared norms as the stopped call left them, behind its event
+            FDX_TRY(eS0.record(st));
+            FDX_TRY(carry_in->done.wait_on(st));
+            dH.take(carry_in->dH);
+            rows.dRowSq.take(carry_in->dRowSq);
+            rows.fused = carry_in->fused;
+            rows.gram_ms = carry_in->gram_ms;
+            FDX_TRY(eS1.record(st));
+        } else {
+            FDX_TRY(queue_sketch());
+        }
     }
-    FDX_TRY(eS1.record(st));                      // read at the end of the fit, no wait here
     // ---- the graph's counts (a build that was only queued has long finished behind the sketch launch).  Ties under stop_on_ties: the
     // caller wants the reference's choice among equidistant neighbours - nothing is solved on this graph, and the sketch -> H stage
     // that is already running goes to the caller as a carry for the fit on the rebuilt graph (tie-free inputs never pay for the

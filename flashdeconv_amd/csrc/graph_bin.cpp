@@ -290,61 +290,55 @@ struct BboxJob {
     }
 };
 
-// also: the cache lookup's compare kernels (graph_cache.cpp), queued behind the box kernels and ahead of the event, with the device
-// address of words 8..11 of the pinned block (zeroed here) - they and the box are read after the one wait
-static int bbox_begin(const double* d_coords, long long n, int dim, hipStream_t st, BboxJob* job, bool with_box = true,
-                      const std::function<int(long long*)>* also = nullptr) {
+static int bbox_begin(const double* d_coords, long long n, int dim, hipStream_t st, BboxJob* job) {
     job->coords = d_coords; job->n = n; job->dim = dim;
     FDX_HIP(hipGetDevice(&job->dev));
     // (256 to 16384 blocks, one to sixteen points per thread, four loads in flight or one: 33-60 us for the 16 MB of a million 2-D
     // points whatever the shape - the kernel's time is not its loop; 512 blocks measured best)
     const int nblk = (int)std::min<long long>(512, (n + 255) / 256);
-    if (with_box) FDX_TRY(job->part.alloc((size_t)nblk * 6 * sizeof(double)));
+    FDX_TRY(job->part.alloc((size_t)nblk * 6 * sizeof(double)));
     job->host = (double*)pinned_block_get();
     FDX_REQUIRE(job->host != nullptr, "graph: pinned host block");
     void* host_dev = nullptr;
     FDX_HIP(hipHostGetDevicePointer(&host_dev, job->host, 0));
     FDX_HIP(hipEventCreateWithFlags(&job->ev, hipEventDisableTiming));
-    if (with_box) {
-        hipLaunchKernelGGL(bbox_partial_kernel, dim3(nblk), dim3(256), 0, st, d_coords, n, dim, job->part.as<double>());
-        hipLaunchKernelGGL(bbox_final_kernel, dim3(1), dim3(256), 0, st, job->part.as<double>(), nblk, (double*)host_dev);
-        FDX_CHECK_LAUNCH();
-    }
-    if (also && *also) {
-        for (int j = 8; j < 12; ++j) job->host[j] = 0.0;       // (all bits zero)
-        FDX_TRY((*also)(reinterpret_cast<long long*>(host_dev) + 8));
-    }
+    hipLaunchKernelGGL(bbox_partial_kernel, dim3(nblk), dim3(256), 0, st, d_coords, n, dim, job->part.as<double>());
+    hipLaunchKernelGGL(bbox_final_kernel, dim3(1), dim3(256), 0, st, job->part.as<double>(), nblk, (double*)host_dev);
+    FDX_CHECK_LAUNCH();
     FDX_HIP(hipEventRecord(job->ev, st));
     return 0;
 }
 
-int coords_box(const double* d_coords, long long n, int dim, hipStream_t st, bool with_box, const std::function<int(long long*)>& also,
-               double box[6], long long words[4]) {
-    FDX_REQUIRE(!with_box || (dim >= 1 && dim <= 3), "graph: a bounding box takes 1 to 3 coordinates");
-    BboxJob job;
-    FDX_TRY(bbox_begin(d_coords, n, dim, st, &job, with_box, &also));
+// The cache lookup's compare kernels (graph_cache.cpp) write into a pinned block as the box kernels do, and nothing else of a
+// lookup runs on the device: a hit is decided by the flags alone, so no box is computed for it (25 us of kernels on every hit);
+// a miss computes its box in the build that follows, as a build without a candidate does.
+int flag_words(hipStream_t st, const std::function<int(long long*)>& queue, long long words[4]) {
+    BboxJob job;                                               // (its pinned block and event; no box kernels)
+    job.host = (double*)pinned_block_get();
+    FDX_REQUIRE(job.host != nullptr, "graph: pinned host block");
+    void* host_dev = nullptr;
+    FDX_HIP(hipHostGetDevicePointer(&host_dev, job.host, 0));
+    FDX_HIP(hipEventCreateWithFlags(&job.ev, hipEventDisableTiming));
+    for (int j = 0; j < 4; ++j) job.host[j] = 0.0;             // (all bits zero)
+    FDX_TRY(queue(reinterpret_cast<long long*>(host_dev)));
+    FDX_HIP(hipEventRecord(job.ev, st));
     FDX_HIP(hipEventSynchronize(job.ev));
-    for (int a = 0; a < 6; ++a) box[a] = with_box ? job.host[a] : 0.0;
-    std::memcpy(words, job.host + 8, 4 * sizeof(long long));
+    std::memcpy(words, job.host, 4 * sizeof(long long));
     return 0;
 }
 
 // under_wait: queued behind the bounding-box kernels and ahead of the host's wait for them - fills whose sizes depend on n alone
 // run on the device while the host takes the six numbers over (they used to sit in the chain of dependent launches after it)
-// box: mn[3], mx[3] already in hand (coords_box, the cache lookup of fdx_graph_build_dev) - no kernels, no wait
 static int make_grid(const double* d_coords, long long n, int dim, double target_per_cell, double min_h,
-                     GridParams* gp, hipStream_t st, const std::function<int()>* under_wait = nullptr, const double* box = nullptr) {
-    std::unique_ptr<BboxJob> job;
-    if (!box) {
-        job = std::make_unique<BboxJob>();
-        FDX_TRY(bbox_begin(d_coords, n, dim, st, job.get()));
-    }
+                     GridParams* gp, hipStream_t st, const std::function<int()>* under_wait = nullptr) {
+    auto job = std::make_unique<BboxJob>();
+    FDX_TRY(bbox_begin(d_coords, n, dim, st, job.get()));
     if (under_wait && *under_wait) FDX_TRY((*under_wait)());
-    if (job) FDX_HIP(hipEventSynchronize(job->ev));
+    FDX_HIP(hipEventSynchronize(job->ev));
     double mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
     for (int a = 0; a < dim; ++a) {
-        mn[a] = box ? box[a] : job->host[a];
-        mx[a] = box ? box[3 + a] : job->host[3 + a];
+        mn[a] = job->host[a];
+        mx[a] = job->host[3 + a];
         if (!(std::isfinite(mn[a]) && std::isfinite(mx[a])))
             return fail(FDX_ERR_INVALID, "graph: coordinates contain NaN or infinity");
     }
@@ -386,7 +380,7 @@ static int make_grid(const double* d_coords, long long n, int dim, double target
 // (cell_need_kernel; counting path only: the sorting path lays out everything)
 int bin_points(const double* d_coords, long long n, int dim, double target_per_cell, double min_h,
                       BinnedPoints* b, hipStream_t st, long long shard_lo, long long shard_hi, int shard_R,
-               const std::function<int()>* extra_under_wait, const double* box) {
+               const std::function<int()>* extra_under_wait) {
     b->n = n;
     FDX_TRY(b->sc.alloc((size_t)n * 3 * sizeof(double)));
     const std::function<int()> under_wait = [&]() -> int {
@@ -395,7 +389,7 @@ int bin_points(const double* d_coords, long long n, int dim, double target_per_c
         if (extra_under_wait && *extra_under_wait) FDX_TRY((*extra_under_wait)());
         return 0;
     };
-    FDX_TRY(make_grid(d_coords, n, dim, target_per_cell, min_h, &b->gp, st, &under_wait, box));
+    FDX_TRY(make_grid(d_coords, n, dim, target_per_cell, min_h, &b->gp, st, &under_wait));
     trace_host("bin: make_grid (bbox kernel + read-back)");
     b->n_cells = b->gp.nc[0] * b->gp.nc[1] * b->gp.nc[2];
     DevBuf& keys = b->keys;

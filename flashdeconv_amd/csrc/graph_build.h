@@ -6,18 +6,15 @@ struct fdx_graph_plan;   // binned points of a two-phase k-NN build (graph_inter
 
 namespace fdx {
 
-// What fdx_graph_build_dev hands a build after its cache lookup (graph_cache.cpp).  box: mn[3], mx[3] of d_coords already in hand
-// (the lookup waited for it together with its compare kernels) - the build queues no box kernels and waits for nothing.
-// under_wait: queued while the host waits for the box (the entry's copy of the coordinates), or at once when the box is in hand.
+// What fdx_graph_build_dev hands a build that missed the cache (graph_cache.cpp).
+// under_wait: queued while the host waits for the bounding box (the entry's copy of the coordinates).
 struct GraphBuildHooks {
-    const double* box = nullptr;
     const std::function<int()>* under_wait = nullptr;
 };
 inline int graph_hook_under_wait(const GraphBuildHooks* h) { return (h && h->under_wait && *h->under_wait) ? (*h->under_wait)() : 0; }
-// The bounding box of d_coords (with_box; dim <= 3) and whatever `also` queues behind its kernels, given the device address of
-// four zeroed 64-bit words of the job's pinned block: ONE host wait, then box[6] = mn[3], mx[3] and words[4] as the device left them.
-int coords_box(const double* d_coords, long long n, int dim, hipStream_t st, bool with_box, const std::function<int(long long*)>& also,
-               double box[6], long long words[4]);
+// Whatever `queue` queues on st, given the device address of four zeroed 64-bit words of a pinned block: ONE host wait, then
+// words[4] as the device left them (graph_bin.cpp; the cache lookup's compare kernels)
+int flag_words(hipStream_t st, const std::function<int(long long*)>& queue, long long words[4]);
 
 // coords: device (n, dim) row-major float64, dim in {1,2,3}
 int graph_build_knn(const double* d_coords, long long n, int dim, int k, fdx_graph* g, hipStream_t st, const GraphBuildHooks* hooks = nullptr);

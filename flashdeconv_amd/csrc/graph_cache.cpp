@@ -69,12 +69,11 @@ GraphCacheKey graph_cache_key(long long n, int dim, int method, int k, double ra
 }
 
 // *out: the graph of an entry with these scalars and these coordinates (one more holder), or NULL.  With an entry that matches
-// on the scalars the compare kernels are queued behind the bounding-box kernels and both are read after ONE wait: box[6] is then
-// in hand (*have_box) for the build that follows a miss.  No such entry: nothing is queued.
-int graph_cache_lookup(const GraphCacheKey& key, const double* d_coords, hipStream_t st, fdx_graph** out, double box[6],
-                       bool* have_box) {
+// on the scalars the compare kernels are queued, alone, and their flags read after one wait: a hit needs no bounding box, and a
+// repeated slide is the case the cache is there for.  A miss behind such an entry (another slide of the same size) builds as a
+// build without a candidate does and so pays a second round trip, for its box.  No such entry: nothing is queued.
+int graph_cache_lookup(const GraphCacheKey& key, const double* d_coords, hipStream_t st, fdx_graph** out) {
     *out = nullptr;
-    *have_box = false;
     std::vector<std::shared_ptr<GraphCacheEntry>> cand = cache().candidates(key);
     if (cand.empty()) {
         cache().miss();
@@ -91,9 +90,7 @@ int graph_cache_lookup(const GraphCacheKey& key, const double* d_coords, hipStre
         return 0;
     };
     long long flags[4] = {0, 0, 0, 0};
-    const bool with_box = key.dim <= 3;              // (more dimensions: the build bins other coordinates - only the flags travel)
-    FDX_TRY(coords_box(d_coords, key.n, key.dim, st, with_box, compare, box, flags));
-    *have_box = with_box;
+    FDX_TRY(flag_words(st, compare, flags));
     for (size_t c = 0; c < cand.size(); ++c)
         if (flags[c] == 0) {
             cache().hit(cand[c]);

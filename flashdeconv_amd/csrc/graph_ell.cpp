@@ -685,8 +685,7 @@ int graph_build_radius(const double* d_coords, long long n, int dim, double radi
         return empty_graph(n, g, st);
     }
     BinnedPoints b;
-    FDX_TRY(bin_points(d_coords, n, dim, 1.0, radius, &b, st, 0, 0, 0, hooks ? hooks->under_wait : nullptr,
-                       hooks ? hooks->box : nullptr));   // cell edge >= radius: one shell suffices
+    FDX_TRY(bin_points(d_coords, n, dim, 1.0, radius, &b, st, 0, 0, 0, hooks ? hooks->under_wait : nullptr));   // cell edge >= radius: one shell suffices
     const int R = (int)std::ceil(radius / b.gp.h[0] * (1.0 + 1e-12));
     g->n = n; g->n_total = n; g->identity_order = false;
     g->perm.take(b.perm);

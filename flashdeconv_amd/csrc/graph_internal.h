@@ -139,8 +139,7 @@ int with_temp(DevBuf& tmp, Call&& call) {
 // shard_lo < shard_hi: a spot shard's binning - the ranking pass lays out only the cells the shard's build looks at
 // (cell_need_kernel; counting path only: the sorting path lays out everything)
 int bin_points(const double* d_coords, long long n, int dim, double target_per_cell, double min_h, BinnedPoints* b, hipStream_t st,
-               long long shard_lo = 0, long long shard_hi = 0, int shard_R = 0, const std::function<int()>* extra_under_wait = nullptr,
-               const double* box = nullptr);   // box: the bounding box of d_coords, already in hand (GraphBuildHooks)
+               long long shard_lo = 0, long long shard_hi = 0, int shard_R = 0, const std::function<int()>* extra_under_wait = nullptr);
 
 // ---- graph_ell.cpp: the stages the whole-graph builds and the shard builds share
 int exclusive_scan_int(const int* in, int* out, long long count, hipStream_t st, DevBuf& tmp);

@@ -502,7 +502,7 @@ int graph_knn_lists(const double* d_coords, long long n, int dim, int k, long lo
         // solver order from the first three coordinates, exhaustive search in all of them
         DevBuf c3;
         rc = c3.alloc((size_t)n * 3 * sizeof(double));
-        if (!rc) rc = graph_hook_under_wait(hooks);   // (no box of d_coords is used here)
+        if (!rc) rc = graph_hook_under_wait(hooks);
         if (!rc) {
             hipLaunchKernelGGL(take3_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, d_coords, n, dim, c3.as<double>());
             rc = bin_points(c3.as<double>(), n, 3, tpc, 0.0, &plan->b, st);
@@ -543,9 +543,8 @@ int graph_knn_lists(const double* d_coords, long long n, int dim, int k, long lo
         FDX_TRY(graph_hook_under_wait(hooks));
         return 0;
     };
-    const double* box = hooks ? hooks->box : nullptr;
-    rc = shard_band ? bin_points(d_coords, n, dim, tpc, 0.0, &plan->b, st, lo, hi, BAND_R, &fills, box)
-                    : bin_points(d_coords, n, dim, tpc, 0.0, &plan->b, st, 0, 0, 0, &fills, box);
+    rc = shard_band ? bin_points(d_coords, n, dim, tpc, 0.0, &plan->b, st, lo, hi, BAND_R, &fills)
+                    : bin_points(d_coords, n, dim, tpc, 0.0, &plan->b, st, 0, 0, 0, &fills);
     if (rc) { delete plan; return rc; }
     const BinnedPoints& b = plan->b;
     const int* perm = b.perm.as<int>();

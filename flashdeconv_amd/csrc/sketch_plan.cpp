@@ -129,7 +129,6 @@ int SketchPlan::build(const long long* col_ptr, const int* gene_idx, const doubl
 namespace {
 struct CacheEntry {
     int dev = 0, G = 0, d = 0;
-    unsigned long long hash = 0;
     std::vector<int32_t> bucket;
     std::vector<double> weight;
     std::shared_ptr<SketchPlan> plan;
@@ -139,29 +138,22 @@ struct CacheEntry {
 std::mutex& g_cache_mu = *new std::mutex();
 std::vector<CacheEntry>& g_cache = *new std::vector<CacheEntry>();   // most recently used last
 constexpr size_t kCacheCap = 12;
-
-unsigned long long fnv1a(const void* p, size_t n, unsigned long long h) {
-    const unsigned char* b = static_cast<const unsigned char*>(p);
-    for (size_t i = 0; i < n; ++i) {
-        h ^= b[i];
-        h *= 1099511628211ULL;
-    }
-    return h;
-}
 }  // namespace
+
+// The tables are compared with memcmp behind the scalars, as x_cache.h compares X: two Omegas differ within their first words, so a
+// mismatch costs nothing, and the one full comparison of a hit (24 KB at 2000 genes) about a microsecond.  (A byte-serial hash
+// stood in front of it: ~25 us of every fit on the host's way to the sketch launch, hit or not.)
 
 int sketch_plan_cached(const int32_t* bucket, const double* weight, int G, int d, hipStream_t st, std::shared_ptr<SketchPlan>* out) {
     FDX_REQUIRE(bucket && weight && G > 0 && d > 0 && out, "sketch plan: bad arguments");
     int dev = 0;
     FDX_HIP(hipGetDevice(&dev));
-    unsigned long long h = fnv1a(bucket, (size_t)G * 4, 1469598103934665603ULL);
-    h = fnv1a(weight, (size_t)G * 8, h);
     const bool use_cache = !fdx::env("FDX_NO_PLAN_CACHE");
     if (use_cache) {
         std::lock_guard<std::mutex> lk(g_cache_mu);
         for (size_t i = 0; i < g_cache.size(); ++i) {
             CacheEntry& e = g_cache[i];
-            if (e.hash == h && e.dev == dev && e.G == G && e.d == d && std::memcmp(e.bucket.data(), bucket, (size_t)G * 4) == 0 &&
+            if (e.dev == dev && e.G == G && e.d == d && std::memcmp(e.bucket.data(), bucket, (size_t)G * 4) == 0 &&
                 std::memcmp(e.weight.data(), weight, (size_t)G * 8) == 0) {
                 *out = e.plan;
                 std::rotate(g_cache.begin() + (long)i, g_cache.begin() + (long)i + 1, g_cache.end());
@@ -191,7 +183,7 @@ int sketch_plan_cached(const int32_t* bucket, const double* weight, int G, int d
         std::lock_guard<std::mutex> lk(g_cache_mu);
         if (g_cache.size() >= kCacheCap) g_cache.erase(g_cache.begin());
         CacheEntry e;
-        e.dev = dev; e.G = G; e.d = d; e.hash = h;
+        e.dev = dev; e.G = G; e.d = d;
         e.bucket.assign(bucket, bucket + G);
         e.weight.assign(weight, weight + G);
         e.plan = plan;
