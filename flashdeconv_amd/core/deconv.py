@@ -701,6 +701,37 @@ class FlashDeconv:
         return spatial_niches(self.proportions_ if what == "proportions" else self.beta_, n_niches, graph=self, features=features,
                               **kw)
 
+    def get_celltype_expression(self, Y, what="proportions", spot_scale=None, groups=None, **kw):
+        """What each cell type expresses in this tissue and which genes the fitted composition explains (additive, not in the
+        reference): per-gene non-negative least squares of ``Y`` on the fitted weights -
+        ``utils.expression.celltype_expression`` on ``proportions_`` (``what="proportions"``) or ``beta_``
+        (``what="abundances"``).  ``Y``: ``n_spots_`` rows, dense or CSR, ANY gene set - every column is regressed, not only
+        ``gene_idx_``.  ``spot_scale``: (n_spots,) finite non-negative factors that multiply the rows of the weights (each spot's
+        library size over the mean library size is the natural choice for counts).  ``groups``: labels per spot (the ``labels``
+        of ``get_spatial_niches``, say; ``-1`` = left out) for one signature matrix per group.  Further keywords (``n_groups``,
+        ``ridge``, ``max_iter``, ``tol``, ``output``) go to ``celltype_expression``.  Works for both ``output`` kinds of ``fit``."""
+        self._require_fitted()
+        if what not in ("proportions", "abundances"):
+            raise ValueError(f"Unknown what: {what}. Choose from 'proportions', 'abundances'.")
+        from ..utils.expression import celltype_expression
+        W = self.proportions_ if what == "proportions" else self.beta_
+        n = int(W.shape[0])
+        if not hasattr(Y, "shape") or len(Y.shape) != 2 or int(Y.shape[0]) != n:
+            raise ValueError(f"Y must be a 2-D matrix with the {n} spots of the fit as rows, got shape {getattr(Y, 'shape', None)}")
+        if spot_scale is not None:
+            if _is_torch_cuda(spot_scale):
+                sc = _lib.tensor_to_host(spot_scale).astype(np.float64)
+            else:
+                sc = np.asarray(spot_scale.detach().numpy() if hasattr(spot_scale, "detach") else spot_scale, dtype=np.float64)
+            if sc.shape != (n,) or not np.all(np.isfinite(sc)) or np.any(sc < 0):
+                raise ValueError(f"spot_scale must be {n} finite non-negative numbers, got shape {sc.shape}")
+            if _is_torch_cuda(W):
+                import torch
+                W = W * torch.as_tensor(sc).to(device=W.device, dtype=W.dtype)[:, None]
+            else:
+                W = W * sc[:, None]
+        return celltype_expression(Y, W, groups=groups, **kw)
+
     def get_dominant_cell_type(self):
         self._require_fitted()
         if hasattr(self.proportions_, "argmax") and not isinstance(self.proportions_, np.ndarray):

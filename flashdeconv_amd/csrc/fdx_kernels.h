@@ -3,6 +3,8 @@
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 
+#include "../../include/fdx.h"
+
 #include <cstddef>
 #include <cstdint>
 #include <utility>
@@ -225,6 +227,19 @@ int launch_kmeans_seed_dist(const KmeansPlan& p, const double* F, long long ldf,
 // positive count become sums / counts.  The plan's C and D must be the ones passed here.
 int launch_label_sums(const KmeansPlan& p, const double* F, long long ldf, const int* labels, int n, int D, int C, void* sums_part,
                       double* sums, long long* counts, double* centres, hipStream_t st);
+
+// ---- expression_kernels.cpp
+// Weighted gene sums (fdx_weighted_gene_sums_dev / _csr_dev): the rows of a group, in the order of the sorted row list, are cut into
+// segments of FDX_EXPRESSION_SEGMENT_ROWS; a segment is summed row after row and the segment sums are folded in ascending order.
+constexpr int EXPR_KC = 32, EXPR_KC_TAIL = 16;   // accumulators a thread of the dense kernel keeps: full chunks, and a last chunk of <= 16
+constexpr int EXPR_CSR_KC = 8;                   // types a workgroup of the CSR kernel adds per pass over its rows
+constexpr int EXPR_NNLS_LDS_MAX_K = 88;          // the solve keeps A_c in LDS up to here (88 * 88 doubles < 64 KB), reads it through L2 above
+// Y dense (csr null) or CSR; group_off on the HOST (fdx.h).  Everything queued on st; scratch from the pool.
+int launch_weighted_gene_sums(const void* Y, int dtype, long long n, int G, long long ldy, const fdx_csr_view* csr, const double* W,
+                              long long ldw, int K, const int* rows, const int* group_off, int C, double* A, double* B, double* q,
+                              double* u, hipStream_t st);
+int launch_nnls_gram(const double* A, const double* B, const double* q, int C, int K, int G, double ridge, int max_iter, double tol,
+                     double* S, int* n_iter, int* converged, double* rss, hipStream_t st);
 
 // ---- bcd_kernels.cpp
 int launch_bcd_sweep(const BcdSweepArgs& a, double* generic_scratch, size_t scratch_ld, hipStream_t st);

@@ -1,12 +1,13 @@
 """``deconvolve(adata_st, adata_ref, ...)``: the reference's scanpy-style entry (``flashdeconv/tl/_deconvolve.py:6-174``)
 forwarding the same keyword arguments to the MI355X ``FlashDeconv``."""
+import numpy as np
 
 
 def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512, lambda_spatial="auto", rho_sparsity=0.01,
                n_hvg=2000, n_markers_per_type=50, spatial_method="knn", k_neighbors=6, radius=None, preprocess="log_cpm",
                layer_st=None, layer_ref=None, spatial_key="spatial", key_added="flashdeconv", random_state=0, copy=False,
                spot_diagnostics=False, spatial_stats=False, n_niches=None, spatial_permutations=0, local_stats=False,
-               correlogram=False):
+               correlogram=False, celltype_expression=False):
     """Writes ``.obsm[key_added]`` (proportions DataFrame), ``.obs[key_added + '_dominant']`` and
     ``.uns[key_added + '_params']``; returns the modified copy when ``copy=True``, else ``None``.  ``spot_diagnostics=True``
     (additive) also writes ``.obs[key_added + '_residual']`` (relative sketch residual per spot) and
@@ -26,15 +27,25 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
     ``correlogram`` (additive): ``True`` (ten bands of the grid radius), an int (that many bands) or a sequence (the radii) also
     writes ``.uns[key_added + '_correlogram']``, a dict of ``radii``, ``n_pairs`` (unordered pairs per band), ``morans_i`` and
     ``z_score`` (DataFrames, band x cell type) and ``cross`` (band x cell type x cell type): Moran's I and the co-localisation
-    matrix by distance band (``FlashDeconv.get_spatial_correlogram``)."""
+    matrix by distance band (``FlashDeconv.get_spatial_correlogram``).
+    ``celltype_expression=True`` (additive) also writes ``.uns[key_added + '_expression']`` (DataFrame, common genes x cell types:
+    what each cell type expresses in this tissue - the per-gene non-negative least squares of the spot matrix on the
+    proportions scaled by each spot's row sum over the mean row sum, ``FlashDeconv.get_celltype_expression``) and
+    ``.uns[key_added + '_expression_r2']`` (Series over the common genes: the share of each gene's variance the fitted
+    composition explains)."""
     from ..core.deconv import FlashDeconv
     from ..io import prepare_data, result_to_anndata
     from ..utils.correlogram import correlogram_request
     correlogram_kw = correlogram_request(correlogram)          # a bad request fails here, not behind the fit
+    if not isinstance(celltype_expression, (bool, np.bool_)):
+        raise ValueError(f"celltype_expression must be True or False, got {celltype_expression!r}")
 
     adata = adata_st.copy() if copy else adata_st
-    Y, X, coords, names, _ = prepare_data(adata, adata_ref, cell_type_key=cell_type_key, layer_st=layer_st,
+    Y, X, coords, names, genes = prepare_data(adata, adata_ref, cell_type_key=cell_type_key, layer_st=layer_st,
                                           layer_ref=layer_ref, spatial_coord_key=spatial_key)
+    if celltype_expression:
+        from ..utils.expression import check_request
+        check_request(tuple(Y.shape), len(names))                # more cell types than the solve takes: fails here too
     # like the reference, max_iter / tol / verbose are not exposed here (tl/_deconvolve.py:132-144)
     model = FlashDeconv(sketch_dim=sketch_dim, lambda_spatial=lambda_spatial, rho_sparsity=rho_sparsity, n_hvg=n_hvg,
                         n_markers_per_type=n_markers_per_type, spatial_method=spatial_method, k_neighbors=k_neighbors,
@@ -105,4 +116,30 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
             "cross": cg["cross"]}
         adata.uns[f"{key_added}_params"]["correlogram"] = (True if not correlogram_kw else
                                                             correlogram_kw.get("n_bands", correlogram_kw.get("radii")))
+    if celltype_expression:
+        import pandas as pd
+        ex = model.get_celltype_expression(Y, spot_scale=_library_scale(Y))
+        adata.uns[f"{key_added}_expression"] = pd.DataFrame(ex["expression"].T, index=[str(g) for g in genes],
+                                                             columns=[str(t) for t in names])
+        adata.uns[f"{key_added}_expression_r2"] = pd.Series(ex["r2"], index=[str(g) for g in genes])
+        adata.uns[f"{key_added}_params"]["celltype_expression"] = True
     return adata if copy else None
+
+
+def _library_scale(Y):
+    """Each spot's row sum of ``Y`` over the mean row sum (ones when the matrix is all zero), as a host float64 array."""
+    from .. import _lib
+    if _lib.is_torch_sparse_csr(Y):
+        import torch
+        crow = Y.crow_indices().to(torch.int64)
+        row_of = torch.repeat_interleave(torch.arange(Y.shape[0], device=Y.device), crow[1:] - crow[:-1])
+        rs = torch.zeros(Y.shape[0], dtype=torch.float64, device=Y.device)
+        rs.index_add_(0, row_of, Y.values().to(torch.float64))     # (counts: exact in float64 whatever the order)
+        rs = _lib.tensor_to_host(rs)
+    elif getattr(Y, "is_cuda", False):
+        import torch
+        rs = _lib.tensor_to_host(Y.sum(dim=1, dtype=torch.float64))
+    else:
+        rs = np.asarray(Y.sum(axis=1), dtype=np.float64).ravel()
+    mean = rs.mean() if rs.size else 0.0
+    return rs / mean if mean > 0 else np.ones_like(rs)

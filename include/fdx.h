@@ -693,6 +693,42 @@ int fdx_kmeans_seed_dist_dev(const double* F_dev, int64_t ldf, int64_t n, int32_
 int fdx_kmeans_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, int32_t C, int32_t max_iter, double* centres_dev,
                    int32_t* labels_dev, int64_t* counts_out, double* inertia_out, int32_t* n_iter_out, int32_t* converged_out,
                    void* stream);
+/* ---- cell-type expression in tissue (additive, not in the reference; csrc/expression_kernels.cpp) ------------------------------ *
+ * Sufficient statistics of the per-gene regressions Y[:, g] ~ W s_g, s_g >= 0, over groups of rows, and the solves.
+ *
+ * fdx_weighted_gene_sums_dev / _csr_dev: Y (n, G) dense FDX_F32 / FDX_F64 with row stride ldy, or a CSR view whose rows have
+ * distinct columns (sorted or not); W_dev (n, K) float64 with row stride ldw >= K, 1 <= K <= 272.  rows_dev: int32 DEVICE, the
+ * rows sorted by group and ascending inside a group (a stable sort of the labels), group_off: int32[C + 1] HOST, the ranges of the
+ * C >= 1 groups in rows_dev (group_off[0] = 0, ascending; rows left out are simply not listed).  rows_dev == NULL: rows 0 .. n - 1
+ * as ONE group (C must be 1, group_off is not read).  With R_c the rows of group c in that order, to DEVICE memory, float64:
+ *   A (C, K, K) = sum_i w_i w_i'     B (C, K, G) = sum_i w_i y_i'     q (C, G) = sum_i y_ig^2     u (C, G) = sum_i y_ig
+ * The order of every sum is fixed by the data alone: the rows of a group are cut into segments of FDX_EXPRESSION_SEGMENT_ROWS
+ * rows, a segment is added row after row (a product and its addition are one fused operation), and the segment sums are added in
+ * ascending order.  No floating-point atomics; two calls return the same bits, and so does a call whose launch gives a workgroup
+ * more or fewer segments (FDX_EXPR_STRIPE_SEGMENTS) or the genes in more passes.  float32 Y is widened in registers; CSR entries
+ * that are not stored add nothing.  Asynchronous on `stream`; the segment sums live in the library's pool (about 1 GiB at a time:
+ * beyond that the segments go in batches and the sums continue from the previous batch's, the same bits again), beside a copy
+ * of the listed rows of W padded to a multiple of 16 columns. */
+#define FDX_EXPRESSION_SEGMENT_ROWS 2048
+#define FDX_EXPRESSION_MAX_K 272
+int fdx_weighted_gene_sums_dev(const void* Y_dev, int32_t dtype, int64_t n, int32_t G, int64_t ldy, const double* W_dev, int64_t ldw,
+                               int32_t K, const int32_t* rows_dev, const int32_t* group_off, int32_t C, double* A_dev, double* B_dev,
+                               double* q_dev, double* u_dev, void* stream);
+int fdx_weighted_gene_sums_csr_dev(const fdx_csr_view* Y, const double* W_dev, int64_t ldw, int32_t K, const int32_t* rows_dev,
+                                   const int32_t* group_off, int32_t C, double* A_dev, double* B_dev, double* q_dev, double* u_dev,
+                                   void* stream);
+/* Non-negative least squares from the sums, one problem per (group c, gene g): minimise s' A_c s - 2 s' B_c[:, g] over s >= 0 by
+ * cyclic coordinate descent from s = 0 with D_k = A_c[k][k] + ridge * (A_c[0][0] + ... + A_c[K-1][K-1]) / K:
+ *   sweep it = 1 .. max_iter:  for k = 0 .. K - 1:  new = D_k > 0 ? max(0, (b_k - sum_{j != k} A_c[k][j] s_j) / D_k) : 0
+ *   converged after the sweep where max_k |new - s_k| <= tol * max_k s_k.
+ * The kernel keeps t = A_c s - b and forms the numerator as A_c[k][k] s_k - t_k (fused), t += A_c[:, k] (new - s_k) (fused): the
+ * iterates agree with the dot-product form up to rounding.  A_dev (C, K, K), B_dev (C, K, G), q_dev (C, G; may be NULL) on the
+ * DEVICE; to DEVICE memory S (C, K, G), n_iter and converged (C, G) int32, and - where q_dev is given - rss (C, G) =
+ * max(0, q - 2 s.b + s' A_c s) with A_c s formed afresh (no ridge in it).  1 <= K <= 272 (A_c in LDS up to 88 types, read through
+ * L2 above), ridge >= 0, max_iter >= 1, tol > 0.  Asynchronous on `stream`. */
+int fdx_nnls_gram_dev(const double* A_dev, const double* B_dev, const double* q_dev, int32_t C, int32_t K, int32_t G, double ridge,
+                      int32_t max_iter, double tol, double* S_dev, int32_t* n_iter_dev, int32_t* converged_dev, double* rss_dev,
+                      void* stream);
 /* beta (K, ld) type-major -> beta_out / prop_out (n, K) row-major in solver order of the own spots. */
 int fdx_normalize_dev(const double* beta_dev, int64_t ld, int64_t n, int32_t K, double* beta_out_dev, double* prop_out_dev,
                       void* stream);
