@@ -346,10 +346,18 @@ def host_cpu_budget():
     return max(1, int(round(cpus)))
 
 
-def current_stream():
-    """torch's current stream of the current device, as the stream argument of the device-pointer calls."""
+def is_torch(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def is_cuda_tensor(x):
+    return is_torch(x) and bool(getattr(x, "is_cuda", False))
+
+
+def current_stream(device=None):
+    """torch's current stream of ``device`` (None: the current device), as the stream argument of the device-pointer calls."""
     import torch
-    return c_void_p(torch.cuda.current_stream().cuda_stream)
+    return c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def dtype_code(t):

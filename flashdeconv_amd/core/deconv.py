@@ -22,10 +22,6 @@ from .sketching import sketch_tables
 _PRE_MODES = ("log_cpm", "pearson", "raw")
 
 
-def _is_torch_cuda(x):
-    return hasattr(x, "data_ptr") and hasattr(x, "is_cuda") and bool(x.is_cuda)
-
-
 def device_counts_as_float(Y):
     """A dense CUDA tensor as the float32 / float64 matrix the kernels stream, plus whether its transform must keep float64
     accuracy (``PRE_F64_MATH``).  Integer counts: numpy promotes them to float64 in the reference (core/deconv.py:190-191),
@@ -311,7 +307,7 @@ class FlashDeconv:
                 csr = _lib.CsrOnDevice.from_scipy(Y) if sparse.issparse(Y) else _lib.CsrOnDevice.from_torch(Y)
                 owned.append(csr)
                 y_ptr, y_code, y_sparse_rule = None, csr.view.dtype, True
-            elif _is_torch_cuda(Y):
+            elif _lib.is_cuda_tensor(Y):
                 Y, y_f64_math = device_counts_as_float(Y)
                 y_ptr, y_code, y_sparse_rule = Y.data_ptr(), _lib.dtype_code(Y), False
             else:
@@ -324,7 +320,7 @@ class FlashDeconv:
             # coordinates into HBM; with gene selection active (G > n_hvg) the spatial graph - which does not depend on the genes -
             # is queued FIRST: its ~0.7 ms of kernels then run under the gene statistics and the host's ranking of the G-vector
             # instead of after them (the device idled ~1.5 ms there)
-            if _is_torch_cuda(coords):
+            if _lib.is_cuda_tensor(coords):
                 import torch
                 cd = coords.to(torch.float64).contiguous()
                 c_ptr = cd.data_ptr()
@@ -351,7 +347,7 @@ class FlashDeconv:
                 else:
                     # on the library's side stream, behind whatever produced the coordinates on the default stream so far
                     _lib.check(lib.fdx_side_stream(ctypes.byref(side)))
-                    if _is_torch_cuda(coords):
+                    if _lib.is_cuda_tensor(coords):
                         _lib.check(lib.fdx_stream_wait_stream(side, _lib.current_stream()))
                 _lib.check(lib.fdx_graph_build_dev(c_ptr, n, dim, g_method, g_k, g_radius, side, ctypes.byref(gh)))
                 self._graph = _lib.Graph(gh.value)
@@ -455,7 +451,7 @@ class FlashDeconv:
 
             if output == "torch":
                 import torch
-                dev = Y.device if _is_torch_cuda(Y) else torch.device("cuda", torch.cuda.current_device())
+                dev = Y.device if _lib.is_cuda_tensor(Y) else torch.device("cuda", torch.cuda.current_device())
                 beta_t = torch.empty((n, K), dtype=torch.float64, device=dev)
                 prop_t = torch.empty((n, K), dtype=torch.float64, device=dev)
                 b_ptr, p_ptr = beta_t.data_ptr(), prop_t.data_ptr()
@@ -719,13 +715,13 @@ class FlashDeconv:
         if not hasattr(Y, "shape") or len(Y.shape) != 2 or int(Y.shape[0]) != n:
             raise ValueError(f"Y must be a 2-D matrix with the {n} spots of the fit as rows, got shape {getattr(Y, 'shape', None)}")
         if spot_scale is not None:
-            if _is_torch_cuda(spot_scale):
+            if _lib.is_cuda_tensor(spot_scale):
                 sc = _lib.tensor_to_host(spot_scale).astype(np.float64)
             else:
                 sc = np.asarray(spot_scale.detach().numpy() if hasattr(spot_scale, "detach") else spot_scale, dtype=np.float64)
             if sc.shape != (n,) or not np.all(np.isfinite(sc)) or np.any(sc < 0):
                 raise ValueError(f"spot_scale must be {n} finite non-negative numbers, got shape {sc.shape}")
-            if _is_torch_cuda(W):
+            if _lib.is_cuda_tensor(W):
                 import torch
                 W = W * torch.as_tensor(sc).to(device=W.device, dtype=W.dtype)[:, None]
             else:

@@ -354,7 +354,7 @@ int fdx_bcd_solve(const fdx_graph* g, const double* Y_sketch, const double* X_sk
     p.lambda = lambda; p.rho_eff = rho * diag_mean; p.max_iter = max_iter; p.tol = tol; p.verbose = verbose;
     SolveResult r;
     FDX_TRY(solver_run(p, &r, st));
-    FDX_TRY(launch_normalize_export(p.beta[r.result_buffer], ld, g->identity_order ? nullptr : g->perm.as<int>(), (int)n,
+    FDX_TRY(launch_normalize_export(p.beta[r.result_buffer], ld, caller_order_perm(g), (int)n,
                                     g->n_slices, K, dOut.as<double>(), nullptr, st));
     FDX_TRY(copy_d2h(beta_out, dOut.p, (size_t)n * K * sizeof(double), st));
     FDX_TRY(e1.record(st));

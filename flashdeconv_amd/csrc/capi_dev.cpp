@@ -1,7 +1,8 @@
-// Device-pointer C-ABI building blocks used by the spot-sharded multi-GPU driver (see include/fdx.h).
+// Device-pointer C-ABI building blocks used by the spot-sharded multi-GPU driver and the stage tests (see include/fdx.h): graph
+// builds and their queries, and the stages of a fit one by one - gene moments / column gather, prepare, sweep, objective, spot
+// diagnostics, normalise / export.  The analysis entries stand beside their kernels (spatial_stats_kernels.cpp,
+// local_stats_kernels.cpp, correlogram_kernels.cpp, niche_kernels.cpp, metrics_kernels.cpp, expression_kernels.cpp).
 #include "fdx_env.h"
-#include <algorithm>
-#include <cmath>
 #include <memory>
 #include <vector>
 
@@ -420,274 +421,9 @@ int fdx_spot_diagnostics_dev(const fdx_graph* g, const double* beta_dev, int64_t
     FDX_REQUIRE(ldh >= g->n, "fdx_spot_diagnostics_dev: ldh must cover the own spots");
     if (g->n == 0) return 0;
     // a shard's local graph keeps GLOBAL ids in perm: its rows stay in the graph's own order
-    const int* perm = (g->identity_order || !g->perm.p || g->world_n > 0) ? nullptr : g->perm.as<int>();
+    const int* perm = g->world_n > 0 ? nullptr : caller_order_perm(g);
     return launch_spot_diagnostics(beta_dev, ld, H_dev, ldh, XtX_dev, ldg, row_sq_dev, g->ell.as<int>(), g->slice_off.as<int>(),
                                    g->deg.as<int>(), perm, (int)g->n, g->n_slices, K, out_dev, (hipStream_t)stream);
-}
-
-int fdx_spatial_autocorr_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, int32_t K, double* mean_out, double* m2_out,
-                             double* C_out, int64_t* counts_out, double* neighbor_mean_dev, void* stream) {
-    FDX_TRY(fdx::graph_meta_sync(g));
-    FDX_REQUIRE(g && V_dev && mean_out && m2_out && C_out && counts_out, "fdx_spatial_autocorr_dev: null argument");
-    FDX_REQUIRE(K >= 1 && ldv >= K, "fdx_spatial_autocorr_dev: K must be positive and ldv at least K");
-    FDX_REQUIRE(!g->shard_pending && g->n_total == g->n && g->world_n == 0,
-                "fdx_spatial_autocorr_dev: a shard's local graph is refused (whole graphs on one GPU only)");
-    FDX_REQUIRE(g->n < (1LL << 31) - 128, "fdx_spatial_autocorr_dev: too many spots");
-    hipStream_t st = (hipStream_t)stream;
-    PoolStream pool_stream(st);
-    const size_t KK = (size_t)K * K;
-    counts_out[0] = g->n;
-    counts_out[1] = counts_out[2] = 0;
-    if (g->n == 0) {                                    // no spots: no mean
-        std::fill(mean_out, mean_out + K, std::nan(""));
-        std::fill(m2_out, m2_out + K, 0.0);
-        std::fill(C_out, C_out + KK, 0.0);
-        return 0;
-    }
-    const SpatialStatsPlan plan = spatial_stats_plan(g->n, K);
-    DevBuf scratch, out;
-    FDX_TRY(scratch.alloc(plan.scratch_doubles * sizeof(double)));
-    FDX_TRY(out.alloc(plan.out_doubles * sizeof(double)));
-    const int* perm = (g->identity_order || !g->perm.p) ? nullptr : g->perm.as<int>();
-    FDX_TRY(launch_spatial_stats(plan, V_dev, ldv, (int)g->n, K, g->ell.as<int>(), g->slice_off.as<int>(), g->deg.as<int>(), perm,
-                                 scratch.as<double>(), out.as<double>(), neighbor_mean_dev, st));
-    std::vector<double> host(plan.out_doubles);
-    FDX_TRY(copy_d2h(host.data(), out.p, plan.out_doubles * sizeof(double), st));   // the call's one host synchronisation
-    std::copy(host.begin(), host.begin() + K, mean_out);
-    std::copy(host.begin() + K, host.begin() + 2 * (size_t)K, m2_out);
-    std::copy(host.begin() + 2 * (size_t)K, host.begin() + 2 * (size_t)K + KK, C_out);
-    std::memcpy(counts_out + 1, host.data() + 2 * (size_t)K + KK, 2 * sizeof(int64_t));
-    return 0;
-}
-
-int fdx_spatial_perm_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, int32_t K, uint64_t seed, int64_t first_perm,
-                         int64_t n_perm, int32_t max_batch, double* null_dev, double* mean_out, double* m2_out, double* C_out,
-                         int64_t* counts_out, double* m4_out, int64_t* count_ge_out, int64_t* count_le_out, double* sum_d_out,
-                         double* sumsq_d_out, int32_t* batch_out, void* stream) {
-    FDX_TRY(fdx::graph_meta_sync(g));
-    FDX_REQUIRE(g && V_dev && mean_out && m2_out && C_out && counts_out && m4_out && count_ge_out && count_le_out && sum_d_out &&
-                    sumsq_d_out,
-                "fdx_spatial_perm_dev: null argument");
-    FDX_REQUIRE(K >= 1 && ldv >= K, "fdx_spatial_perm_dev: K must be positive and ldv at least K");
-    FDX_REQUIRE(first_perm >= 0 && n_perm >= 0 && max_batch >= 0,
-                "fdx_spatial_perm_dev: first_perm, n_perm and max_batch must not be negative");
-    FDX_REQUIRE(!g->shard_pending && g->n_total == g->n && g->world_n == 0,
-                "fdx_spatial_perm_dev: a shard's local graph is refused (whole graphs on one GPU only)");
-    FDX_REQUIRE(g->n < (1LL << 31) - 128, "fdx_spatial_perm_dev: too many spots");
-    hipStream_t st = (hipStream_t)stream;
-    PoolStream pool_stream(st);
-    const size_t KK = (size_t)K * K;
-    counts_out[0] = g->n;
-    counts_out[1] = counts_out[2] = 0;
-    std::fill(count_ge_out, count_ge_out + KK, (int64_t)0);
-    std::fill(count_le_out, count_le_out + KK, (int64_t)0);
-    std::fill(sum_d_out, sum_d_out + KK, 0.0);
-    std::fill(sumsq_d_out, sumsq_d_out + KK, 0.0);
-    if (batch_out) *batch_out = 0;
-    if (g->n == 0) {                                    // no spots: no mean, and nothing to permute
-        std::fill(mean_out, mean_out + K, std::nan(""));
-        std::fill(m2_out, m2_out + K, 0.0);
-        std::fill(m4_out, m4_out + K, 0.0);
-        std::fill(C_out, C_out + KK, 0.0);
-        if (null_dev && n_perm > 0) FDX_HIP(hipMemsetAsync(null_dev, 0, (size_t)n_perm * KK * sizeof(double), st));
-        for (size_t i = 0; i < KK; ++i) count_ge_out[i] = count_le_out[i] = n_perm;      // every C_r equals C_obs = 0
-        return 0;
-    }
-    const SpatialPermPlan plan = spatial_perm_plan(g->n, K, n_perm, max_batch, null_dev == nullptr);
-    if (batch_out) *batch_out = n_perm > 0 ? plan.batch : 0;
-    DevBuf scratch, out;
-    FDX_TRY(scratch.alloc(plan.scratch_doubles * sizeof(double)));
-    FDX_TRY(out.alloc(plan.out_doubles * sizeof(double)));
-    const int* perm = (g->identity_order || !g->perm.p) ? nullptr : g->perm.as<int>();
-    FDX_TRY(launch_spatial_perm(plan, V_dev, ldv, (int)g->n, K, g->ell.as<int>(), g->slice_off.as<int>(), g->deg.as<int>(), perm,
-                                seed, first_perm, n_perm, null_dev, scratch.as<double>(), out.as<double>(), st));
-    std::vector<double> host(plan.out_doubles);
-    FDX_TRY(copy_d2h(host.data(), out.p, plan.out_doubles * sizeof(double), st));   // the call's one host synchronisation
-    const double* h = host.data();
-    std::copy(h, h + K, mean_out);
-    std::copy(h + K, h + 2 * (size_t)K, m2_out);
-    std::copy(h + 2 * (size_t)K, h + 2 * (size_t)K + KK, C_out);
-    std::memcpy(counts_out + 1, h + 2 * (size_t)K + KK, 2 * sizeof(int64_t));
-    h += plan.s.out_doubles;
-    std::copy(h, h + K, m4_out);
-    std::memcpy(count_ge_out, h + K, KK * sizeof(int64_t));
-    std::memcpy(count_le_out, h + K + KK, KK * sizeof(int64_t));
-    std::copy(h + K + 2 * KK, h + K + 3 * KK, sum_d_out);
-    std::copy(h + K + 3 * KK, h + K + 4 * KK, sumsq_d_out);
-    return 0;
-}
-
-int fdx_permutation_indices_dev(uint64_t seed, int64_t r, int64_t n, int32_t* out_dev, void* stream) {
-    FDX_REQUIRE(n >= 0 && n < (1LL << 31) - 128, "fdx_permutation_indices_dev: n must be between 0 and 2^31 - 129");
-    FDX_REQUIRE(r >= 0, "fdx_permutation_indices_dev: r must not be negative");
-    FDX_REQUIRE(n == 0 || out_dev, "fdx_permutation_indices_dev: null argument");
-    return launch_permutation_indices(seed, r, (int)n, out_dev, (hipStream_t)stream);
-}
-
-int fdx_local_stats_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, int32_t K, uint64_t seed, int64_t first_perm,
-                        int64_t n_perm, double* nbr_sum_dev, int32_t* deg_dev, int32_t* count_ge_dev, int32_t* count_le_dev,
-                        double* sum_d_dev, double* sumsq_d_dev, double* mean_out, double* m2_out, int64_t* counts_out,
-                        void* stream) {
-    FDX_REQUIRE(g && V_dev && nbr_sum_dev && deg_dev && mean_out && m2_out && counts_out, "fdx_local_stats_dev: null argument");
-    FDX_TRY(fdx::graph_meta_sync(g));
-    FDX_REQUIRE(K >= 1 && ldv >= K, "fdx_local_stats_dev: K must be positive and ldv at least K");
-    FDX_REQUIRE(first_perm >= 0 && n_perm >= 0, "fdx_local_stats_dev: first_perm and n_perm must not be negative");
-    FDX_REQUIRE(n_perm < (1LL << 31), "fdx_local_stats_dev: n_perm must be below 2^31");
-    FDX_REQUIRE(n_perm == 0 || (count_ge_dev && count_le_dev && sum_d_dev && sumsq_d_dev),
-                "fdx_local_stats_dev: null argument (the permutation outputs may be null only with n_perm == 0)");
-    FDX_REQUIRE(!g->shard_pending && g->n_total == g->n && g->world_n == 0,
-                "fdx_local_stats_dev: a shard's local graph is refused (whole graphs on one GPU only)");
-    FDX_REQUIRE(g->n < (1LL << 31) - 128, "fdx_local_stats_dev: too many spots");
-    FDX_REQUIRE(g->n == 0 || (g->ell.p && g->slice_off.p && g->deg.p), "fdx_local_stats_dev: the graph has no device tables");
-    hipStream_t st = (hipStream_t)stream;
-    PoolStream pool_stream(st);
-    counts_out[0] = g->n;
-    counts_out[1] = counts_out[2] = 0;
-    if (g->n == 0) {                                    // no spots: no mean, and no row to write
-        std::fill(mean_out, mean_out + K, std::nan(""));
-        std::fill(m2_out, m2_out + K, 0.0);
-        return 0;
-    }
-    const SpatialStatsPlan plan = spatial_stats_plan(g->n, K);
-    DevBuf scratch, out;
-    FDX_TRY(scratch.alloc(plan.scratch_doubles * sizeof(double)));
-    FDX_TRY(out.alloc(plan.out_doubles * sizeof(double)));
-    const int* perm = (g->identity_order || !g->perm.p) ? nullptr : g->perm.as<int>();
-    FDX_TRY(launch_local_stats(plan, V_dev, ldv, (int)g->n, K, g->ell.as<int>(), g->slice_off.as<int>(), g->deg.as<int>(), perm,
-                               seed, first_perm, (int)n_perm, scratch.as<double>(), out.as<double>(), nbr_sum_dev, deg_dev,
-                               count_ge_dev, count_le_dev, sum_d_dev, sumsq_d_dev, st));
-    std::vector<double> host(plan.out_doubles);
-    FDX_TRY(copy_d2h(host.data(), out.p, plan.out_doubles * sizeof(double), st));   // the call's one host synchronisation
-    const size_t KK = (size_t)K * K;
-    std::copy(host.begin(), host.begin() + K, mean_out);
-    std::copy(host.begin() + K, host.begin() + 2 * (size_t)K, m2_out);
-    std::memcpy(counts_out + 1, host.data() + 2 * (size_t)K + KK, 2 * sizeof(int64_t));
-    return 0;
-}
-
-int fdx_conditional_indices_dev(uint64_t seed, int64_t r, int64_t spot, int64_t n, int64_t count, int32_t* out_dev, void* stream) {
-    FDX_REQUIRE(n >= 1 && n < (1LL << 31) - 128, "fdx_conditional_indices_dev: n must be between 1 and 2^31 - 129");
-    FDX_REQUIRE(r >= 0, "fdx_conditional_indices_dev: r must not be negative");
-    FDX_REQUIRE(spot >= 0 && spot < n, "fdx_conditional_indices_dev: spot must be in [0, n)");
-    FDX_REQUIRE(count >= 0 && count <= n - 1, "fdx_conditional_indices_dev: count must be between 0 and n - 1");
-    FDX_REQUIRE(count == 0 || out_dev, "fdx_conditional_indices_dev: null argument");
-    return launch_conditional_indices(seed, r, (int)spot, (int)n, (int)count, out_dev, (hipStream_t)stream);
-}
-
-}  // extern "C"
-
-// the shape checks the k-means entries share; `who` names the entry in the message
-static int kmeans_check_shape(const char* who, int64_t ldf, int64_t n, int32_t D, int32_t C, bool centres_are_rows) {
-    const std::string w(who);
-    FDX_REQUIRE(D >= 1, w + ": D must be positive");
-    FDX_REQUIRE(ldf >= D, w + ": ldf must be at least D");
-    FDX_REQUIRE(C >= 1 && C <= 64, w + ": C must be between 1 and 64");
-    FDX_REQUIRE(n >= 0 && n < (1LL << 31) - 128, w + ": too many rows");
-    if (centres_are_rows) FDX_REQUIRE(C <= n, w + ": C must not exceed n");
-    return 0;
-}
-
-extern "C" {
-
-int fdx_kmeans_assign_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, const double* centres_dev, int32_t C,
-                          int32_t* labels_dev, double* min_d2_dev, int64_t* changed_out, double* inertia_out, void* stream) {
-    FDX_REQUIRE(F_dev && centres_dev && labels_dev && changed_out && inertia_out, "fdx_kmeans_assign_dev: null argument");
-    FDX_TRY(kmeans_check_shape("fdx_kmeans_assign_dev", ldf, n, D, C, true));
-    hipStream_t st = (hipStream_t)stream;
-    PoolStream pool_stream(st);
-    const KmeansPlan plan = kmeans_plan(n, D, C);
-    DevBuf part, out;
-    FDX_TRY(part.alloc(plan.dist_part_bytes));
-    FDX_TRY(out.alloc(16));
-    FDX_TRY(launch_kmeans_assign(plan, F_dev, ldf, (int)n, D, centres_dev, C, labels_dev, min_d2_dev, part.p, out.as<long long>(),
-                                 out.as<double>() + 1, st));
-    unsigned char host[16];
-    FDX_TRY(copy_d2h(host, out.p, 16, st));            // the call's one host synchronisation
-    std::memcpy(changed_out, host, 8);
-    std::memcpy(inertia_out, host + 8, 8);
-    return 0;
-}
-
-int fdx_label_sums_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, const int32_t* labels_dev, int32_t C,
-                       double* sums_out, int64_t* counts_out, void* stream) {
-    FDX_REQUIRE(sums_out && counts_out && (n == 0 || (F_dev && labels_dev)), "fdx_label_sums_dev: null argument");
-    FDX_TRY(kmeans_check_shape("fdx_label_sums_dev", ldf, n, D, C, false));
-    const size_t CD = (size_t)C * D;
-    std::fill(sums_out, sums_out + CD, 0.0);
-    std::fill(counts_out, counts_out + C, (int64_t)0);
-    if (n == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    PoolStream pool_stream(st);
-    const KmeansPlan plan = kmeans_plan(n, D, C);
-    DevBuf part, out;
-    FDX_TRY(part.alloc(plan.sums_part_bytes));
-    FDX_TRY(out.alloc((CD + C) * 8));
-    FDX_TRY(launch_label_sums(plan, F_dev, ldf, labels_dev, (int)n, D, C, part.p, out.as<double>(),
-                              reinterpret_cast<long long*>(out.as<double>() + CD), nullptr, st));
-    std::vector<double> host(CD + C);
-    FDX_TRY(copy_d2h(host.data(), out.p, (CD + C) * 8, st));
-    std::copy(host.begin(), host.begin() + CD, sums_out);
-    std::memcpy(counts_out, host.data() + CD, (size_t)C * 8);
-    return 0;
-}
-
-int fdx_kmeans_seed_dist_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, const double* centre_dev, double* d2_dev,
-                             double* block_sums_out, int64_t* block_rows_out, int32_t* n_blocks_out, void* stream) {
-    FDX_REQUIRE(F_dev && centre_dev && d2_dev && block_sums_out && block_rows_out && n_blocks_out,
-                "fdx_kmeans_seed_dist_dev: null argument");
-    FDX_TRY(kmeans_check_shape("fdx_kmeans_seed_dist_dev", ldf, n, D, 1, true));
-    hipStream_t st = (hipStream_t)stream;
-    PoolStream pool_stream(st);
-    const KmeansPlan plan = kmeans_plan(n, D, 1);
-    DevBuf part, out;
-    FDX_TRY(part.alloc(plan.dist_part_bytes));
-    FDX_TRY(out.alloc((size_t)plan.seed_blocks * 8));
-    FDX_TRY(launch_kmeans_seed_dist(plan, F_dev, ldf, (int)n, D, centre_dev, d2_dev, part.p, out.as<double>(), st));
-    FDX_TRY(copy_d2h(block_sums_out, out.p, (size_t)plan.seed_blocks * 8, st));
-    *block_rows_out = plan.seed_rows;
-    *n_blocks_out = plan.seed_blocks;
-    return 0;
-}
-
-int fdx_kmeans_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, int32_t C, int32_t max_iter, double* centres_dev,
-                   int32_t* labels_dev, int64_t* counts_out, double* inertia_out, int32_t* n_iter_out, int32_t* converged_out,
-                   void* stream) {
-    FDX_REQUIRE(F_dev && centres_dev && labels_dev && counts_out && inertia_out && n_iter_out && converged_out,
-                "fdx_kmeans_dev: null argument");
-    FDX_TRY(kmeans_check_shape("fdx_kmeans_dev", ldf, n, D, C, true));
-    FDX_REQUIRE(max_iter >= 1, "fdx_kmeans_dev: max_iter must be positive");
-    hipStream_t st = (hipStream_t)stream;
-    PoolStream pool_stream(st);
-    const KmeansPlan plan = kmeans_plan(n, D, C);
-    const size_t CD = (size_t)C * D;
-    DevBuf dist_part, sums_part, out;
-    FDX_TRY(dist_part.alloc(plan.dist_part_bytes));
-    FDX_TRY(sums_part.alloc(plan.sums_part_bytes));
-    FDX_TRY(out.alloc(16 + (CD + C) * 8));               // [changed | inertia | sums C*D | counts C]
-    long long* changed_d = out.as<long long>();
-    double* inertia_d = out.as<double>() + 1;
-    double* sums_d = out.as<double>() + 2;
-    long long* counts_d = reinterpret_cast<long long*>(sums_d + CD);
-    FDX_HIP(hipMemsetAsync(labels_dev, 0xFF, (size_t)n * sizeof(int32_t), st));      // every label -1
-    int it = 0, converged = 0;
-    unsigned char host[16];
-    for (;;) {
-        ++it;
-        FDX_TRY(launch_kmeans_assign(plan, F_dev, ldf, (int)n, D, centres_dev, C, labels_dev, nullptr, dist_part.p, changed_d,
-                                     inertia_d, st));
-        FDX_TRY(copy_d2h(host, out.p, 16, st));          // 16 bytes per iteration: the loop's only host synchronisation
-        int64_t changed;
-        std::memcpy(&changed, host, 8);
-        if (changed == 0) { converged = 1; break; }
-        if (it == max_iter) break;
-        FDX_TRY(launch_label_sums(plan, F_dev, ldf, labels_dev, (int)n, D, C, sums_part.p, sums_d, counts_d, centres_dev, st));
-    }
-    FDX_TRY(launch_label_sums(plan, nullptr, ldf, labels_dev, (int)n, D, C, sums_part.p, sums_d, counts_d, nullptr, st));
-    FDX_TRY(copy_d2h(counts_out, counts_d, (size_t)C * 8, st));
-    std::memcpy(inertia_out, host + 8, 8);
-    *n_iter_out = it;
-    *converged_out = converged;
-    return 0;
 }
 
 int fdx_export_dev(const fdx_graph* g, const double* beta_dev, int64_t ld, int32_t K, double* beta_out_dev, double* prop_out_dev,
@@ -698,8 +434,8 @@ int fdx_export_dev(const fdx_graph* g, const double* beta_dev, int64_t ld, int32
     FDX_REQUIRE(g->world_n == 0 && g->n_total == g->n, "fdx_export_dev: a shard's local graph is refused (its perm holds global ids)");
     if (g->n == 0) return 0;
     // the export of a fit (fit.cpp): the graph's own perm, null for a graph in the caller's order
-    const int* perm = (g->identity_order || !g->perm.p) ? nullptr : g->perm.as<int>();
-    return launch_normalize_export(beta_dev, ld, perm, (int)g->n, g->n_slices, K, beta_out_dev, prop_out_dev, (hipStream_t)stream);
+    return launch_normalize_export(beta_dev, ld, caller_order_perm(g), (int)g->n, g->n_slices, K, beta_out_dev, prop_out_dev,
+                                   (hipStream_t)stream);
 }
 
 int fdx_normalize_dev(const double* beta_dev, int64_t ld, int64_t n, int32_t K, double* beta_out_dev, double* prop_out_dev,

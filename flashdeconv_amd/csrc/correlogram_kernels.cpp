@@ -259,9 +259,7 @@ extern "C" int fdx_spatial_correlogram_dev(const double* coords_dev, int64_t n, 
     if (bands_per_pass_out) *bands_per_pass_out = 0;
     if (candidates_out) *candidates_out = 0;
     if (n == 0) {                                       // no spots: no mean
-        std::fill(mean, mean + K, std::nan(""));
-        std::fill(m2, m2 + K, 0.0);
-        if (m4) std::fill(m4, m4 + K, 0.0);
+        SpatialSumsLayout(K).fill_empty(mean, m2, nullptr, m4);
         std::fill(C, C + (size_t)B * KK, 0.0);
         return 0;
     }

@@ -101,6 +101,16 @@ struct fdx_graph {
 
 namespace fdx {
 int graph_meta_sync(const fdx_graph* g);         // no-op unless a deferred build is outstanding
+// The caller-order rule: position p of the graph's order holds the caller's spot perm[p]; null where the two orders are the same.
+inline const int* caller_order_perm(const fdx_graph* g) { return (g->identity_order || !g->perm.p) ? nullptr : g->perm.as<int>(); }
+// The device tables of a WHOLE graph, as the analysis kernels read them (the pad index of the ELL is n).
+struct GraphTables {
+    const int *ell, *slice_off, *deg, *perm;     // perm: caller_order_perm
+    int n;
+};
+// Checks g for an entry named `who` and fills *out: not null, its deferred build complete (graph_meta_sync), no shard's local
+// graph, fewer than 2^31 - 128 spots, and device tables wherever there are spots.
+int whole_graph_tables(const fdx_graph* g, const char* who, GraphTables* out);
 void graph_release(fdx_graph* g);                // one holder less; the last one deletes
 // ---- graph_cache.cpp: whole graphs by content of the coordinates (FDX_NO_PLAN_CACHE bypasses, fdx_trim drops)
 bool graph_cache_enabled();

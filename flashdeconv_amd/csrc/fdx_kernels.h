@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/fdx.h"
+#include "spatial_sums.h"
 
 #include <cstddef>
 #include <cstdint>
@@ -130,7 +131,8 @@ int launch_spot_diagnostics(const double* beta, long long ld, const double* H, l
                             const double* row_sq, const int* ell, const int* slice_off, const int* deg, const int* perm, int n,
                             int n_slices, int K, double* out, hipStream_t st);
 
-// ---- spatial_stats_kernels.cpp
+// ---- spatial_stats_kernels.cpp (the entries of local_stats_kernels.cpp and correlogram_kernels.cpp build on it)
+struct GraphTables;              // fdx_graph.h: the device tables of a whole graph
 // Sizes and grids of one spatial-statistics call on n spots and K columns (functions of n and K only).
 struct SpatialStatsPlan {
     long long ld;                // row stride of the Z and lag planes: n + 1 rounded up to 64
@@ -138,36 +140,16 @@ struct SpatialStatsPlan {
     int colsum_blocks, rows_per_block, centre_blocks, lag_blocks, cross_blocks, pair_tiles_1d;
     size_t partials_doubles;     // largest partials block of the four passes
     size_t scratch_doubles;      // Z and lag planes (K, ld) each, then the partials
-    size_t out_doubles;          // [mean K | m2 K | C K*K | sum deg, sum deg^2 as int64]
+    SpatialSumsLayout sums;      // the packed result on the device: sums.observed_doubles doubles
 };
 SpatialStatsPlan spatial_stats_plan(long long n, int K);
-// V (n, K) row-major with row stride ldv in the caller's spot order; perm null: the graph keeps that order.  out (device) as laid
-// out above; nbr_mean (n, K) row-major in the caller's order, or null.  The graph must be whole (pad index n).
-int launch_spatial_stats(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* ell,
-                         const int* slice_off, const int* deg, const int* perm, double* scratch, double* out, double* nbr_mean,
-                         hipStream_t st);
-// A permutation-null call (fdx_spatial_perm_dev): the observed plan, the batch B of permutations per launch chain - what a scratch
-// budget of 1 GiB holds, 512 at the most, capped by max_batch (0: no cap) and n_perm, one at the least - and its buffers.
-struct SpatialPermPlan {
-    SpatialStatsPlan s;
-    int batch;
-    size_t plane_doubles;        // K * ld: the Z (and lag) planes of one batch element
-    size_t cross_part_doubles;   // cross partials of one batch element
-    size_t part_doubles;         // partials block: the observed pass's or the batch's cross partials, whichever is larger
-    size_t null_doubles;         // B * K * K when the caller keeps no null (own_null), else 0
-    size_t scratch_doubles;      // [Z B planes | lag B planes | partials | C_r of a batch]
-    size_t out_doubles;          // SpatialStatsPlan's out, then [m4 K | count_ge K*K int64 | count_le K*K int64 | sum_d | sumsq_d]
-};
-SpatialPermPlan spatial_perm_plan(long long n, int K, long long n_perm, int max_batch, bool own_null);
-// The observed pass, m4, then permutations first_perm .. first_perm + n_perm - 1 of `seed` in batches; null_dev (n_perm, K, K)
-// device or null.  Everything is left in out (device) as laid out above.
-int launch_spatial_perm(const SpatialPermPlan& p, const double* V, long long ldv, int n, int K, const int* ell,
-                        const int* slice_off, const int* deg, const int* perm, unsigned long long seed, long long first_perm,
-                        long long n_perm, double* null_dev, double* scratch, double* out, hipStream_t st);
-// out[i] = pi_r(i), i < n: the permutation the kernels above apply
-int launch_permutation_indices(unsigned long long seed, long long r, int n, int* out, hipStream_t st);
+// The observed pass.  V (g.n, K) row-major with row stride ldv in the caller's spot order; scratch laid out for `batch` sets of
+// planes (1: s.scratch_doubles); out (device) as s.sums lays it out; nbr_mean (n, K) row-major in the caller's order, or null; m4
+// (K, device; sum Z^4), or null.
+int launch_spatial_stats(const SpatialStatsPlan& s, const double* V, long long ldv, int K, const GraphTables& g, double* scratch,
+                         int batch, double* out, double* nbr_mean, double* m4, hipStream_t st);
 
-// What correlogram_kernels.cpp takes from the kernels above (they stay in spatial_stats_kernels.cpp).
+// What correlogram_kernels.cpp takes from the kernels of spatial_stats_kernels.cpp.
 size_t spatial_scratch_budget_bytes();       // the permutation batches' scratch budget (1 GiB)
 // column sums -> mean, centre -> Z (K, s.ld) in the order `perm` gives (null: the caller's) and m2, m4 (null: not computed) from Z;
 // part: s.partials_doubles doubles.  mean, m2, m4 on the device.
@@ -192,41 +174,6 @@ struct CorrelogramPlan {
     size_t scratch_doubles;      // [Z K planes | lag bands_per_pass * K planes | partials]
 };
 CorrelogramPlan correlogram_plan(long long n, int K, int B, int max_bands_per_pass);
-
-// ---- local_stats_kernels.cpp
-// Per-spot neighbour sums and their conditional-permutation null (fdx_local_stats_dev), behind the observed pass of
-// launch_spatial_stats on the same scratch and out (mean, m2 and the counts are that pass's).  nbr_sum (n, K) float64 and
-// deg_out (n) int32 in the caller's spot order; with n_perm > 0 count_ge, count_le (n, K) int32 and sum_d, sumsq_d (n, K)
-// float64 over conditional permutations first_perm .. first_perm + n_perm - 1 of `seed`, overwritten.
-int launch_local_stats(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* ell,
-                       const int* slice_off, const int* deg, const int* perm, unsigned long long seed, long long first_perm,
-                       int n_perm, double* scratch, double* out, double* nbr_sum, int* deg_out, int* count_ge, int* count_le,
-                       double* sum_d, double* sumsq_d, hipStream_t st);
-// out[t] = the t-th of the `count` spots drawn for `spot` in conditional permutation r (0 <= count <= n - 1)
-int launch_conditional_indices(unsigned long long seed, long long r, int spot, int n, int count, int* out, hipStream_t st);
-
-// ---- niche_kernels.cpp
-// Grids and scratch of the k-means kernels on n rows, D columns and C centres (functions of the shapes only).
-struct KmeansPlan {
-    int dist_blocks;             // workgroups of the assign / seed-distance kernel: 256 rows each
-    int seed_per, seed_blocks;   // seed distance: workgroups per block of seed_rows rows, and how many such blocks (<= 1024)
-    long long seed_rows;
-    int sums_blocks, rows_per_block;   // label sums
-    size_t dist_part_bytes;      // scratch of an assign / seed-distance launch
-    size_t sums_part_bytes;      // scratch of a label-sums launch
-};
-KmeansPlan kmeans_plan(long long n, int D, int C);
-// labels[i] = arg-min over c of d2(i, c) (smallest c), min_d2 (may be null); to the device: changed_out[0] = rows whose label
-// differs from the previous content of labels, inertia_out[0] = sum_i d2(i, label_i).
-int launch_kmeans_assign(const KmeansPlan& p, const double* F, long long ldf, int n, int D, const double* M, int C, int* labels,
-                         double* min_d2, void* dist_part, long long* changed_out, double* inertia_out, hipStream_t st);
-// d2[i] = min(d2[i], d2(i, m)); block_sums[b] (device, p.seed_blocks of them) = sum of d2 over rows [b * seed_rows, ...).
-int launch_kmeans_seed_dist(const KmeansPlan& p, const double* F, long long ldf, int n, int D, const double* m, double* d2,
-                            void* dist_part, double* block_sums, hipStream_t st);
-// sums (C, D) and counts (C) per label (device); F null: counts only (sums untouched).  centres (may be null): rows with a
-// positive count become sums / counts.  The plan's C and D must be the ones passed here.
-int launch_label_sums(const KmeansPlan& p, const double* F, long long ldf, const int* labels, int n, int D, int C, void* sums_part,
-                      double* sums, long long* counts, double* centres, hipStream_t st);
 
 // ---- expression_kernels.cpp
 // Weighted gene sums (fdx_weighted_gene_sums_dev / _csr_dev): the rows of a group, in the order of the sorted row list, are cut into

@@ -640,6 +640,18 @@ int graph_meta_sync(const fdx_graph* gc) {
     return 0;
 }
 
+int whole_graph_tables(const fdx_graph* g, const char* who, GraphTables* out) {
+    const std::string w(who);
+    FDX_REQUIRE(g != nullptr, w + ": null argument");
+    FDX_TRY(graph_meta_sync(g));
+    FDX_REQUIRE(!g->shard_pending && g->n_total == g->n && g->world_n == 0,
+                w + ": a shard's local graph is refused (whole graphs on one GPU only)");
+    FDX_REQUIRE(g->n < (1LL << 31) - 128, w + ": too many spots");
+    FDX_REQUIRE(g->n == 0 || (g->ell.p && g->slice_off.p && g->deg.p), w + ": the graph has no device tables");
+    *out = GraphTables{g->ell.as<int>(), g->slice_off.as<int>(), g->deg.as<int>(), caller_order_perm(g), (int)g->n};
+    return 0;
+}
+
 int graph_build_knn(const double* d_coords, long long n, int dim, int k, fdx_graph* g, hipStream_t st, const GraphBuildHooks* hooks) {
     FDX_REQUIRE(dim >= 1 && dim <= FDX_KNN_MAX_DIM, "graph: k-NN graphs take coordinates of 1 to 8 dimensions");
     FDX_REQUIRE(n >= 0 && n < 0x7fffff00LL, "graph: n out of range");
@@ -741,7 +753,7 @@ int graph_export_csr(const fdx_graph* g, long long* d_indptr, int* d_indices, hi
 
 int graph_copy_perm(const fdx_graph* g, int* d_out, hipStream_t st) {
     if (g->n == 0) return 0;
-    if (g->identity_order || !g->perm.p) {
+    if (!caller_order_perm(g)) {
         hipLaunchKernelGGL(iota_kernel, dim3(ceil_div(g->n, 256)), dim3(256), 0, st, d_out, g->n);
         FDX_CHECK_LAUNCH();
     } else {

@@ -1,4 +1,4 @@
-// Host-only exerciser of the schedule builders (tile_plan.cpp) for the sanitizer build: `make -C flashdeconv_amd/csrc asan-host`
+// Host-only exerciser of the schedule builders (tile_plan.cpp) and of the packed spatial-sums layout (spatial_sums.h) for the sanitizer build: `make -C flashdeconv_amd/csrc asan-host`
 // compiles this file and tile_plan.cpp with g++ -fsanitize=address,undefined and runs it.  No HIP, no GPU.
 // (GPU AddressSanitizer is not available on the build pool; the pure-host parts of the library are what can be sanitised.)
 #include <cstdio>
@@ -6,6 +6,7 @@
 #include <random>
 #include <vector>
 
+#include "../spatial_sums.h"
 #include "../tile_plan.h"
 
 using namespace fdx;
@@ -42,8 +43,44 @@ static int check_tile(int G, int d, int NW, int JW, int GB, unsigned seed) {
     return 0;
 }
 
+// the offsets tile [0, perm_doubles) without gap or overlap, and a block holding its own indices unpacks into arrays that are exactly
+// as long as their slices (a copy that runs over ends in a redzone), each receiving its slice
+static int check_spatial_sums(int K) {
+    const SpatialSumsLayout L(K);
+    const size_t k = (size_t)K, kk = k * k;
+    const size_t at[] = {L.mean, L.m2, L.C, L.deg_sums, L.m4, L.count_ge, L.count_le, L.sum_d, L.sumsq_d, L.perm_doubles};
+    const size_t len[] = {k, k, kk, 2, k, kk, kk, kk, kk};
+    if (at[0] != 0 || L.observed_doubles != L.m4) return 1;
+    for (int i = 0; i < 9; ++i)
+        if (at[i] + len[i] != at[i + 1]) return 2;
+    std::vector<double> h(L.perm_doubles), mean(k), m2(k), C(kk), m4(k), sd(kk), sq(kk);
+    std::vector<int64_t> deg(2), ge(kk), le(kk);
+    for (size_t i = 0; i < h.size(); ++i) {
+        const bool is_int = (i >= L.deg_sums && i < L.m4) || (i >= L.count_ge && i < L.sum_d);
+        const int64_t v = (int64_t)i;
+        if (is_int) std::memcpy(&h[i], &v, 8);
+        else h[i] = (double)i;
+    }
+    L.unpack(h.data(), mean.data(), m2.data(), C.data(), deg.data(), m4.data(), ge.data(), le.data(), sd.data(), sq.data());
+    for (size_t i = 0; i < k; ++i)
+        if (mean[i] != (double)(L.mean + i) || m2[i] != (double)(L.m2 + i) || m4[i] != (double)(L.m4 + i)) return 3;
+    for (size_t i = 0; i < kk; ++i)
+        if (C[i] != (double)(L.C + i) || sd[i] != (double)(L.sum_d + i) || sq[i] != (double)(L.sumsq_d + i) ||
+            ge[i] != (int64_t)(L.count_ge + i) || le[i] != (int64_t)(L.count_le + i))
+            return 4;
+    if (deg[0] != (int64_t)L.deg_sums || deg[1] != (int64_t)L.deg_sums + 1) return 5;
+    h.resize(L.observed_doubles);                      // an observed block alone, C left out; then the answers without spots
+    L.unpack(h.data(), mean.data(), m2.data(), nullptr, deg.data());
+    L.fill_empty(mean.data(), m2.data(), C.data(), m4.data());
+    return mean[0] == mean[0] || m2[k - 1] != 0.0 || C[kk - 1] != 0.0 || m4[k - 1] != 0.0 ? 6 : 0;
+}
+
 int main() {
     int bad = 0;
+    for (int K : {1, 4, 33}) {
+        const int rc = check_spatial_sums(K);
+        if (rc) { std::printf("spatial sums layout K=%d: error %d\n", K, rc); ++bad; }
+    }
     const int shapes[][5] = {{2000, 512, 16, 8, 768}, {2000, 512, 12, 11, 1024}, {5000, 1024, 12, 22, 736}, {5003, 1024, 8, 32, 512},
                              {300, 64, 16, 8, 512}, {40, 7, 16, 8, 256}, {1001, 500, 8, 16, 256}, {2000, 600, 12, 11, 1024}};
     for (const auto& s : shapes)
@@ -51,6 +88,6 @@ int main() {
             const int rc = check_tile(s[0], s[1], s[2], s[3], s[4], seed);
             if (rc) { std::printf("tile plan G=%d d=%d NW=%d JW=%d GB=%d seed=%u: error %d\n", s[0], s[1], s[2], s[3], s[4], seed, rc); ++bad; }
         }
-    std::printf(bad ? "FAILED\n" : "plan builders: ok under the sanitizers\n");
+    std::printf(bad ? "FAILED\n" : "plan builders and sums layout: ok under the sanitizers\n");
     return bad ? 1 : 0;
 }

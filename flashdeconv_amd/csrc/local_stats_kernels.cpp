@@ -24,11 +24,13 @@
 //                    are counted by ballot and popcount.  No floating-point atomics, no LDS, no per-lane array indexed at run
 //                    time, any degree (a hub of degree n - 1 just loops longer).  The grid is a function of n only and no
 //                    result depends on it.
+#include "fdx_graph.h"
 #include "fdx_internal.h"
 #include "fdx_kernels.h"
 #include "perm_device.h"
 
 #include <algorithm>
+#include <vector>
 
 namespace fdx {
 
@@ -167,36 +169,73 @@ __global__ __launch_bounds__(64) void ls_cond_indices_kernel(unsigned long long 
     ls_draw(key, spot, n, count, wl, wr, [&](int slot, int c) { out[slot] = c; });
 }
 
-int launch_local_stats(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* ell,
-                       const int* slice_off, const int* deg, const int* perm, unsigned long long seed, long long first_perm,
-                       int n_perm, double* scratch, double* out, double* nbr_sum, int* deg_out, int* count_ge, int* count_le,
-                       double* sum_d, double* sumsq_d, hipStream_t st) {
-    if (n <= 0) return 0;
-    FDX_TRY(launch_spatial_stats(s, V, ldv, n, K, ell, slice_off, deg, perm, scratch, out, nullptr, st));
-    hipLaunchKernelGGL(ls_nbr_sum_kernel, dim3(s.lag_blocks), dim3(256), 0, st, V, ldv, ell, slice_off, deg, perm, n, s.n_slices, K,
-                       nbr_sum, deg_out);
-    FDX_CHECK_LAUNCH();
-    if (n_perm <= 0) return 0;
-    LsPermArgs pa;
-    pa.seed_mixed = ss_mix64(seed);
-    pa.first = first_perm;
-    pa.n_perm = n_perm;
-    ss_feistel_widths(n, &pa.wl, &pa.wr);
-    const int blocks = std::min(LS_CAP_BLOCKS, ceil_div(n, 4));
-    hipLaunchKernelGGL(ls_cond_null_kernel, dim3(blocks), dim3(256), 0, st, V, ldv, n, K, deg_out, nbr_sum, pa, count_ge, count_le,
-                       sum_d, sumsq_d);
-    FDX_CHECK_LAUNCH();
-    return 0;
-}
-
-int launch_conditional_indices(unsigned long long seed, long long r, int spot, int n, int count, int* out, hipStream_t st) {
-    if (count <= 0) return 0;
-    int wl, wr;
-    ss_feistel_widths(n, &wl, &wr);
-    hipLaunchKernelGGL(ls_cond_indices_kernel, dim3(1), dim3(64), 0, st, ls_cond_key(ss_perm_key(ss_mix64(seed), r), spot), spot, n,
-                       count, wl, wr, out);
-    FDX_CHECK_LAUNCH();
-    return 0;
-}
-
 }  // namespace fdx
+
+using namespace fdx;
+
+extern "C" {
+
+// Behind the observed pass of launch_spatial_stats (mean, m2 and the counts are that pass's): nbr_sum (n, K) float64 and deg (n)
+// int32 in the caller's spot order; with n_perm > 0 count_ge, count_le (n, K) int32 and sum_d, sumsq_d (n, K) float64 over
+// conditional permutations first_perm .. first_perm + n_perm - 1 of `seed`, overwritten.
+int fdx_local_stats_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, int32_t K, uint64_t seed, int64_t first_perm,
+                        int64_t n_perm, double* nbr_sum_dev, int32_t* deg_dev, int32_t* count_ge_dev, int32_t* count_le_dev,
+                        double* sum_d_dev, double* sumsq_d_dev, double* mean_out, double* m2_out, int64_t* counts_out,
+                        void* stream) {
+    FDX_REQUIRE(g && V_dev && nbr_sum_dev && deg_dev && mean_out && m2_out && counts_out, "fdx_local_stats_dev: null argument");
+    FDX_REQUIRE(K >= 1 && ldv >= K, "fdx_local_stats_dev: K must be positive and ldv at least K");
+    FDX_REQUIRE(first_perm >= 0 && n_perm >= 0, "fdx_local_stats_dev: first_perm and n_perm must not be negative");
+    FDX_REQUIRE(n_perm < (1LL << 31), "fdx_local_stats_dev: n_perm must be below 2^31");
+    FDX_REQUIRE(n_perm == 0 || (count_ge_dev && count_le_dev && sum_d_dev && sumsq_d_dev),
+                "fdx_local_stats_dev: null argument (the permutation outputs may be null only with n_perm == 0)");
+    GraphTables t;
+    FDX_TRY(whole_graph_tables(g, "fdx_local_stats_dev", &t));
+    hipStream_t st = (hipStream_t)stream;
+    PoolStream pool_stream(st);
+    counts_out[0] = t.n;
+    counts_out[1] = counts_out[2] = 0;
+    if (t.n == 0) {                                     // no row to write
+        SpatialSumsLayout(K).fill_empty(mean_out, m2_out, nullptr);
+        return 0;
+    }
+    const SpatialStatsPlan plan = spatial_stats_plan(t.n, K);
+    DevBuf scratch, out;
+    FDX_TRY(scratch.alloc(plan.scratch_doubles * sizeof(double)));
+    FDX_TRY(out.alloc(plan.sums.observed_doubles * sizeof(double)));
+    FDX_TRY(launch_spatial_stats(plan, V_dev, ldv, K, t, scratch.as<double>(), 1, out.as<double>(), nullptr, nullptr, st));
+    hipLaunchKernelGGL(ls_nbr_sum_kernel, dim3(plan.lag_blocks), dim3(256), 0, st, V_dev, ldv, t.ell, t.slice_off, t.deg, t.perm, t.n,
+                       plan.n_slices, K, nbr_sum_dev, deg_dev);
+    FDX_CHECK_LAUNCH();
+    if (n_perm > 0) {
+        LsPermArgs pa;
+        pa.seed_mixed = ss_mix64(seed);
+        pa.first = first_perm;
+        pa.n_perm = (int)n_perm;
+        ss_feistel_widths(t.n, &pa.wl, &pa.wr);
+        hipLaunchKernelGGL(ls_cond_null_kernel, dim3(std::min(LS_CAP_BLOCKS, ceil_div(t.n, 4))), dim3(256), 0, st, V_dev, ldv, t.n, K,
+                           deg_dev, nbr_sum_dev, pa, count_ge_dev, count_le_dev, sum_d_dev, sumsq_d_dev);
+        FDX_CHECK_LAUNCH();
+    }
+    std::vector<double> host(plan.sums.observed_doubles);
+    FDX_TRY(copy_d2h(host.data(), out.p, host.size() * sizeof(double), st));   // the call's one host synchronisation
+    plan.sums.unpack(host.data(), mean_out, m2_out, nullptr, counts_out + 1);
+    return 0;
+}
+
+// out_dev[t] = the t-th of the `count` spots drawn for `spot` in conditional permutation r
+int fdx_conditional_indices_dev(uint64_t seed, int64_t r, int64_t spot, int64_t n, int64_t count, int32_t* out_dev, void* stream) {
+    FDX_REQUIRE(n >= 1 && n < (1LL << 31) - 128, "fdx_conditional_indices_dev: n must be between 1 and 2^31 - 129");
+    FDX_REQUIRE(r >= 0, "fdx_conditional_indices_dev: r must not be negative");
+    FDX_REQUIRE(spot >= 0 && spot < n, "fdx_conditional_indices_dev: spot must be in [0, n)");
+    FDX_REQUIRE(count >= 0 && count <= n - 1, "fdx_conditional_indices_dev: count must be between 0 and n - 1");
+    FDX_REQUIRE(count == 0 || out_dev, "fdx_conditional_indices_dev: null argument");
+    if (count == 0) return 0;
+    int wl, wr;
+    ss_feistel_widths((int)n, &wl, &wr);
+    hipLaunchKernelGGL(ls_cond_indices_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream,
+                       ls_cond_key(ss_perm_key(ss_mix64(seed), r), (int)spot), (int)spot, (int)n, (int)count, wl, wr, out_dev);
+    FDX_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // extern "C"

@@ -23,6 +23,8 @@
 #include "fdx_kernels.h"
 
 #include <algorithm>
+#include <string>
+#include <vector>
 
 namespace fdx {
 
@@ -211,7 +213,17 @@ __global__ __launch_bounds__(256) void km_reduce_sums_kernel(const double* __res
     if (centres && cnt > 0) centres[i] = s / (double)cnt;
 }
 
-KmeansPlan kmeans_plan(long long n, int D, int C) {
+// Grids and scratch of the k-means kernels on n rows, D columns and C centres (functions of the shapes only).
+struct KmeansPlan {
+    int dist_blocks;             // workgroups of the assign / seed-distance kernel: 256 rows each
+    int seed_per, seed_blocks;   // seed distance: workgroups per block of seed_rows rows, and how many such blocks (<= 1024)
+    long long seed_rows;
+    int sums_blocks, rows_per_block;   // label sums
+    size_t dist_part_bytes;      // scratch of an assign / seed-distance launch
+    size_t sums_part_bytes;      // scratch of a label-sums launch
+};
+
+static KmeansPlan kmeans_plan(long long n, int D, int C) {
     KmeansPlan p;
     p.dist_blocks = std::max(1, ceil_div(n, KM_ROWS));
     p.seed_per = std::max(1, ceil_div(p.dist_blocks, KM_SEED_CAP));
@@ -240,8 +252,10 @@ static int launch_dist(const KmeansPlan& p, const double* F, long long ldf, int 
     return 0;
 }
 
-int launch_kmeans_assign(const KmeansPlan& p, const double* F, long long ldf, int n, int D, const double* M, int C, int* labels,
-                         double* min_d2, void* dist_part, long long* changed_out, double* inertia_out, hipStream_t st) {
+// labels[i] = arg-min over c of d2(i, c) (smallest c), min_d2 (may be null); to the device: changed_out[0] = rows whose label
+// differs from the previous content of labels, inertia_out[0] = sum_i d2(i, label_i).
+static int launch_kmeans_assign(const KmeansPlan& p, const double* F, long long ldf, int n, int D, const double* M, int C,
+                                int* labels, double* min_d2, void* dist_part, long long* changed_out, double* inertia_out, hipStream_t st) {
     double* sum_part = reinterpret_cast<double*>(dist_part);
     long long* changed_part = reinterpret_cast<long long*>(sum_part + p.dist_blocks);
     if (C <= 8) FDX_TRY((launch_dist<8, false>(p, F, ldf, n, D, M, C, labels, min_d2, nullptr, changed_part, sum_part, st)));
@@ -252,8 +266,9 @@ int launch_kmeans_assign(const KmeansPlan& p, const double* F, long long ldf, in
     return 0;
 }
 
-int launch_kmeans_seed_dist(const KmeansPlan& p, const double* F, long long ldf, int n, int D, const double* m, double* d2,
-                            void* dist_part, double* block_sums, hipStream_t st) {
+// d2[i] = min(d2[i], d2(i, m)); block_sums[b] (device, p.seed_blocks of them) = sum of d2 over rows [b * seed_rows, ...).
+static int launch_kmeans_seed_dist(const KmeansPlan& p, const double* F, long long ldf, int n, int D, const double* m,
+                                   double* d2, void* dist_part, double* block_sums, hipStream_t st) {
     double* sum_part = reinterpret_cast<double*>(dist_part);
     FDX_TRY((launch_dist<1, true>(p, F, ldf, n, D, m, 1, nullptr, nullptr, d2, nullptr, sum_part, st)));
     hipLaunchKernelGGL(km_reduce_parts_kernel, dim3(p.seed_blocks), dim3(256), 0, st, sum_part, (const long long*)nullptr,
@@ -262,8 +277,10 @@ int launch_kmeans_seed_dist(const KmeansPlan& p, const double* F, long long ldf,
     return 0;
 }
 
-int launch_label_sums(const KmeansPlan& p, const double* F, long long ldf, const int* labels, int n, int D, int C, void* sums_part,
-                      double* sums, long long* counts, double* centres, hipStream_t st) {
+// sums (C, D) and counts (C) per label (device); F null: counts only (sums untouched).  centres (may be null): rows with a
+// positive count become sums / counts.  The plan's C and D must be the ones passed here.
+static int launch_label_sums(const KmeansPlan& p, const double* F, long long ldf, const int* labels, int n, int D, int C,
+                             void* sums_part, double* sums, long long* counts, double* centres, hipStream_t st) {
     double* partials = reinterpret_cast<double*>(sums_part);
     long long* cnt_partials = reinterpret_cast<long long*>(partials + (size_t)p.sums_blocks * C * D);
     const size_t lds = (size_t)C * 256 * sizeof(double);
@@ -280,3 +297,121 @@ int launch_label_sums(const KmeansPlan& p, const double* F, long long ldf, const
 }
 
 }  // namespace fdx
+
+using namespace fdx;
+
+// the shape checks the k-means entries share; `who` names the entry in the message
+static int kmeans_check_shape(const char* who, int64_t ldf, int64_t n, int32_t D, int32_t C, bool centres_are_rows) {
+    const std::string w(who);
+    FDX_REQUIRE(D >= 1, w + ": D must be positive");
+    FDX_REQUIRE(ldf >= D, w + ": ldf must be at least D");
+    FDX_REQUIRE(C >= 1 && C <= 64, w + ": C must be between 1 and 64");
+    FDX_REQUIRE(n >= 0 && n < (1LL << 31) - 128, w + ": too many rows");
+    if (centres_are_rows) FDX_REQUIRE(C <= n, w + ": C must not exceed n");
+    return 0;
+}
+
+extern "C" {
+
+int fdx_kmeans_assign_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, const double* centres_dev, int32_t C,
+                          int32_t* labels_dev, double* min_d2_dev, int64_t* changed_out, double* inertia_out, void* stream) {
+    FDX_REQUIRE(F_dev && centres_dev && labels_dev && changed_out && inertia_out, "fdx_kmeans_assign_dev: null argument");
+    FDX_TRY(kmeans_check_shape("fdx_kmeans_assign_dev", ldf, n, D, C, true));
+    hipStream_t st = (hipStream_t)stream;
+    PoolStream pool_stream(st);
+    const KmeansPlan plan = kmeans_plan(n, D, C);
+    DevBuf part, out;
+    FDX_TRY(part.alloc(plan.dist_part_bytes));
+    FDX_TRY(out.alloc(16));
+    FDX_TRY(launch_kmeans_assign(plan, F_dev, ldf, (int)n, D, centres_dev, C, labels_dev, min_d2_dev, part.p, out.as<long long>(),
+                                 out.as<double>() + 1, st));
+    unsigned char host[16];
+    FDX_TRY(copy_d2h(host, out.p, 16, st));            // the call's one host synchronisation
+    std::memcpy(changed_out, host, 8);
+    std::memcpy(inertia_out, host + 8, 8);
+    return 0;
+}
+
+int fdx_label_sums_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, const int32_t* labels_dev, int32_t C,
+                       double* sums_out, int64_t* counts_out, void* stream) {
+    FDX_REQUIRE(sums_out && counts_out && (n == 0 || (F_dev && labels_dev)), "fdx_label_sums_dev: null argument");
+    FDX_TRY(kmeans_check_shape("fdx_label_sums_dev", ldf, n, D, C, false));
+    const size_t CD = (size_t)C * D;
+    std::fill(sums_out, sums_out + CD, 0.0);
+    std::fill(counts_out, counts_out + C, (int64_t)0);
+    if (n == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    PoolStream pool_stream(st);
+    const KmeansPlan plan = kmeans_plan(n, D, C);
+    DevBuf part, out;
+    FDX_TRY(part.alloc(plan.sums_part_bytes));
+    FDX_TRY(out.alloc((CD + C) * 8));
+    FDX_TRY(launch_label_sums(plan, F_dev, ldf, labels_dev, (int)n, D, C, part.p, out.as<double>(),
+                              reinterpret_cast<long long*>(out.as<double>() + CD), nullptr, st));
+    std::vector<double> host(CD + C);
+    FDX_TRY(copy_d2h(host.data(), out.p, (CD + C) * 8, st));
+    std::copy(host.begin(), host.begin() + CD, sums_out);
+    std::memcpy(counts_out, host.data() + CD, (size_t)C * 8);
+    return 0;
+}
+
+int fdx_kmeans_seed_dist_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, const double* centre_dev, double* d2_dev,
+                             double* block_sums_out, int64_t* block_rows_out, int32_t* n_blocks_out, void* stream) {
+    FDX_REQUIRE(F_dev && centre_dev && d2_dev && block_sums_out && block_rows_out && n_blocks_out,
+                "fdx_kmeans_seed_dist_dev: null argument");
+    FDX_TRY(kmeans_check_shape("fdx_kmeans_seed_dist_dev", ldf, n, D, 1, true));
+    hipStream_t st = (hipStream_t)stream;
+    PoolStream pool_stream(st);
+    const KmeansPlan plan = kmeans_plan(n, D, 1);
+    DevBuf part, out;
+    FDX_TRY(part.alloc(plan.dist_part_bytes));
+    FDX_TRY(out.alloc((size_t)plan.seed_blocks * 8));
+    FDX_TRY(launch_kmeans_seed_dist(plan, F_dev, ldf, (int)n, D, centre_dev, d2_dev, part.p, out.as<double>(), st));
+    FDX_TRY(copy_d2h(block_sums_out, out.p, (size_t)plan.seed_blocks * 8, st));
+    *block_rows_out = plan.seed_rows;
+    *n_blocks_out = plan.seed_blocks;
+    return 0;
+}
+
+int fdx_kmeans_dev(const double* F_dev, int64_t ldf, int64_t n, int32_t D, int32_t C, int32_t max_iter, double* centres_dev,
+                   int32_t* labels_dev, int64_t* counts_out, double* inertia_out, int32_t* n_iter_out, int32_t* converged_out,
+                   void* stream) {
+    FDX_REQUIRE(F_dev && centres_dev && labels_dev && counts_out && inertia_out && n_iter_out && converged_out,
+                "fdx_kmeans_dev: null argument");
+    FDX_TRY(kmeans_check_shape("fdx_kmeans_dev", ldf, n, D, C, true));
+    FDX_REQUIRE(max_iter >= 1, "fdx_kmeans_dev: max_iter must be positive");
+    hipStream_t st = (hipStream_t)stream;
+    PoolStream pool_stream(st);
+    const KmeansPlan plan = kmeans_plan(n, D, C);
+    const size_t CD = (size_t)C * D;
+    DevBuf dist_part, sums_part, out;
+    FDX_TRY(dist_part.alloc(plan.dist_part_bytes));
+    FDX_TRY(sums_part.alloc(plan.sums_part_bytes));
+    FDX_TRY(out.alloc(16 + (CD + C) * 8));               // [changed | inertia | sums C*D | counts C]
+    long long* changed_d = out.as<long long>();
+    double* inertia_d = out.as<double>() + 1;
+    double* sums_d = out.as<double>() + 2;
+    long long* counts_d = reinterpret_cast<long long*>(sums_d + CD);
+    FDX_HIP(hipMemsetAsync(labels_dev, 0xFF, (size_t)n * sizeof(int32_t), st));      // every label -1
+    int it = 0, converged = 0;
+    unsigned char host[16];
+    for (;;) {
+        ++it;
+        FDX_TRY(launch_kmeans_assign(plan, F_dev, ldf, (int)n, D, centres_dev, C, labels_dev, nullptr, dist_part.p, changed_d,
+                                     inertia_d, st));
+        FDX_TRY(copy_d2h(host, out.p, 16, st));          // 16 bytes per iteration: the loop's only host synchronisation
+        int64_t changed;
+        std::memcpy(&changed, host, 8);
+        if (changed == 0) { converged = 1; break; }
+        if (it == max_iter) break;
+        FDX_TRY(launch_label_sums(plan, F_dev, ldf, labels_dev, (int)n, D, C, sums_part.p, sums_d, counts_d, centres_dev, st));
+    }
+    FDX_TRY(launch_label_sums(plan, nullptr, ldf, labels_dev, (int)n, D, C, sums_part.p, sums_d, counts_d, nullptr, st));
+    FDX_TRY(copy_d2h(counts_out, counts_d, (size_t)C * 8, st));
+    std::memcpy(inertia_out, host + 8, 8);
+    *n_iter_out = it;
+    *converged_out = converged;
+    return 0;
+}
+
+}  // extern "C"

@@ -30,11 +30,13 @@
 // pi_r is a keyed bijection of [0, n): an unbalanced Feistel network of 8 rounds on b = max(2, bit_length(n - 1)) bits (left half
 // b / 2 bits, right half the rest, the widths swap every round), the round function the splitmix64 finaliser, values >= n walked
 // along their cycle until they fall below n (perm_device.h).  utils/spatial_stats.py:permutation_indices is its definition.
+#include "fdx_graph.h"
 #include "fdx_internal.h"
 #include "fdx_kernels.h"
 #include "perm_device.h"
 
 #include <algorithm>
+#include <vector>
 
 namespace fdx {
 
@@ -348,24 +350,22 @@ SpatialStatsPlan spatial_stats_plan(long long n, int K) {
     s.partials_doubles = std::max({(size_t)s.colsum_blocks * K, (size_t)s.centre_blocks * K, (size_t)s.cross_blocks * KK,
                                    (size_t)s.lag_blocks * 2});
     s.scratch_doubles = 2 * (size_t)K * s.ld + s.partials_doubles;
-    s.out_doubles = 2 * (size_t)K + KK + 2;
+    s.sums = SpatialSumsLayout(K);
     return s;
 }
 
 template <int KC>
-static void launch_lag(const SpatialStatsPlan& s, int batch, long long batch_stride, const double* Z, const int* ell,
-                       const int* slice_off, const int* deg, const int* perm, const double* mean, int n, int K, double* lag,
-                       double* nbr_mean, long long* deg_part, hipStream_t st) {
-    hipLaunchKernelGGL(ss_lag_kernel<KC>, dim3(s.lag_blocks, batch), dim3(256), 0, st, Z, s.ld, ell, slice_off, deg, perm, mean, n,
-                       s.n_slices, K, lag, nbr_mean, deg_part, batch_stride);
+static void launch_lag(const SpatialStatsPlan& s, int batch, long long batch_stride, const double* Z, const GraphTables& g,
+                       const double* mean, int K, double* lag, double* nbr_mean, long long* deg_part, hipStream_t st) {
+    hipLaunchKernelGGL(ss_lag_kernel<KC>, dim3(s.lag_blocks, batch), dim3(256), 0, st, Z, s.ld, g.ell, g.slice_off, g.deg, g.perm, mean,
+                       g.n, s.n_slices, K, lag, nbr_mean, deg_part, batch_stride);
 }
 
-static void launch_lag_for(const SpatialStatsPlan& s, int batch, long long batch_stride, const double* Z, const int* ell,
-                           const int* slice_off, const int* deg, const int* perm, const double* mean, int n, int K, double* lag,
-                           double* nbr_mean, long long* deg_part, hipStream_t st) {
-    if (K <= 8) launch_lag<8>(s, batch, batch_stride, Z, ell, slice_off, deg, perm, mean, n, K, lag, nbr_mean, deg_part, st);
-    else if (K <= 16) launch_lag<16>(s, batch, batch_stride, Z, ell, slice_off, deg, perm, mean, n, K, lag, nbr_mean, deg_part, st);
-    else launch_lag<32>(s, batch, batch_stride, Z, ell, slice_off, deg, perm, mean, n, K, lag, nbr_mean, deg_part, st);
+static void launch_lag_for(const SpatialStatsPlan& s, int batch, long long batch_stride, const double* Z, const GraphTables& g,
+                           const double* mean, int K, double* lag, double* nbr_mean, long long* deg_part, hipStream_t st) {
+    if (K <= 8) launch_lag<8>(s, batch, batch_stride, Z, g, mean, K, lag, nbr_mean, deg_part, st);
+    else if (K <= 16) launch_lag<16>(s, batch, batch_stride, Z, g, mean, K, lag, nbr_mean, deg_part, st);
+    else launch_lag<32>(s, batch, batch_stride, Z, g, mean, K, lag, nbr_mean, deg_part, st);
 }
 
 size_t spatial_scratch_budget_bytes() { return SS_PERM_SCRATCH_BYTES; }
@@ -415,20 +415,23 @@ int launch_reduce_i64(const long long* partials, int nparts, long long width, lo
     return 0;
 }
 
-// the four passes of the observed statistics: Z and lag (K, ld) each, part s.partials_doubles; m4 (may be null) = sum Z^4
-static int observed_pass(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* ell,
-                         const int* slice_off, const int* deg, const int* perm, double* Z, double* lag, double* part, double* out,
-                         double* nbr_mean, double* m4, hipStream_t st) {
-    double* mean = out;
-    double* m2 = out + K;
-    double* C = out + 2 * (size_t)K;
-    long long* counts = reinterpret_cast<long long*>(C + (size_t)K * K);
-    const size_t KK = (size_t)K * K;
+// The four passes of the observed statistics.  scratch: Z planes (K, ld) for `batch` elements, as many lag planes - the first of
+// each are used - then s.partials_doubles of partials; m4 (may be null) = sum Z^4.
+int launch_spatial_stats(const SpatialStatsPlan& s, const double* V, long long ldv, int K, const GraphTables& g, double* scratch,
+                         int batch, double* out, double* nbr_mean, double* m4, hipStream_t st) {
+    if (g.n <= 0) return 0;
+    double* Z = scratch;
+    double* lag = Z + (size_t)batch * K * s.ld;
+    double* part = lag + (size_t)batch * K * s.ld;
+    double* mean = out + s.sums.mean;
+    double* C = out + s.sums.C;
+    long long* counts = reinterpret_cast<long long*>(out + s.sums.deg_sums);
+    const size_t KK = s.sums.KK;
 
-    FDX_TRY(launch_spatial_moments(s, V, ldv, n, K, perm, Z, part, mean, m2, m4, st));
+    FDX_TRY(launch_spatial_moments(s, V, ldv, g.n, K, g.perm, Z, part, mean, out + s.sums.m2, m4, st));
 
     long long* deg_part = reinterpret_cast<long long*>(part);
-    launch_lag_for(s, 1, 0, Z, ell, slice_off, deg, perm, mean, n, K, lag, nbr_mean, deg_part, st);
+    launch_lag_for(s, 1, 0, Z, g, mean, K, lag, nbr_mean, deg_part, st);
     FDX_CHECK_LAUNCH();
     hipLaunchKernelGGL(ss_reduce_kernel<long long>, dim3(1), dim3(256), 0, st, deg_part, s.lag_blocks, 2LL, 1LL, counts);
     FDX_CHECK_LAUNCH();
@@ -442,17 +445,20 @@ static int observed_pass(const SpatialStatsPlan& s, const double* V, long long l
     return 0;
 }
 
-int launch_spatial_stats(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* ell,
-                         const int* slice_off, const int* deg, const int* perm, double* scratch, double* out, double* nbr_mean,
-                         hipStream_t st) {
-    if (n <= 0) return 0;
-    double* Z = scratch;
-    double* lag = Z + (size_t)K * s.ld;
-    double* part = lag + (size_t)K * s.ld;
-    return observed_pass(s, V, ldv, n, K, ell, slice_off, deg, perm, Z, lag, part, out, nbr_mean, nullptr, st);
-}
+// A permutation-null call (fdx_spatial_perm_dev): the observed plan, the batch B of permutations per launch chain - what a scratch
+// budget of 1 GiB holds, 512 at the most, capped by max_batch (0: no cap) and n_perm, one at the least - and its buffers.  The
+// packed result is s.sums.perm_doubles doubles.
+struct SpatialPermPlan {
+    SpatialStatsPlan s;
+    int batch;
+    size_t plane_doubles;        // K * ld: the Z (and lag) planes of one batch element
+    size_t cross_part_doubles;   // cross partials of one batch element
+    size_t part_doubles;         // partials block: the observed pass's or the batch's cross partials, whichever is larger
+    size_t null_doubles;         // B * K * K when the caller keeps no null (own_null), else 0
+    size_t scratch_doubles;      // [Z B planes | lag B planes | partials | C_r of a batch]
+};
 
-SpatialPermPlan spatial_perm_plan(long long n, int K, long long n_perm, int max_batch, bool own_null) {
+static SpatialPermPlan spatial_perm_plan(long long n, int K, long long n_perm, int max_batch, bool own_null) {
     SpatialPermPlan p;
     p.s = spatial_stats_plan(n, K);
     const size_t KK = (size_t)K * K;
@@ -468,32 +474,33 @@ SpatialPermPlan spatial_perm_plan(long long n, int K, long long n_perm, int max_
     p.part_doubles = std::max(p.s.partials_doubles, (size_t)B * p.cross_part_doubles);
     p.null_doubles = own_null ? (size_t)B * KK : 0;
     p.scratch_doubles = 2 * (size_t)B * p.plane_doubles + p.part_doubles + p.null_doubles;
-    p.out_doubles = p.s.out_doubles + K + 4 * KK;
     return p;
 }
 
-int launch_spatial_perm(const SpatialPermPlan& p, const double* V, long long ldv, int n, int K, const int* ell,
-                        const int* slice_off, const int* deg, const int* perm, unsigned long long seed, long long first_perm,
-                        long long n_perm, double* null_dev, double* scratch, double* out, hipStream_t st) {
+// The observed pass, m4, then permutations first_perm .. first_perm + n_perm - 1 of `seed` in batches; null_dev (n_perm, K, K)
+// device or null.  Everything is left in out (device) as p.s.sums lays it out.
+static int launch_spatial_perm(const SpatialPermPlan& p, const double* V, long long ldv, int K, const GraphTables& g,
+                               unsigned long long seed, long long first_perm, long long n_perm, double* null_dev, double* scratch,
+                               double* out, hipStream_t st) {
+    const int n = g.n;
     if (n <= 0) return 0;
     const SpatialStatsPlan& s = p.s;
-    const size_t KK = (size_t)K * K;
+    const size_t KK = s.sums.KK;
     const int B = p.batch;
     double* Zall = scratch;
     double* lagall = Zall + (size_t)B * p.plane_doubles;
     double* part = lagall + (size_t)B * p.plane_doubles;
     double* own_null = part + p.part_doubles;
-    double* mean = out;
-    double* C_obs = out + 2 * (size_t)K;
-    double* m4 = out + s.out_doubles;
-    long long* count_ge = reinterpret_cast<long long*>(m4 + K);
-    long long* count_le = count_ge + KK;
-    double* sum_d = m4 + K + 2 * KK;
-    double* sumsq_d = sum_d + KK;
+    double* mean = out + s.sums.mean;
+    double* C_obs = out + s.sums.C;
+    long long* count_ge = reinterpret_cast<long long*>(out + s.sums.count_ge);
+    long long* count_le = reinterpret_cast<long long*>(out + s.sums.count_le);
+    double* sum_d = out + s.sums.sum_d;
+    double* sumsq_d = out + s.sums.sumsq_d;
 
     // the observed statistics in batch element 0's planes, m4 from its Z among them (the permutations overwrite it)
-    FDX_TRY(observed_pass(s, V, ldv, n, K, ell, slice_off, deg, perm, Zall, lagall, part, out, nullptr, m4, st));
-    FDX_HIP(hipMemsetAsync(count_ge, 0, 4 * KK * sizeof(double), st));
+    FDX_TRY(launch_spatial_stats(s, V, ldv, K, g, scratch, B, out, nullptr, out + s.sums.m4, st));
+    FDX_HIP(hipMemsetAsync(count_ge, 0, (s.sums.perm_doubles - s.sums.count_ge) * sizeof(double), st));   // the counts and the sums of d
     if (n_perm <= 0) return 0;
 
     SsPermArgs pa;
@@ -506,10 +513,10 @@ int launch_spatial_perm(const SpatialPermPlan& p, const double* V, long long ldv
     for (long long done = 0; done < n_perm; done += B) {
         const int b = (int)std::min<long long>(B, n_perm - done);       // the last batch may be ragged
         pa.first = first_perm + done;
-        hipLaunchKernelGGL(ss_centre_kernel<true>, dim3(s.centre_blocks, b), dim3(256), lds, st, V, ldv, mean, perm, n,
+        hipLaunchKernelGGL(ss_centre_kernel<true>, dim3(s.centre_blocks, b), dim3(256), lds, st, V, ldv, mean, g.perm, n,
                            (int)(s.ld / 64), K, Zall, s.ld, (double*)nullptr, pa);
         FDX_CHECK_LAUNCH();
-        launch_lag_for(s, b, pa.plane_stride, Zall, ell, slice_off, deg, perm, mean, n, K, lagall, nullptr, nullptr, st);
+        launch_lag_for(s, b, pa.plane_stride, Zall, g, mean, K, lagall, nullptr, nullptr, st);
         FDX_CHECK_LAUNCH();
         hipLaunchKernelGGL(ss_cross_kernel, dim3(s.cross_blocks, tiles, b), dim3(256), 0, st, Zall, lagall, s.ld, s.n_slices, K,
                            s.pair_tiles_1d, part, pa.plane_stride, pa.plane_stride);
@@ -525,14 +532,89 @@ int launch_spatial_perm(const SpatialPermPlan& p, const double* V, long long ldv
     return 0;
 }
 
-int launch_permutation_indices(unsigned long long seed, long long r, int n, int* out, hipStream_t st) {
-    if (n <= 0) return 0;
+}  // namespace fdx
+
+using namespace fdx;
+
+extern "C" {
+
+int fdx_spatial_autocorr_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, int32_t K, double* mean_out, double* m2_out,
+                             double* C_out, int64_t* counts_out, double* neighbor_mean_dev, void* stream) {
+    FDX_REQUIRE(g && V_dev && mean_out && m2_out && C_out && counts_out, "fdx_spatial_autocorr_dev: null argument");
+    FDX_REQUIRE(K >= 1 && ldv >= K, "fdx_spatial_autocorr_dev: K must be positive and ldv at least K");
+    GraphTables t;
+    FDX_TRY(whole_graph_tables(g, "fdx_spatial_autocorr_dev", &t));
+    hipStream_t st = (hipStream_t)stream;
+    PoolStream pool_stream(st);
+    counts_out[0] = t.n;
+    counts_out[1] = counts_out[2] = 0;
+    if (t.n == 0) {
+        SpatialSumsLayout(K).fill_empty(mean_out, m2_out, C_out);
+        return 0;
+    }
+    const SpatialStatsPlan plan = spatial_stats_plan(t.n, K);
+    DevBuf scratch, out;
+    FDX_TRY(scratch.alloc(plan.scratch_doubles * sizeof(double)));
+    FDX_TRY(out.alloc(plan.sums.observed_doubles * sizeof(double)));
+    FDX_TRY(launch_spatial_stats(plan, V_dev, ldv, K, t, scratch.as<double>(), 1, out.as<double>(), neighbor_mean_dev, nullptr, st));
+    std::vector<double> host(plan.sums.observed_doubles);
+    FDX_TRY(copy_d2h(host.data(), out.p, host.size() * sizeof(double), st));   // the call's one host synchronisation
+    plan.sums.unpack(host.data(), mean_out, m2_out, C_out, counts_out + 1);
+    return 0;
+}
+
+int fdx_spatial_perm_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, int32_t K, uint64_t seed, int64_t first_perm,
+                         int64_t n_perm, int32_t max_batch, double* null_dev, double* mean_out, double* m2_out, double* C_out,
+                         int64_t* counts_out, double* m4_out, int64_t* count_ge_out, int64_t* count_le_out, double* sum_d_out,
+                         double* sumsq_d_out, int32_t* batch_out, void* stream) {
+    FDX_REQUIRE(g && V_dev && mean_out && m2_out && C_out && counts_out && m4_out && count_ge_out && count_le_out && sum_d_out &&
+                    sumsq_d_out,
+                "fdx_spatial_perm_dev: null argument");
+    FDX_REQUIRE(K >= 1 && ldv >= K, "fdx_spatial_perm_dev: K must be positive and ldv at least K");
+    FDX_REQUIRE(first_perm >= 0 && n_perm >= 0 && max_batch >= 0,
+                "fdx_spatial_perm_dev: first_perm, n_perm and max_batch must not be negative");
+    GraphTables t;
+    FDX_TRY(whole_graph_tables(g, "fdx_spatial_perm_dev", &t));
+    hipStream_t st = (hipStream_t)stream;
+    PoolStream pool_stream(st);
+    const size_t KK = (size_t)K * K;
+    counts_out[0] = t.n;
+    counts_out[1] = counts_out[2] = 0;
+    if (batch_out) *batch_out = 0;
+    if (t.n == 0) {                                     // nothing to permute: every C_r equals C_obs = 0
+        SpatialSumsLayout(K).fill_empty(mean_out, m2_out, C_out, m4_out);
+        std::fill(count_ge_out, count_ge_out + KK, n_perm);
+        std::fill(count_le_out, count_le_out + KK, n_perm);
+        std::fill(sum_d_out, sum_d_out + KK, 0.0);
+        std::fill(sumsq_d_out, sumsq_d_out + KK, 0.0);
+        if (null_dev && n_perm > 0) FDX_HIP(hipMemsetAsync(null_dev, 0, (size_t)n_perm * KK * sizeof(double), st));
+        return 0;
+    }
+    const SpatialPermPlan plan = spatial_perm_plan(t.n, K, n_perm, max_batch, null_dev == nullptr);
+    if (batch_out) *batch_out = n_perm > 0 ? plan.batch : 0;
+    DevBuf scratch, out;
+    FDX_TRY(scratch.alloc(plan.scratch_doubles * sizeof(double)));
+    FDX_TRY(out.alloc(plan.s.sums.perm_doubles * sizeof(double)));
+    FDX_TRY(launch_spatial_perm(plan, V_dev, ldv, K, t, seed, first_perm, n_perm, null_dev, scratch.as<double>(), out.as<double>(), st));
+    std::vector<double> host(plan.s.sums.perm_doubles);
+    FDX_TRY(copy_d2h(host.data(), out.p, host.size() * sizeof(double), st));   // the call's one host synchronisation
+    plan.s.sums.unpack(host.data(), mean_out, m2_out, C_out, counts_out + 1, m4_out, count_ge_out, count_le_out, sum_d_out,
+                       sumsq_d_out);
+    return 0;
+}
+
+// out_dev[i] = pi_r(i), i < n: the permutation the kernels above apply
+int fdx_permutation_indices_dev(uint64_t seed, int64_t r, int64_t n, int32_t* out_dev, void* stream) {
+    FDX_REQUIRE(n >= 0 && n < (1LL << 31) - 128, "fdx_permutation_indices_dev: n must be between 0 and 2^31 - 129");
+    FDX_REQUIRE(r >= 0, "fdx_permutation_indices_dev: r must not be negative");
+    FDX_REQUIRE(n == 0 || out_dev, "fdx_permutation_indices_dev: null argument");
+    if (n == 0) return 0;
     int wl, wr;
-    ss_feistel_widths(n, &wl, &wr);
-    hipLaunchKernelGGL(ss_perm_indices_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, ss_perm_key(ss_mix64(seed), r), n, wl, wr,
-                       out);
+    ss_feistel_widths((int)n, &wl, &wr);
+    hipLaunchKernelGGL(ss_perm_indices_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream,
+                       ss_perm_key(ss_mix64(seed), r), (int)n, wl, wr, out_dev);
     FDX_CHECK_LAUNCH();
     return 0;
 }
 
-}  // namespace fdx
+}  // extern "C"

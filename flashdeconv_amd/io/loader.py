@@ -14,10 +14,6 @@ from scipy import sparse
 from .. import _lib
 
 
-def _is_cuda_tensor(x):
-    return type(x).__module__.split(".")[0] == "torch" and getattr(x, "is_cuda", False)
-
-
 def _type_sums_device(expr, codes, K, mean):
     """(K, G) float64 signatures of a CUDA tensor (dense or sparse_csr): rows added per type in ascending row order."""
     import torch
@@ -88,7 +84,7 @@ def load_reference(adata_ref, cell_type_key="cell_type", layer=None, method="mea
     if method not in ("mean", "sum"):
         raise ValueError(f"Unknown aggregation method: {method}")
     labels = np.array(adata_ref.obs[cell_type_key])
-    if _is_cuda_tensor(expr):                                               # the matrix stays on the GPU
+    if _lib.is_cuda_tensor(expr):                                               # the matrix stays on the GPU
         names, codes = np.unique(labels, return_inverse=True)
         return _type_sums_device(expr, codes.ravel(), len(names), method == "mean"), names, np.array(adata_ref.var_names)
     names = np.unique(labels)
@@ -112,7 +108,7 @@ def align_genes(Y, X, genes_spatial, genes_ref):
         first_r.setdefault(g, i)
     si = np.array([first_s[g] for g in common])
     ri = np.array([first_r[g] for g in common])
-    if _is_cuda_tensor(Y):
+    if _lib.is_cuda_tensor(Y):
         return _select_columns_device(Y, si), X[:, ri], common
     return Y[:, si], X[:, ri], common
 

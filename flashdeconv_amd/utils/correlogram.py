@@ -32,17 +32,12 @@ import ctypes
 import numpy as np
 
 from .. import _lib
-from .spatial_stats import _check_values, _is_cuda_tensor, _is_torch, _values_on_device, assemble, randomization_variance
+from ._device import check_count, check_values, device_of, values_on_device
+from .spatial_stats import assemble, randomization_variance
 
 __all__ = ["spatial_correlogram", "correlogram_sums", "assemble_correlogram", "correlogram_request", "MAX_BANDS"]
 
 MAX_BANDS = 32
-
-
-def _check_int(name, v, lo):
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < lo:
-        raise ValueError(f"{name} must be an int >= {lo}, got {v!r}")
-    return int(v)
 
 
 def _check_radii(radii):
@@ -62,7 +57,7 @@ def _check_radii(radii):
 
 
 def _check_n_bands(n_bands):
-    nb = _check_int("n_bands", n_bands, 1)
+    nb = check_count("n_bands", n_bands, 1)
     if nb > MAX_BANDS:
         raise ValueError(f"at most {MAX_BANDS} bands, got n_bands = {nb}")
     return nb
@@ -85,31 +80,31 @@ def correlogram_request(arg):
 
 def _check_coords(coords, n_rows):
     """(n, dim) of ``coords``: a 2-D numpy array (anything numeric) or float64 CUDA tensor with 1 to 3 columns and ``n_rows`` rows."""
-    shape = tuple(coords.shape) if _is_torch(coords) else np.shape(coords)
+    shape = tuple(coords.shape) if _lib.is_torch(coords) else np.shape(coords)
     if len(shape) != 2 or shape[1] == 0:
         raise ValueError(f"coords must be 2D with at least 1 coordinate dimension, got shape {shape}")
     if shape[1] > 3:
         raise ValueError(f"coords has {shape[1]} dimensions: the correlogram is built for 1 to 3 coordinate dimensions")
     if shape[0] != n_rows:
         raise ValueError(f"values has {n_rows} rows but coords has {shape[0]}")
-    if _is_cuda_tensor(coords) and str(coords.dtype) != "torch.float64":
+    if _lib.is_cuda_tensor(coords) and str(coords.dtype) != "torch.float64":
         raise ValueError(f"coords on the device must be float64, got {coords.dtype}")
     return shape
 
 
 def _check_common(values, coords, max_bands_per_pass, max_candidates):
-    n, K = _check_values(values)
+    n, K = check_values(values)
     _check_coords(coords, n)
-    _check_int("max_bands_per_pass", max_bands_per_pass, 0)
+    check_count("max_bands_per_pass", max_bands_per_pass, 0)
     if max_candidates is not None:
-        _check_int("max_candidates", max_candidates, 1)
+        check_count("max_candidates", max_candidates, 1)
     return n, K
 
 
 def _coords_host(coords):
-    if _is_cuda_tensor(coords):
+    if _lib.is_cuda_tensor(coords):
         return _lib.tensor_to_host(coords)
-    if _is_torch(coords):
+    if _lib.is_torch(coords):
         coords = coords.detach().numpy()
     return _lib.as_f64(coords)
 
@@ -125,20 +120,15 @@ def correlogram_sums(values, coords, radii, max_bands_per_pass=0, degree=False, 
     B = r.size
     _lib.require_gpu()
     import torch
-    device_out = _is_cuda_tensor(values)
-    if device_out:
-        device = values.device
-    elif _is_cuda_tensor(coords):
-        device = coords.device
-    else:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device_out = _lib.is_cuda_tensor(values)
+    device = device_of(values, coords)
     mean, m2, m4, C = np.empty(K), np.empty(K), np.empty(K), np.empty((B, K, K))
     W, sds = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
     bpp, cand = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int64)
     with torch.cuda.device(device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        V, ldv = _values_on_device(values, device, stream)
-        if _is_cuda_tensor(coords):
+        stream = _lib.current_stream(device)
+        V, ldv = values_on_device(values, device, stream)
+        if _lib.is_cuda_tensor(coords):
             xy = coords.detach().to(device).contiguous()
         else:
             ch = _coords_host(coords)

@@ -42,7 +42,7 @@ import ctypes
 import numpy as np
 
 from .. import _lib
-from .spatial_stats import _is_cuda_tensor, _is_torch
+from ._device import device_of
 
 __all__ = ["celltype_expression", "weighted_gene_sums", "nnls_gram", "check_request", "MAX_TYPES"]
 
@@ -66,7 +66,7 @@ def _check_Y(Y):
         raise ValueError(f"Y must be a 2-D (n_spots, n_genes) matrix, got shape {shape}")
     if shape[1] < 1:
         raise ValueError(f"Y must have at least one gene, got shape {shape}")
-    if _is_cuda_tensor(Y) and not _lib.is_torch_sparse_csr(Y) and str(Y.layout) != "torch.strided":
+    if _lib.is_cuda_tensor(Y) and not _lib.is_torch_sparse_csr(Y) and str(Y.layout) != "torch.strided":
         raise ValueError(f"a sparse CUDA Y must be torch.sparse_csr, got {Y.layout}")
     return int(shape[0]), int(shape[1])
 
@@ -81,11 +81,11 @@ def _check_weights(W, n):
     K = int(shape[1])
     if K < 1 or K > MAX_TYPES:
         raise ValueError(f"weights must have 1 to {MAX_TYPES} columns, got {K}")
-    if _is_cuda_tensor(W):
+    if _lib.is_cuda_tensor(W):
         if str(W.dtype) != "torch.float64":
             raise ValueError(f"weights on the device must be float64, got {W.dtype}")
         return K
-    Wh = W.detach().numpy() if _is_torch(W) else np.asarray(W)
+    Wh = W.detach().numpy() if _lib.is_torch(W) else np.asarray(W)
     if Wh.dtype.kind not in "fiub":
         raise ValueError(f"weights must be numeric, got dtype {Wh.dtype}")
     if not np.all(np.isfinite(Wh)):
@@ -125,11 +125,11 @@ def _check_groups(groups, n, n_groups):
     shape = tuple(groups.shape) if hasattr(groups, "shape") else np.shape(groups)
     if len(shape) != 1 or shape[0] != n:
         raise ValueError(f"groups must be a 1-D array of {n} labels, got shape {shape}")
-    if _is_cuda_tensor(groups):
+    if _lib.is_cuda_tensor(groups):
         if groups.dtype.is_floating_point or str(groups.dtype) == "torch.bool":
             raise ValueError(f"groups must be integers, got {groups.dtype}")
         return groups, C
-    g = groups.detach().numpy() if _is_torch(groups) else np.asarray(groups)
+    g = groups.detach().numpy() if _lib.is_torch(groups) else np.asarray(groups)
     if g.dtype.kind not in "iu":
         raise ValueError(f"groups must be integers, got dtype {g.dtype}")
     g = g.astype(np.int64)
@@ -159,7 +159,7 @@ def _sort_groups(labels, C, n, device, stream):
     import torch
     if labels is None:
         return None, np.array([0, n], dtype=np.int32), 1
-    if _is_cuda_tensor(labels):
+    if _lib.is_cuda_tensor(labels):
         lab = labels.detach().to(device=device, dtype=torch.int64)
         lo, hi = (int(lab.min().item()), int(lab.max().item())) if n else (0, -1)
         if C is None:
@@ -185,24 +185,16 @@ def _sort_groups(labels, C, n, device, stream):
 def _weights_on_device(W, device, stream):
     """(float64 device tensor with unit column stride, row stride)."""
     import torch
-    if _is_cuda_tensor(W):
+    if _lib.is_cuda_tensor(W):
         w = W.detach().to(device)
         if w.stride(1) != 1 or w.stride(0) < w.shape[1]:
             w = w.contiguous()
         return w, w.stride(0)
-    Wh = _lib.as_f64(W.detach().numpy() if _is_torch(W) else W)
+    Wh = _lib.as_f64(W.detach().numpy() if _lib.is_torch(W) else W)
     d = torch.empty(Wh.shape, dtype=torch.float64, device=device)
     if Wh.size:
         _lib.check(_lib.load().fdx_memcpy_h2d(ctypes.c_void_p(d.data_ptr()), Wh.ctypes.data_as(ctypes.c_void_p), Wh.nbytes, stream))
     return d, Wh.shape[1]
-
-
-def _device_of(*xs):
-    import torch
-    for x in xs:
-        if _is_cuda_tensor(x):
-            return x.device
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def _sums_device(Y, W, labels, C, n, G, K):
@@ -210,9 +202,9 @@ def _sums_device(Y, W, labels, C, n, G, K):
     import torch
     _lib.require_gpu()
     lib = _lib.load()
-    device = _device_of(Y, W, labels)
+    device = device_of(Y, W, labels)
     with torch.cuda.device(device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        stream = _lib.current_stream(device)
         rows, off, C = _sort_groups(labels, C, n, device, stream)
         Wd, ldw = _weights_on_device(W, device, stream)
         A = torch.empty((C, K, K), dtype=torch.float64, device=device)
@@ -229,7 +221,7 @@ def _sums_device(Y, W, labels, C, n, G, K):
                 torch.cuda.current_stream(device).synchronize()       # the arrays go back to the allocator below
             finally:
                 csr.free()
-        elif _is_cuda_tensor(Y):
+        elif _lib.is_cuda_tensor(Y):
             Yd = Y.detach()
             if Yd.dtype not in (torch.float32, torch.float64):
                 from ..core.deconv import device_counts_as_float
@@ -240,7 +232,7 @@ def _sums_device(Y, W, labels, C, n, G, K):
                                                       ctypes.c_void_p(Wd.data_ptr()), int(ldw), K, rows_p, _lib.ptr_i32(off), C, *out,
                                                       stream))
         else:
-            Yh = Y.detach().numpy() if _is_torch(Y) else np.asarray(Y)
+            Yh = Y.detach().numpy() if _lib.is_torch(Y) else np.asarray(Y)
             ptr, code = _lib.upload_matrix(Yh)
             try:
                 _lib.check(lib.fdx_weighted_gene_sums_dev(ptr, code, n, G, G, ctypes.c_void_p(Wd.data_ptr()), int(ldw), K, rows_p,
@@ -262,7 +254,7 @@ def weighted_gene_sums(Y, weights, groups=None, n_groups=None):
     out = {"A": A, "B": B, "q": q, "u": u}
     if groups is None:
         out = {k: v[0] for k, v in out.items()}
-    if not _is_cuda_tensor(weights):
+    if not _lib.is_cuda_tensor(weights):
         out = {k: _lib.tensor_to_host(v) for k, v in out.items()}
     out["n_rows"] = n_rows if groups is not None else n_rows[0]
     return out
@@ -274,7 +266,7 @@ def _solve_device(A, B, q, ridge, max_iter, tol):
     C, K, G = B.shape
     device = B.device
     with torch.cuda.device(device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        stream = _lib.current_stream(device)
         S = torch.empty((C, K, G), dtype=torch.float64, device=device)
         n_iter = torch.empty((C, G), dtype=torch.int32, device=device)
         conv = torch.empty((C, G), dtype=torch.int32, device=device)
@@ -306,28 +298,28 @@ def nnls_gram(A, B, ridge=0.0, max_iter=10000, tol=1e-10, q=None):
     for name, x in (("A", A), ("B", B), ("q", q)):
         if x is None:
             continue
-        if _is_cuda_tensor(x):
+        if _lib.is_cuda_tensor(x):
             if str(x.dtype) != "torch.float64":
                 raise ValueError(f"{name} on the device must be float64, got {x.dtype}")
         elif not np.all(np.isfinite(np.asarray(x, dtype=np.float64))):
             raise ValueError(f"{name} must be finite")
-    if not _is_cuda_tensor(A):
+    if not _lib.is_cuda_tensor(A):
         Ah = np.asarray(A, dtype=np.float64)
         if not np.array_equal(Ah, np.swapaxes(Ah, -1, -2)):
             raise ValueError("A must be symmetric")
     _lib.require_gpu()
     import torch
-    device = _device_of(B, A, q)
+    device = device_of(B, A, q)
 
     def dev(x, shape):
         if x is None:
             return None
-        if _is_cuda_tensor(x):
+        if _lib.is_cuda_tensor(x):
             return x.detach().to(device).reshape(shape).contiguous()
         h = _lib.as_f64(x).reshape(shape)
         d = torch.empty(shape, dtype=torch.float64, device=device)
         _lib.check(_lib.load().fdx_memcpy_h2d(ctypes.c_void_p(d.data_ptr()), h.ctypes.data_as(ctypes.c_void_p), h.nbytes,
-                                              ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+                                              _lib.current_stream(device)))
         return d
     C = sb[0] if grouped else 1
     with torch.cuda.device(device):
@@ -337,7 +329,7 @@ def nnls_gram(A, B, ridge=0.0, max_iter=10000, tol=1e-10, q=None):
         out["rss"] = rss
     if not grouped:
         out = {k: v[0] for k, v in out.items()}
-    if not _is_cuda_tensor(B):
+    if not _lib.is_cuda_tensor(B):
         out = {k: _lib.tensor_to_host(v) for k, v in out.items()}
     return out
 

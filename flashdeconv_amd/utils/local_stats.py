@@ -47,8 +47,8 @@ import ctypes
 import numpy as np
 
 from .. import _lib
-from .spatial_stats import (_GOLDEN, _check_count, _check_values, _is_cuda_tensor, _is_torch, _keyed_bijection, _mix64_int,
-                            _permutation_seed, _resolve_graph, _values_on_device)
+from ._device import check_count, check_values, device_of, resolved_graph, values_on_device
+from .spatial_stats import _GOLDEN, _keyed_bijection, _mix64_int, _permutation_seed
 
 __all__ = ["local_spatial_statistics", "local_sums", "assemble_local", "conditional_indices"]
 
@@ -161,13 +161,13 @@ def _local_calls(values, g, seed, first_perm, n_perm):
     """``fdx_local_stats_dev`` on a resolved graph: (the float64 device copy of ``values``, a dict of device tensors and host
     sums)."""
     import torch
-    n, K = _check_values(values)
-    device = values.device if _is_cuda_tensor(values) else torch.device("cuda", torch.cuda.current_device())
+    n, K = check_values(values)
+    device = device_of(values)
     mean, m2 = np.empty(K), np.empty(K)
     counts = np.zeros(3, dtype=np.int64)
     with torch.cuda.device(device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        V, ldv = _values_on_device(values, device, stream)
+        stream = _lib.current_stream(device)
+        V, ldv = values_on_device(values, device, stream)
         S = torch.empty((n, K), dtype=torch.float64, device=device)
         deg = torch.empty((n,), dtype=torch.int32, device=device)
         perm = {}
@@ -187,23 +187,14 @@ def _local_calls(values, g, seed, first_perm, n_perm):
     return V, out
 
 
-def _checked_args(values, first_perm, n_permutations):
-    n, _ = _check_values(values)
-    n_perm, first_perm = _check_count("n_permutations", n_permutations), _check_count("first_perm", first_perm)
+def _device_sums(values, graph, seed, first_perm, n_permutations):
+    n, _ = check_values(values)
+    n_perm, first_perm = check_count("n_permutations", n_permutations), check_count("first_perm", first_perm)
     if n_perm >= 1 << 31:
         raise ValueError(f"n_permutations must be below 2^31, got {n_perm}")
-    return n, first_perm, n_perm
-
-
-def _device_sums(values, graph, seed, first_perm, n_permutations):
-    n, first_perm, n_perm = _checked_args(values, first_perm, n_permutations)
     seed = _permutation_seed(seed)
-    g, owned = _resolve_graph(graph, n)
-    try:
+    with resolved_graph(graph, n) as g:
         return _local_calls(values, g, seed, first_perm, n_perm)
-    finally:
-        if owned:
-            g.close()
 
 
 def local_sums(values, graph, seed=0, first_perm=0, n_permutations=0):
@@ -214,7 +205,7 @@ def local_sums(values, graph, seed=0, first_perm=0, n_permutations=0):
     ``count_le`` (int32), ``sum_d``, ``sumsq_d`` (float64).  The arrays are CUDA tensors when ``values`` was one, else numpy.
     Same arguments and checks as ``local_spatial_statistics``.  The counts do not depend on how a range of permutations is split
     into calls; the sums of split calls add up to the rounding of their additions."""
-    device_out = _is_cuda_tensor(values)
+    device_out = _lib.is_cuda_tensor(values)
     _, out = _device_sums(values, graph, seed, first_perm, n_permutations)
     if not device_out:
         for k in ("neighbor_sum", "degree") + _PERM_KEYS:
@@ -237,14 +228,14 @@ def local_spatial_statistics(values, graph, n_permutations=0, random_state=0):
     ``mean``, ``m2`` (K,) numpy, ``n``, ``n_edges``; with R >= 1 also ``n_permutations`` and the (n, K) arrays ``p_greater``,
     ``p_less``, ``p_value``, ``z_sim``, ``local_i_p_greater``.  The per-spot arrays are CUDA tensors when ``values`` was one (the
     assembly then runs in torch on the device), else numpy."""
-    device_out = _is_cuda_tensor(values)
+    device_out = _lib.is_cuda_tensor(values)
     V, s = _device_sums(values, graph, random_state, 0, n_permutations)
     if device_out:
         out = _assemble_torch(V, s)
         out["neighbor_sum"], out["degree"] = s["neighbor_sum"], s["degree"]
     else:
         host = {k: _lib.tensor_to_host(s[k]) for k in ("neighbor_sum", "degree") + _PERM_KEYS if k in s}
-        host_values = values.detach().numpy() if _is_torch(values) else values
+        host_values = values.detach().numpy() if _lib.is_torch(values) else values
         out = assemble_local(host_values, host["neighbor_sum"], host["degree"], s["mean"], s["m2"], s["n"], s["W"],
                              *(host.get(k) for k in _PERM_KEYS), n_permutations=s["n_permutations"])
         out["neighbor_sum"], out["degree"] = host["neighbor_sum"], host["degree"]

@@ -12,6 +12,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from .. import _lib
+from ._device import device_of, values_on_device
 
 N_MAX = 2 ** 31 - 1                      # n_spots * n_types limit of the device path (int32 sort payloads)
 
@@ -22,12 +23,8 @@ _FIELDS = 18
 _SPEARMAN_OVERALL, _SPEARMAN_PER_TYPE = 1, 2
 
 
-def _is_cuda_tensor(x):
-    return type(x).__module__.split(".")[0] == "torch" and getattr(x, "is_cuda", False)
-
-
 def _shape(x):
-    if type(x).__module__.split(".")[0] == "torch":
+    if _lib.is_torch(x):
         return tuple(x.shape)
     return np.shape(x)
 
@@ -53,41 +50,20 @@ class _Pair:
     def __init__(self, pred, true):
         self.n, self.K = _validate(pred, true)
         import torch
-        self.device_out = _is_cuda_tensor(pred) and _is_cuda_tensor(true)
-        devs = [x.device for x in (pred, true) if _is_cuda_tensor(x)]
+        self.device_out = _lib.is_cuda_tensor(pred) and _lib.is_cuda_tensor(true)
+        devs = [x.device for x in (pred, true) if _lib.is_cuda_tensor(x)]
         if len(devs) == 2 and devs[0] != devs[1]:
             raise ValueError(f"pred and true are on different devices ({devs[0]} and {devs[1]})")
-        self.device = devs[0] if devs else torch.device("cuda", torch.cuda.current_device())
+        self.device = device_of(pred, true)
         if not devs:
             _lib.require_gpu()
-        f32 = all(self._dtype_name(x) == "float32" for x in (pred, true))
+        f32 = all(str(x.dtype).replace("torch.", "") == "float32" for x in (pred, true))
         self.tdtype = torch.float32 if f32 else torch.float64
         self.code = _lib.FDX_F32 if f32 else _lib.FDX_F64
         with torch.cuda.device(self.device):
-            self.stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self.P, self.ldp = self._on_device(pred)
-            self.T, self.ldt = self._on_device(true)
-
-    @staticmethod
-    def _dtype_name(x):
-        return str(x.dtype).replace("torch.", "")
-
-    def _on_device(self, x):
-        import torch
-        if _is_cuda_tensor(x):
-            x = x.detach()
-            if x.dtype != self.tdtype:
-                x = x.to(self.tdtype)
-            if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
-                x = x.contiguous()
-            return x, x.stride(0)
-        if type(x).__module__.split(".")[0] == "torch":
-            x = x.detach().numpy()
-        a = np.ascontiguousarray(x, dtype=np.float32 if self.tdtype == torch.float32 else np.float64)
-        d = torch.empty(a.shape, dtype=self.tdtype, device=self.device)
-        _lib.check(_lib.load().fdx_upload_convert_dev(ctypes.c_void_p(d.data_ptr()), self.code, a.ctypes.data_as(ctypes.c_void_p),
-                                                      _lib.SRC_CODES[a.dtype.name], a.size, None, self.stream))
-        return d, a.shape[1]
+            self.stream = _lib.current_stream(self.device)
+            self.P, self.ldp = values_on_device(pred, self.device, self.stream, self.tdtype)
+            self.T, self.ldt = values_on_device(true, self.device, self.stream, self.tdtype)
 
     def run(self, moments=True, threshold=0.05, epsilon=1e-10, jsd=False, spearman=0):
         """(stats (K+1, FIELDS), rare int64 [n_rare, tp, fp, fn], rho (K+1), jsd device tensor or None): one device sequence,

@@ -17,13 +17,15 @@ so the labels returned are always the arg-min of the centres returned.  The loop
 stream, float64 throughout and in a fixed summation order: two calls return the same bits.  The k-means++ draw itself is host
 arithmetic on at most 1024 block sums and one block of distances (``pick_row``).
 """
+import contextlib
 import ctypes
 
 import numpy as np
 
 from .. import _lib
 from .random import check_random_state
-from .spatial_stats import _is_cuda_tensor, _is_torch, _resolve_graph, _values_on_device, spatial_sums
+from ._device import check_values, device_of, resolved_graph, values_on_device
+from .spatial_stats import spatial_sums
 
 __all__ = ["spatial_niches", "kmeans", "kmeans_plusplus", "pick_row"]
 
@@ -55,19 +57,6 @@ def pick_row(block_sums, fetch_block, t):
     return int(first) + j
 
 
-def _shape_of(a, name):
-    """(n, D) of a 2-D numpy array or torch tensor of floats; ValueError otherwise."""
-    shape = tuple(a.shape) if _is_torch(a) else np.shape(a)
-    if len(shape) != 2:
-        raise ValueError(f"{name} must be a 2-D (n_spots, n_columns) array, got shape {shape}")
-    if shape[0] < 1 or shape[1] < 1:
-        raise ValueError(f"{name} must not be empty, got shape {shape}")
-    dtype = str(a.dtype).replace("torch.", "") if hasattr(a, "dtype") else "float64"
-    if _is_cuda_tensor(a) and dtype not in ("float32", "float64"):
-        raise ValueError(f"{name} must be float32 or float64, got {dtype}")
-    return shape
-
-
 def _check_n_niches(n_niches, n):
     if isinstance(n_niches, bool) or not isinstance(n_niches, (int, np.integer)):
         raise ValueError(f"n_niches must be an integer, got {n_niches!r}")
@@ -85,24 +74,19 @@ def _check_max_iter(max_iter):
 
 
 def _check_init(init, n, D):
-    shape = _shape_of(init, "init")
+    shape = check_values(init, "init")
     if shape[1] != D:
         raise ValueError(f"init must have the features' {D} columns, got shape {shape}")
     _check_n_niches(shape[0], n)
     return shape[0]
 
 
-def _device_of(x):
-    import torch
-    return x.device if _is_cuda_tensor(x) else torch.device("cuda", torch.cuda.current_device())
-
-
 def _lloyd(F, ldf, n, D, init, max_iter, device, stream):
     """fdx_kmeans_dev on the device matrix F: (labels - a CUDA int32 tensor -, the rest of the result dict)."""
     import torch
-    C = (tuple(init.shape) if _is_torch(init) else np.shape(init))[0]
-    centres, _ = _values_on_device(init, device, stream)
-    if _is_cuda_tensor(init) or not centres.is_contiguous():
+    C = (tuple(init.shape) if _lib.is_torch(init) else np.shape(init))[0]
+    centres, _ = values_on_device(init, device, stream)
+    if _lib.is_cuda_tensor(init) or not centres.is_contiguous():
         centres = centres.clone(memory_format=torch.contiguous_format)          # updated in place: never the caller's tensor
     labels = torch.empty(n, dtype=torch.int32, device=device)
     counts = np.zeros(C, dtype=np.int64)
@@ -151,15 +135,15 @@ def kmeans(features, init, max_iter=100):
     array is uploaded once; a tensor with unit column stride is read in place).  ``init``: (C, D), 1 <= C <= min(64, n).
     Returns a dict: ``labels`` (n,) int32 - a CUDA tensor when ``features`` was one, else numpy -, ``centers`` (C, D), ``counts``
     (C,) int64, ``inertia``, ``n_iter`` (assign passes) and ``converged``.  Shapes are checked before the GPU is touched."""
-    n, D = _shape_of(features, "features")
+    n, D = check_values(features, "features")
     _check_init(init, n, D)
     max_iter = _check_max_iter(max_iter)
     import torch
-    device_out = _is_cuda_tensor(features)
-    device = _device_of(features)
+    device_out = _lib.is_cuda_tensor(features)
+    device = device_of(features)
     with torch.cuda.device(device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        F, ldf = _values_on_device(features, device, stream)
+        stream = _lib.current_stream(device)
+        F, ldf = values_on_device(features, device, stream)
         labels, out = _lloyd(F, ldf, n, D, init, max_iter, device, stream)
         out["labels"] = labels if device_out else _lib.tensor_to_host(labels)
     return out
@@ -170,14 +154,14 @@ def kmeans_plusplus(features, n_niches, random_state=0):
     drawn with probability proportional to its squared distance to the nearest row chosen so far (``pick_row`` on the device's
     block sums with ``t = rs.random_sample() * total``), so a row at distance 0 of a chosen one is never drawn; where every row is
     (``total == 0``), row ``rs.randint(n)``."""
-    n, D = _shape_of(features, "features")
+    n, D = check_values(features, "features")
     C = _check_n_niches(n_niches, n)
     rs = check_random_state(random_state)
     import torch
-    device = _device_of(features)
+    device = device_of(features)
     with torch.cuda.device(device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        F, ldf = _values_on_device(features, device, stream)
+        stream = _lib.current_stream(device)
+        F, ldf = values_on_device(features, device, stream)
         rows = _seed(F, ldf, n, D, C, rs, device, stream)
         return _lib.tensor_to_host(F[torch.as_tensor(rows, device=device)])
 
@@ -193,7 +177,7 @@ def spatial_niches(values, n_niches, graph=None, features="composition", neighbo
     ``init``: ``"k-means++"`` (seeded by ``random_state``) or the (n_niches, D) initial centres, D the width of the features.
     Returns the dict of ``kmeans`` plus ``composition`` (n_niches, K): the mean of ``values`` over each niche's spots, NaN rows
     for empty niches.  Every shape and argument check raises ``ValueError`` before the GPU is touched."""
-    n, K = _shape_of(values, "values")
+    n, K = check_values(values, "values")
     C = _check_n_niches(n_niches, n)
     if features not in FEATURE_MODES:
         raise ValueError(f"Unknown features: {features!r}. Choose from {', '.join(repr(m) for m in FEATURE_MODES)}.")
@@ -213,14 +197,13 @@ def spatial_niches(values, n_niches, graph=None, features="composition", neighbo
         raise ValueError(f"init must hold n_niches = {C} centres, got shape {tuple(np.shape(init))}")
     max_iter = _check_max_iter(max_iter)
 
-    g, owned = _resolve_graph(graph, n) if needs_graph else (None, False)
-    try:
+    with (resolved_graph(graph, n) if needs_graph else contextlib.nullcontext()) as g:
         import torch
-        device_out = _is_cuda_tensor(values)
-        device = _device_of(values)
+        device_out = _lib.is_cuda_tensor(values)
+        device = device_of(values)
         with torch.cuda.device(device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-            V, ldv = _values_on_device(values, device, stream)
+            stream = _lib.current_stream(device)
+            V, ldv = values_on_device(values, device, stream)
             if needs_graph:
                 nm = spatial_sums(V, g, neighbor_mean=True)["neighbor_mean"]
                 F = nm if features == "neighborhood" else torch.cat([V, nm if w == 1.0 else w * nm], dim=1)
@@ -238,7 +221,4 @@ def spatial_niches(values, n_niches, graph=None, features="composition", neighbo
             with np.errstate(divide="ignore", invalid="ignore"):
                 out["composition"] = np.where(counts[:, None] > 0, sums / counts[:, None], np.nan)
             out["labels"] = labels if device_out else _lib.tensor_to_host(labels)
-    finally:
-        if owned:
-            g.close()
     return out

@@ -32,6 +32,7 @@ import ctypes
 import numpy as np
 
 from .. import _lib
+from ._device import check_count, check_values, device_of, resolved_graph, values_on_device
 
 __all__ = ["spatial_autocorrelation", "spatial_sums", "assemble", "spatial_permutation_test", "spatial_permutation_sums",
            "permutation_indices", "randomization_variance", "assemble_permutation"]
@@ -40,14 +41,6 @@ _MASK64 = (1 << 64) - 1
 _GOLDEN = 0x9e3779b97f4a7c15
 _FEISTEL_ROUNDS = 8
 _NULL_CALL_BYTES = 256 << 20          # return_null on host arrays: the device holds this much of the null per call
-
-
-def _is_torch(x):
-    return type(x).__module__.split(".")[0] == "torch"
-
-
-def _is_cuda_tensor(x):
-    return _is_torch(x) and getattr(x, "is_cuda", False)
 
 
 def assemble(n, W, sum_deg_sq, m2, C):
@@ -200,93 +193,19 @@ def assemble_permutation(n, W, m2, C, count_ge, count_le, sum_d, sumsq_d, n_perm
     return out
 
 
-def _check_adjacency(A, n_rows):
-    """A scipy sparse adjacency as canonical CSR; shape, symmetry and the empty diagonal are checked on the host."""
-    if A.ndim != 2 or A.shape[0] != A.shape[1]:
-        raise ValueError(f"graph must be a square adjacency matrix, got shape {A.shape}")
-    if A.shape[0] != n_rows:
-        raise ValueError(f"values has {n_rows} rows but the graph has {A.shape[0]} spots")
-    A = A.tocsr().astype(bool).astype(np.int8)        # binary weights: stored values only mark the edges
-    A.eliminate_zeros()
-    A.sum_duplicates()
-    A.sort_indices()
-    if A.diagonal().any():
-        raise ValueError("graph must have no self loops (a non-zero diagonal entry was found)")
-    if (A != A.T).nnz != 0:
-        raise ValueError("graph must be symmetric")
-    return A
-
-
-def _resolve_graph(graph, n_rows):
-    """(_lib.Graph, owned): the device graph behind `graph`; owned graphs are closed by the caller."""
-    if isinstance(graph, _lib.Graph):
-        g, owned = graph, False
-    elif hasattr(graph, "_graph") and hasattr(graph, "_require_fitted"):      # a FlashDeconv
-        graph._require_fitted()
-        if graph._graph is None:
-            raise RuntimeError("Model has not been fitted. Call fit() first.")
-        g, owned = graph._graph, False
-    elif hasattr(graph, "tocsr"):
-        A = _check_adjacency(graph, n_rows)
-        _lib.require_gpu()
-        return _lib.Graph.from_csr(A.indptr, A.indices, A.shape[0]), True
-    else:
-        raise TypeError("graph must be a fitted FlashDeconv, a flashdeconv_amd._lib.Graph or a scipy sparse adjacency matrix, "
-                        f"got {type(graph).__name__}")
-    n = g.info()[0]
-    if n != n_rows:
-        raise ValueError(f"values has {n_rows} rows but the graph has {n} spots")
-    return g, owned
-
-
-def _values_on_device(values, device, stream):
-    """(float64 device tensor with unit column stride, row stride)."""
-    import torch
-    if _is_cuda_tensor(values):
-        v = values.detach()
-        if v.dtype != torch.float64:
-            v = v.to(torch.float64)
-        if v.stride(1) != 1 or v.stride(0) < v.shape[1]:
-            v = v.contiguous()
-        return v, v.stride(0)
-    if _is_torch(values):
-        values = values.detach().numpy()
-    a = np.asarray(values)
-    a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
-    d = torch.empty(a.shape, dtype=torch.float64, device=device)
-    _lib.check(_lib.load().fdx_upload_convert_dev(ctypes.c_void_p(d.data_ptr()), _lib.FDX_F64, a.ctypes.data_as(ctypes.c_void_p),
-                                                  _lib.SRC_CODES[a.dtype.name], a.size, None, stream))
-    return d, a.shape[1]
-
-
-def _check_values(values):
-    """(n, K) of a 2-D, non-empty ``values``; ``ValueError`` otherwise."""
-    shape = tuple(values.shape) if _is_torch(values) else np.shape(values)
-    if len(shape) != 2:
-        raise ValueError(f"values must be a 2-D (n_spots, n_columns) array, got shape {shape}")
-    n, K = shape
-    if n < 1 or K < 1:
-        raise ValueError(f"values must not be empty, got shape {shape}")
-    dtype = str(values.dtype).replace("torch.", "") if hasattr(values, "dtype") else "float64"
-    if _is_cuda_tensor(values) and dtype not in ("float32", "float64"):
-        raise ValueError(f"values must be float32 or float64, got {dtype}")
-    return n, K
-
-
 def spatial_sums(values, graph, neighbor_mean=False):
     """The device half of ``spatial_autocorrelation``: a dict of ``mean``, ``m2`` (K,), ``C`` (K, K) - numpy - and the integers
     ``n``, ``W``, ``sum_deg_sq``, plus ``neighbor_mean`` (n, K) on request.  Same arguments and checks."""
-    n, K = _check_values(values)
-    g, owned = _resolve_graph(graph, n)
-    try:
+    n, K = check_values(values)
+    with resolved_graph(graph, n) as g:
         import torch
-        device_out = _is_cuda_tensor(values)
-        device = values.device if device_out else torch.device("cuda", torch.cuda.current_device())
+        device_out = _lib.is_cuda_tensor(values)
+        device = device_of(values)
         mean, m2, C = np.empty(K), np.empty(K), np.empty((K, K))
         counts = np.zeros(3, dtype=np.int64)
         with torch.cuda.device(device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-            V, ldv = _values_on_device(values, device, stream)
+            stream = _lib.current_stream(device)
+            V, ldv = values_on_device(values, device, stream)
             nm = torch.empty((n, K), dtype=torch.float64, device=device) if neighbor_mean else None
             _lib.check(_lib.load().fdx_spatial_autocorr_dev(
                 g.handle, ctypes.c_void_p(V.data_ptr()), int(ldv), int(K), _lib.ptr_f64(mean), _lib.ptr_f64(m2), _lib.ptr_f64(C),
@@ -294,9 +213,6 @@ def spatial_sums(values, graph, neighbor_mean=False):
             out = {"mean": mean, "m2": m2, "C": C, "n": int(counts[0]), "W": int(counts[1]), "sum_deg_sq": int(counts[2])}
             if neighbor_mean:
                 out["neighbor_mean"] = nm if device_out else _lib.tensor_to_host(nm)
-    finally:
-        if owned:
-            g.close()
     return out
 
 
@@ -319,12 +235,6 @@ def spatial_autocorrelation(values, graph, neighbor_mean=False):
     return out
 
 
-def _check_count(name, v):
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0:
-        raise ValueError(f"{name} must be an int >= 0, got {v!r}")
-    return int(v)
-
-
 def _permutation_seed(random_state):
     """A uint64 seed: a non-negative int as it stands, else one 63-bit draw from the ``RandomState`` that
     ``utils.check_random_state`` makes of the argument."""
@@ -341,9 +251,9 @@ def _permutation_calls(values, g, seed, first_perm, n_perm, max_batch, return_nu
     """The calls of ``spatial_permutation_sums`` on a resolved graph: permutations ``first_perm .. first_perm + n_perm - 1`` in
     calls of at most ``chunk``, counts and sums merged in order."""
     import torch
-    n, K = _check_values(values)
-    device_out = _is_cuda_tensor(values)
-    device = values.device if device_out else torch.device("cuda", torch.cuda.current_device())
+    n, K = check_values(values)
+    device_out = _lib.is_cuda_tensor(values)
+    device = device_of(values)
     mean, m2, m4, C = np.empty(K), np.empty(K), np.empty(K), np.empty((K, K))
     counts = np.zeros(3, dtype=np.int64)
     tot_ge, tot_le = np.zeros((K, K), dtype=np.int64), np.zeros((K, K), dtype=np.int64)
@@ -352,8 +262,8 @@ def _permutation_calls(values, g, seed, first_perm, n_perm, max_batch, return_nu
     batch = ctypes.c_int32(0)
     batches, null = [], None
     with torch.cuda.device(device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        V, ldv = _values_on_device(values, device, stream)
+        stream = _lib.current_stream(device)
+        V, ldv = values_on_device(values, device, stream)
         if return_null:
             if device_out:
                 null = torch.empty((n_perm, K, K), dtype=torch.float64, device=device)
@@ -397,19 +307,15 @@ def spatial_permutation_sums(values, graph, seed=0, first_perm=0, n_permutations
     device ran per launch chain (``max_batch`` caps it, 0: chosen from the scratch budget), and with ``return_null=True`` ``null``
     (n_permutations, K, K) holds every ``C_r`` - a CUDA tensor when ``values`` was one, else numpy.  The counts and the null do
     not depend on ``max_batch`` or on how a range of permutations is split into calls."""
-    n, K = _check_values(values)
-    n_perm = _check_count("n_permutations", n_permutations)
-    first_perm, max_batch = _check_count("first_perm", first_perm), _check_count("max_batch", max_batch)
+    n, K = check_values(values)
+    n_perm = check_count("n_permutations", n_permutations)
+    first_perm, max_batch = check_count("first_perm", first_perm), check_count("max_batch", max_batch)
     seed = _permutation_seed(seed)
-    g, owned = _resolve_graph(graph, n)
-    try:
+    with resolved_graph(graph, n) as g:
         chunk = max(1, n_perm)
-        if return_null and not _is_cuda_tensor(values):
+        if return_null and not _lib.is_cuda_tensor(values):
             chunk = max(1, min(chunk, _NULL_CALL_BYTES // (8 * K * K)))
         return _permutation_calls(values, g, seed, first_perm, n_perm, max_batch, return_null, chunk)
-    finally:
-        if owned:
-            g.close()
 
 
 def spatial_permutation_test(values, graph, n_permutations=999, random_state=0, return_null=False):
@@ -429,8 +335,8 @@ def spatial_permutation_test(values, graph, n_permutations=999, random_state=0, 
     ``cross``), ``cross_z_sim``, their diagonals ``p_value``, ``p_greater``, ``p_less``, ``z_sim`` (K,), and with
     ``return_null=True`` ``cross_null`` (R, K, K), the null in the units of ``cross`` (a CUDA tensor when ``values`` was one, else
     numpy).  Entries that are NaN in ``cross`` are NaN in all of these, ``z_sim`` also where the null does not vary."""
-    _check_values(values)
-    R = _check_count("n_permutations", n_permutations)
+    check_values(values)
+    R = check_count("n_permutations", n_permutations)
     s = spatial_permutation_sums(values, graph, seed=_permutation_seed(random_state), n_permutations=R,
                                  return_null=bool(return_null) and R >= 1)
     out = {"mean": s["mean"], "m2": s["m2"], "m4": s["m4"], "n": s["n"], "n_edges": s["W"] // 2}
@@ -446,7 +352,7 @@ def spatial_permutation_test(values, graph, n_permutations=999, random_state=0, 
             with np.errstate(divide="ignore", invalid="ignore"):
                 scale = np.where(dead, np.nan, (float(s["n"]) / max(float(s["W"]), 1.0)) / np.sqrt(np.outer(s["m2"], s["m2"])))
             null = s["null"]
-            if _is_torch(null):
+            if _lib.is_torch(null):
                 import torch
                 null = null * torch.as_tensor(scale, device=null.device)
             else:

@@ -132,7 +132,7 @@ def test_argument_checks_come_before_the_gpu(monkeypatch):
         niches.spatial_niches(V, 2, max_iter=0)
     with pytest.raises(ValueError, match="cannot be used to seed"):
         niches.spatial_niches(V, 2, random_state="x")
-    # the graph's own checks (spatial_stats._resolve_graph) are host-side too
+    # the graph's own checks (_device.resolve_graph) are host-side too
     with pytest.raises(ValueError, match="5 rows but the graph has 6 spots"):
         niches.spatial_niches(V[:5], 2, ring, features="both")
     asym = ring.tolil()
