@@ -706,10 +706,15 @@ class FlashDeconv:
         library size over the mean library size is the natural choice for counts).  ``groups``: labels per spot (the ``labels``
         of ``get_spatial_niches``, say; ``-1`` = left out) for one signature matrix per group.  Further keywords (``n_groups``,
         ``ridge``, ``max_iter``, ``tol``, ``output``) go to ``celltype_expression``.  Works for both ``output`` kinds of ``fit``."""
+        from ..utils.expression import celltype_expression
+        return celltype_expression(Y, self._weights_for(Y, what, spot_scale), groups=groups, **kw)
+
+    def _weights_for(self, Y, what, spot_scale):
+        """The fitted weights a per-gene analysis of ``Y`` regresses on: ``proportions_`` or ``beta_``, their rows multiplied by
+        ``spot_scale`` where given; ``Y`` must have the fit's spots as rows."""
         self._require_fitted()
         if what not in ("proportions", "abundances"):
             raise ValueError(f"Unknown what: {what}. Choose from 'proportions', 'abundances'.")
-        from ..utils.expression import celltype_expression
         W = self.proportions_ if what == "proportions" else self.beta_
         n = int(W.shape[0])
         if not hasattr(Y, "shape") or len(Y.shape) != 2 or int(Y.shape[0]) != n:
@@ -726,7 +731,22 @@ class FlashDeconv:
                 W = W * torch.as_tensor(sc).to(device=W.device, dtype=W.dtype)[:, None]
             else:
                 W = W * sc[:, None]
-        return celltype_expression(Y, W, groups=groups, **kw)
+        return W
+
+    def get_spatially_variable_genes(self, Y, residual=False, what="proportions", spot_scale=None, n_top=None, **kw):
+        """Which genes vary over this tissue, and which still do once the fitted composition is accounted for (additive, not in
+        the reference): Moran's I and Geary's C per gene of ``Y`` over the graph the fit used, with z scores, p and q values -
+        ``utils.spatial_genes.spatially_variable_genes``.  ``Y``: ``n_spots_`` rows, dense or CSR, ANY gene set, scored as it is
+        passed.  ``residual=True`` also regresses every gene on ``proportions_`` (``what="proportions"``) or ``beta_``
+        (``what="abundances"``), their rows multiplied by ``spot_scale`` as in ``get_celltype_expression``, and reports Moran's I
+        of what the composition leaves (``residual_morans_i``, ``residual_z_score``, ``r2``, ``expression``): high for genes with
+        a gradient or a state of their own inside a cell type.  ``n_top``: also ``top``, the first genes of ``order``.  Further
+        keywords (``ridge``, ``max_iter``, ``tol``) go to the solve.  Works for both ``output`` kinds of ``fit``."""
+        if not isinstance(residual, (bool, np.bool_)):
+            raise ValueError(f"residual must be True or False, got {residual!r}")
+        W = self._weights_for(Y, what, spot_scale)
+        from ..utils.spatial_genes import spatially_variable_genes
+        return spatially_variable_genes(Y, self, weights=W if residual else None, n_top=n_top, **kw)
 
     def get_dominant_cell_type(self):
         self._require_fitted()

@@ -34,7 +34,7 @@ using namespace fdx;
 
 extern "C" {
 
-int fdx_version(void) { return 204; }  // 0.2.4: fdx_weighted_gene_sums_dev / _csr_dev and fdx_nnls_gram_dev added (nothing else changed)
+int fdx_version(void) { return 205; }  // 0.2.5: fdx_gene_spatial_sums_dev / _csr_dev added (nothing else changed)
 
 const char* fdx_last_error(void) { return g_last_error.c_str(); }
 

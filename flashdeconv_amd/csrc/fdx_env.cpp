@@ -49,7 +49,7 @@ Switch g_switches[] = {
     {"FDX_NO_PLAN_CACHE", "sketch plans / tile schedules, leverage scores, the X side and the spatial graph recomputed every fit (bench.py: cold_ms)"},
     {"FDX_NO_SIDE_STREAM", "everything on the caller's stream"},
     {"FDX_CSR_KEEP_CAP", "entries per wave of the fused CSR sketch's keep buffer (tests: rows that overflow it)"},
-    {"FDX_EXPR_STRIPE_SEGMENTS", "row segments per workgroup of the weighted gene sums (bit-identical: tests)"},
+    {"FDX_EXPR_STRIPE_SEGMENTS", "segments per workgroup of the weighted gene sums and of the gene spatial sums (bit-identical: tests)"},
 };
 constexpr int kSwitches = sizeof(g_switches) / sizeof(g_switches[0]);
 std::once_flag g_once;

@@ -188,6 +188,13 @@ int launch_weighted_gene_sums(const void* Y, int dtype, long long n, int G, long
 int launch_nnls_gram(const double* A, const double* B, const double* q, int C, int K, int G, double ridge, int max_iter, double tol,
                      double* S, int* n_iter, int* converged, double* rss, hipStream_t st);
 
+// ---- gene_spatial_kernels.cpp
+// The nine per-gene planes of fdx_gene_spatial_sums_dev / _csr_dev (fdx.h) over a whole graph of t.n >= 1 spots: Y dense (csr null)
+// or CSR; sums (9, G), deg_out (t.n, may be null) and counts = {sum deg, sum deg^2} on the device.  Everything queued on st; the
+// segment sums live in the pool.
+int launch_gene_spatial_sums(const GraphTables& t, const void* Y, int dtype, int G, long long ldy, const fdx_csr_view* csr,
+                             double* sums, int* deg_out, long long* counts, hipStream_t st);
+
 // ---- bcd_kernels.cpp
 int launch_bcd_sweep(const BcdSweepArgs& a, double* generic_scratch, size_t scratch_ld, hipStream_t st);
 // More than 64 cell types, no register-resident instantiation: the LDS-resident sweep (bcd_kernels.cpp) while K x 64 doubles fit;

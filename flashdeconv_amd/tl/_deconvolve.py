@@ -7,7 +7,7 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
                n_hvg=2000, n_markers_per_type=50, spatial_method="knn", k_neighbors=6, radius=None, preprocess="log_cpm",
                layer_st=None, layer_ref=None, spatial_key="spatial", key_added="flashdeconv", random_state=0, copy=False,
                spot_diagnostics=False, spatial_stats=False, n_niches=None, spatial_permutations=0, local_stats=False,
-               correlogram=False, celltype_expression=False):
+               correlogram=False, celltype_expression=False, spatial_genes=False):
     """Writes ``.obsm[key_added]`` (proportions DataFrame), ``.obs[key_added + '_dominant']`` and
     ``.uns[key_added + '_params']``; returns the modified copy when ``copy=True``, else ``None``.  ``spot_diagnostics=True``
     (additive) also writes ``.obs[key_added + '_residual']`` (relative sketch residual per spot) and
@@ -32,13 +32,20 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
     what each cell type expresses in this tissue - the per-gene non-negative least squares of the spot matrix on the
     proportions scaled by each spot's row sum over the mean row sum, ``FlashDeconv.get_celltype_expression``) and
     ``.uns[key_added + '_expression_r2']`` (Series over the common genes: the share of each gene's variance the fitted
-    composition explains)."""
+    composition explains).
+    ``spatial_genes=True`` (additive) also writes ``.uns[key_added + '_spatial_genes']`` (DataFrame indexed by the common genes:
+    Moran's ``I`` and Geary's ``C`` of each gene of the spot matrix over the fit's graph, the ``z_score`` under normality, the
+    one-sided ``p_value`` under randomisation and its Benjamini-Hochberg ``q_value``, and - regressed on the proportions scaled by
+    each spot's row sum over the mean row sum - ``residual_I``, ``residual_z_score`` of what the composition leaves and the
+    ``r2`` it explains, ``FlashDeconv.get_spatially_variable_genes``)."""
     from ..core.deconv import FlashDeconv
     from ..io import prepare_data, result_to_anndata
     from ..utils.correlogram import correlogram_request
     correlogram_kw = correlogram_request(correlogram)          # a bad request fails here, not behind the fit
     if not isinstance(celltype_expression, (bool, np.bool_)):
         raise ValueError(f"celltype_expression must be True or False, got {celltype_expression!r}")
+    if not isinstance(spatial_genes, (bool, np.bool_)):
+        raise ValueError(f"spatial_genes must be True or False, got {spatial_genes!r}")
 
     adata = adata_st.copy() if copy else adata_st
     Y, X, coords, names, genes = prepare_data(adata, adata_ref, cell_type_key=cell_type_key, layer_st=layer_st,
@@ -46,6 +53,9 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
     if celltype_expression:
         from ..utils.expression import check_request
         check_request(tuple(Y.shape), len(names))                # more cell types than the solve takes: fails here too
+    if spatial_genes:
+        from ..utils.spatial_genes import check_request as check_spatial_genes
+        check_spatial_genes(tuple(Y.shape), len(names))
     # like the reference, max_iter / tol / verbose are not exposed here (tl/_deconvolve.py:132-144)
     model = FlashDeconv(sketch_dim=sketch_dim, lambda_spatial=lambda_spatial, rho_sparsity=rho_sparsity, n_hvg=n_hvg,
                         n_markers_per_type=n_markers_per_type, spatial_method=spatial_method, k_neighbors=k_neighbors,
@@ -123,6 +133,14 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
                                                              columns=[str(t) for t in names])
         adata.uns[f"{key_added}_expression_r2"] = pd.Series(ex["r2"], index=[str(g) for g in genes])
         adata.uns[f"{key_added}_params"]["celltype_expression"] = True
+    if spatial_genes:
+        import pandas as pd
+        sv = model.get_spatially_variable_genes(Y, residual=True, spot_scale=_library_scale(Y))
+        adata.uns[f"{key_added}_spatial_genes"] = pd.DataFrame(
+            {"I": sv["morans_i"], "C": sv["gearys_c"], "z_score": sv["z_score"], "p_value": sv["p_value"], "q_value": sv["q_value"],
+             "residual_I": sv["residual_morans_i"], "residual_z_score": sv["residual_z_score"], "r2": sv["r2"]},
+            index=[str(g) for g in genes])
+        adata.uns[f"{key_added}_params"]["spatial_genes"] = True
     return adata if copy else None
 
 

@@ -1,7 +1,8 @@
 """Utilities of the path: the reference's ``flashdeconv/utils`` re-exports (utils/__init__.py:3-31), the evaluation metrics
 (``compute_rmse`` / ``compute_correlation``, utils/metrics.py) among them; the rest of the metrics are in ``utils.metrics``;
 ``spatial_autocorrelation`` / ``spatial_permutation_test`` (``utils.spatial_stats``), ``local_spatial_statistics`` (``utils.local_stats``), ``spatial_correlogram`` (``utils.correlogram``) and ``spatial_niches`` / ``kmeans`` / ``kmeans_plusplus`` (``utils.niches``) and
-``celltype_expression`` / ``weighted_gene_sums`` / ``nnls_gram`` (``utils.expression``) are additive."""
+``celltype_expression`` / ``weighted_gene_sums`` / ``nnls_gram`` (``utils.expression``) and ``spatially_variable_genes`` /
+``gene_spatial_sums`` / ``assemble_genes`` (``utils.spatial_genes``) are additive."""
 from .genes import select_hvg, select_markers, compute_leverage_scores  # noqa: F401
 from .graph import build_knn_graph, build_radius_graph, coords_to_adjacency  # noqa: F401
 from .random import check_random_state  # noqa: F401
@@ -11,9 +12,11 @@ from .local_stats import local_spatial_statistics, conditional_indices  # noqa: 
 from .correlogram import spatial_correlogram  # noqa: F401
 from .niches import spatial_niches, kmeans, kmeans_plusplus  # noqa: F401
 from .expression import celltype_expression, weighted_gene_sums, nnls_gram  # noqa: F401
+from .spatial_genes import spatially_variable_genes, gene_spatial_sums, assemble_genes  # noqa: F401
 
 __all__ = ["select_hvg", "select_markers", "compute_leverage_scores", "build_knn_graph", "build_radius_graph",
            "coords_to_adjacency", "check_random_state", "compute_rmse", "compute_correlation",
            "spatial_autocorrelation", "spatial_niches", "kmeans", "kmeans_plusplus", "spatial_permutation_test",
            "permutation_indices", "randomization_variance", "local_spatial_statistics", "conditional_indices",
-           "spatial_correlogram", "celltype_expression", "weighted_gene_sums", "nnls_gram"]
+           "spatial_correlogram", "celltype_expression", "weighted_gene_sums", "nnls_gram", "spatially_variable_genes",
+           "gene_spatial_sums", "assemble_genes"]

@@ -1,6 +1,6 @@
-"""What the analysis entries under ``utils/`` share on their way to the device (private): the checks of ``values`` and of the graph
-argument, the device a call runs on, and the upload of a matrix.  Everything that can fail on the host fails here, before the GPU is
-touched."""
+"""What the analysis entries under ``utils/`` share on their way to the device (private): the checks of ``values``, of a spot-by-gene
+matrix and of the graph argument, the device a call runs on, the upload of a matrix and the routes of a spot-by-gene matrix to the
+kernels that stream it.  Everything that can fail on the host fails here, before the GPU is touched."""
 import contextlib
 import ctypes
 
@@ -56,6 +56,61 @@ def values_on_device(values, device, stream, dtype=None):
     _lib.check(_lib.load().fdx_upload_convert_dev(ctypes.c_void_p(d.data_ptr()), _lib.dtype_code(dtype),
                                                   a.ctypes.data_as(ctypes.c_void_p), _lib.SRC_CODES[a.dtype.name], a.size, None, stream))
     return d, a.shape[1]
+
+
+def is_scipy_sparse(Y):
+    try:
+        from scipy import sparse
+    except ImportError:                                   # pragma: no cover
+        return False
+    return sparse.issparse(Y)
+
+
+def check_matrix(Y):
+    """(n, G) of a 2-D spot-by-gene matrix with at least one gene."""
+    if not hasattr(Y, "shape"):
+        Y = np.asarray(Y)
+    shape = tuple(Y.shape)
+    if len(shape) != 2:
+        raise ValueError(f"Y must be a 2-D (n_spots, n_genes) matrix, got shape {shape}")
+    if shape[1] < 1:
+        raise ValueError(f"Y must have at least one gene, got shape {shape}")
+    if _lib.is_cuda_tensor(Y) and not _lib.is_torch_sparse_csr(Y) and str(Y.layout) != "torch.strided":
+        raise ValueError(f"a sparse CUDA Y must be torch.sparse_csr, got {Y.layout}")
+    return int(shape[0]), int(shape[1])
+
+
+@contextlib.contextmanager
+def matrix_on_device(Y, device):
+    """The spot-by-gene matrix ``Y`` as the kernels stream it, for the length of a ``with`` block: ``("csr", CsrOnDevice)`` for a
+    scipy sparse matrix or a CUDA ``torch.sparse_csr`` tensor (rows as they are: not sorted), else ``("dense", pointer, dtype code,
+    row stride)`` - a dense CUDA tensor where it lies (integer counts converted, a column stride removed), a host matrix through
+    ``_lib.upload_matrix``.  What was uploaded for the call is freed at the end of the block, after torch's current stream has
+    finished with it."""
+    import torch
+    if is_scipy_sparse(Y) or _lib.is_torch_sparse_csr(Y):
+        csr = _lib.CsrOnDevice.from_scipy(Y, sort=False) if is_scipy_sparse(Y) else _lib.CsrOnDevice.from_torch(Y)
+        try:
+            yield ("csr", csr)
+            torch.cuda.current_stream(device).synchronize()       # the arrays go back to the allocator below
+        finally:
+            csr.free()
+    elif _lib.is_cuda_tensor(Y):
+        Yd = Y.detach()
+        if Yd.dtype not in (torch.float32, torch.float64):
+            from ..core.deconv import device_counts_as_float
+            Yd, _ = device_counts_as_float(Yd)
+        if Yd.stride(1) != 1 or Yd.stride(0) < Yd.shape[1]:
+            Yd = Yd.contiguous()
+        yield ("dense", ctypes.c_void_p(Yd.data_ptr()), _lib.dtype_code(Yd), int(Yd.stride(0)))
+    else:
+        Yh = Y.detach().numpy() if _lib.is_torch(Y) else np.asarray(Y)
+        ptr, code = _lib.upload_matrix(Yh)
+        try:
+            yield ("dense", ptr, code, int(Yh.shape[1]))
+            torch.cuda.current_stream(device).synchronize()
+        finally:
+            _lib.load().fdx_free(ptr)
 
 
 def _check_adjacency(A, n_rows):

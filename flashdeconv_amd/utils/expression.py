@@ -42,33 +42,11 @@ import ctypes
 import numpy as np
 
 from .. import _lib
-from ._device import device_of
+from ._device import check_matrix as _check_Y, device_of, matrix_on_device
 
 __all__ = ["celltype_expression", "weighted_gene_sums", "nnls_gram", "check_request", "MAX_TYPES"]
 
 MAX_TYPES = 272
-
-
-def _is_sparse(Y):
-    try:
-        from scipy import sparse
-    except ImportError:                                   # pragma: no cover
-        return False
-    return sparse.issparse(Y)
-
-
-def _check_Y(Y):
-    """(n, G) of a 2-D spot-by-gene matrix with at least one gene."""
-    if not hasattr(Y, "shape"):
-        Y = np.asarray(Y)
-    shape = tuple(Y.shape)
-    if len(shape) != 2:
-        raise ValueError(f"Y must be a 2-D (n_spots, n_genes) matrix, got shape {shape}")
-    if shape[1] < 1:
-        raise ValueError(f"Y must have at least one gene, got shape {shape}")
-    if _lib.is_cuda_tensor(Y) and not _lib.is_torch_sparse_csr(Y) and str(Y.layout) != "torch.strided":
-        raise ValueError(f"a sparse CUDA Y must be torch.sparse_csr, got {Y.layout}")
-    return int(shape[0]), int(shape[1])
 
 
 def _check_weights(W, n):
@@ -213,33 +191,14 @@ def _sums_device(Y, W, labels, C, n, G, K):
         u = torch.empty((C, G), dtype=torch.float64, device=device)
         out = [ctypes.c_void_p(t.data_ptr()) for t in (A, B, q, u)]
         rows_p = ctypes.c_void_p(rows.data_ptr()) if rows is not None else None
-        if _is_sparse(Y) or _lib.is_torch_sparse_csr(Y):
-            csr = _lib.CsrOnDevice.from_scipy(Y, sort=False) if _is_sparse(Y) else _lib.CsrOnDevice.from_torch(Y)
-            try:
-                _lib.check(lib.fdx_weighted_gene_sums_csr_dev(ctypes.byref(csr.view), ctypes.c_void_p(Wd.data_ptr()), int(ldw), K,
+        with matrix_on_device(Y, device) as m:
+            if m[0] == "csr":
+                _lib.check(lib.fdx_weighted_gene_sums_csr_dev(ctypes.byref(m[1].view), ctypes.c_void_p(Wd.data_ptr()), int(ldw), K,
                                                               rows_p, _lib.ptr_i32(off), C, *out, stream))
-                torch.cuda.current_stream(device).synchronize()       # the arrays go back to the allocator below
-            finally:
-                csr.free()
-        elif _lib.is_cuda_tensor(Y):
-            Yd = Y.detach()
-            if Yd.dtype not in (torch.float32, torch.float64):
-                from ..core.deconv import device_counts_as_float
-                Yd, _ = device_counts_as_float(Yd)
-            if Yd.stride(1) != 1 or Yd.stride(0) < G:
-                Yd = Yd.contiguous()
-            _lib.check(lib.fdx_weighted_gene_sums_dev(ctypes.c_void_p(Yd.data_ptr()), _lib.dtype_code(Yd), n, G, int(Yd.stride(0)),
-                                                      ctypes.c_void_p(Wd.data_ptr()), int(ldw), K, rows_p, _lib.ptr_i32(off), C, *out,
-                                                      stream))
-        else:
-            Yh = Y.detach().numpy() if _lib.is_torch(Y) else np.asarray(Y)
-            ptr, code = _lib.upload_matrix(Yh)
-            try:
-                _lib.check(lib.fdx_weighted_gene_sums_dev(ptr, code, n, G, G, ctypes.c_void_p(Wd.data_ptr()), int(ldw), K, rows_p,
+            else:
+                _, ptr, code, ldy = m
+                _lib.check(lib.fdx_weighted_gene_sums_dev(ptr, code, n, G, ldy, ctypes.c_void_p(Wd.data_ptr()), int(ldw), K, rows_p,
                                                           _lib.ptr_i32(off), C, *out, stream))
-                torch.cuda.current_stream(device).synchronize()
-            finally:
-                lib.fdx_free(ptr)
     return A, B, q, u, np.diff(off.astype(np.int64))
 
 

@@ -729,6 +729,30 @@ int fdx_weighted_gene_sums_csr_dev(const fdx_csr_view* Y, const double* W_dev, i
 int fdx_nnls_gram_dev(const double* A_dev, const double* B_dev, const double* q_dev, int32_t C, int32_t K, int32_t G, double ridge,
                       int32_t max_iter, double tol, double* S_dev, int32_t* n_iter_dev, int32_t* converged_dev, double* rss_dev,
                       void* stream);
+/* ---- spatially variable genes (additive, not in the reference; csrc/gene_spatial_kernels.cpp) ----------------------------------- *
+ * Per gene of Y (n, G) - rows in the CALLER's spot order; dense FDX_F32 / FDX_F64 with row stride ldy >= G, or a CSR view whose rows
+ * have distinct columns (sorted or not: sorted_rows is honoured, stored zeros are legal) - the sums from which Moran's I, Geary's
+ * C and their moments are assembled, over a WHOLE graph g of n spots (a shard's local graph is refused): A its symmetric binary
+ * adjacency, deg_i = sum_j A_ij.  sums_dev: (9, G) row-major float64 on the DEVICE, all arithmetic float64 on the value converted
+ * from its storage type:
+ *   0 u = sum_i y_i        1 q = sum_i y_i*y_i        2 c3 = sum_i (y_i*y_i)*y_i        3 c4 = sum_i (y_i*y_i)*(y_i*y_i)
+ *   4 D = sum_i deg_i*y_i  5 H = sum_i deg_i*(y_i*y_i)
+ *   6 P = sum_i y_i*lag_i, lag_i = sum_{j in N(i)} y_j added in the graph's stored neighbour order
+ *   7 ymin = min_i y_i     8 ymax = max_i y_i
+ * A CSR entry that is not stored is the value 0: it adds nothing to planes 0-6 and takes part in min / max exactly when its column
+ * stores fewer than n entries.  deg_dev: NULL, or n int32 on the DEVICE, deg_i in the caller's order.  counts_out (HOST) =
+ * {n, W = sum deg, sum deg^2}, what fdx_spatial_autocorr_dev returns.  n = 0: zeros, NaN in planes 7 and 8.
+ * The order of every sum is fixed by the graph alone: its positions (position p holds the caller's spot perm[p]) are cut into
+ * segments of FDX_GENE_SPATIAL_SEGMENT_POSITIONS, a segment is added position after position and the segment sums are added in
+ * ascending order.  No floating-point atomics; two calls return the same bits, and so does a call whose launch gives a workgroup
+ * more or fewer segments (FDX_EXPR_STRIPE_SEGMENTS) or keeps fewer segment sums in flight (they live in the library's pool, about
+ * 1 GiB at a time: beyond that the segments go in batches and the sums continue from the previous batch's).  One host
+ * synchronisation, for counts_out.  Refused with a message: null pointers, G < 1, ldy < G, n other than the graph's, n >= 2^31 - 128. */
+#define FDX_GENE_SPATIAL_SEGMENT_POSITIONS 256
+int fdx_gene_spatial_sums_dev(const fdx_graph* g, const void* Y_dev, int32_t dtype, int64_t n, int32_t G, int64_t ldy,
+                              double* sums_dev, int32_t* deg_dev, int64_t* counts_out, void* stream);
+int fdx_gene_spatial_sums_csr_dev(const fdx_graph* g, const fdx_csr_view* Y, double* sums_dev, int32_t* deg_dev, int64_t* counts_out,
+                                  void* stream);
 /* beta (K, ld) type-major -> beta_out / prop_out (n, K) row-major in solver order of the own spots. */
 int fdx_normalize_dev(const double* beta_dev, int64_t ld, int64_t n, int32_t K, double* beta_out_dev, double* prop_out_dev,
                       void* stream);
