@@ -18,6 +18,7 @@
 // candidates again - in a wave of their own (blockIdx.y), so that a small slide still fills the device.  No atomics; every sum
 // is formed in candidate order (cells of the block in z, y, x order, positions ascending), which depends on neither the grid,
 // nor KC, nor the chunk of bands.
+#include "gene_pass.h"
 #include "graph_internal.h"
 
 #include <vector>
@@ -218,7 +219,7 @@ CorrelogramPlan correlogram_plan(long long n, int K, int B, int max_bands_per_pa
     const size_t KK = (size_t)K * K;
     // per band in flight: its lag planes and its cross partials
     const size_t per_band = ((size_t)K * p.s.ld + (size_t)p.s.cross_blocks * KK) * sizeof(double);
-    long long bc = (long long)std::max<size_t>(1, spatial_scratch_budget_bytes() / per_band);
+    long long bc = (long long)std::max<size_t>(1, SCRATCH_BUDGET_BYTES / per_band);
     bc = std::min<long long>(bc, B);
     if (max_bands_per_pass > 0) bc = std::min<long long>(bc, max_bands_per_pass);
     p.bands_per_pass = (int)std::max<long long>(1, bc);

@@ -3,9 +3,9 @@
 // (float32 / float64 dense with any row stride, or CSR), and the G x C small non-negative solves (include/fdx.h has the definitions).
 //
 // Order of the sums.  The rows of a group, in the order of the sorted row list, are cut into SEGMENTS of FDX_EXPRESSION_SEGMENT_ROWS
-// rows; a segment is summed row after row into zeroed accumulators (fma), its sums go to a scratch block, and expr_fold_kernel adds
-// the segment sums of a group in ascending order.  That order is a function of the row list alone: how many segments a workgroup
-// takes (its stripe), how many segments are in flight at once (the scratch budget) and which thread owns a gene change no bit.
+// rows; a segment is summed row after row into zeroed accumulators (fma), its sums go to a scratch block, and the fold adds the
+// segment sums of a group in ascending order.  That order is a function of the row list alone; gene_pass.h has the rule for what
+// changes no bit of it (stripe, batches of segments, the thread of a gene) and the fold.
 //
 // Dense: a thread per two gene columns (coalesced rows), a chunk of 32 (last chunk: 16) accumulators per gene in registers, the
 // weights of a row wave-uniform from a padded copy of W in segment order (Wp), staged in LDS 64 rows at a time and read by
@@ -14,18 +14,19 @@
 // (entry slot, type) and adds into the segment's block [gene][type] in global memory - the entries of a row have distinct columns,
 // so no two threads meet between barriers; rows need not be sorted.
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 
-#include "fdx_env.h"
 #include "fdx_internal.h"
 #include "fdx_kernels.h"
+#include "gene_pass.h"
 
 namespace fdx {
 namespace {
 
 constexpr int SEG = FDX_EXPRESSION_SEGMENT_ROWS;
-constexpr size_t PART_BUDGET_BYTES = (size_t)1 << 30;
+constexpr int EXPR_KC = 32, EXPR_KC_TAIL = 16;   // accumulators a thread of the dense kernel keeps: full chunks, and a last chunk of <= 16
+constexpr int EXPR_CSR_KC = 8;                   // types a workgroup of the CSR kernel adds per pass over its rows
+constexpr int EXPR_NNLS_LDS_MAX_K = 88;          // the solve keeps A_c in LDS up to here (88 * 88 doubles < 64 KB), reads it through L2 above
 
 // Wp (n_sel, Kpad): row p = W[rows[p]] (rows null: W[p]), zeros in columns K .. Kpad - 1
 __global__ __launch_bounds__(256) void expr_gather_w_kernel(const double* __restrict__ W, long long ldw, const int* __restrict__ rows,
@@ -194,31 +195,6 @@ __global__ __launch_bounds__(256) void expr_csr_kernel(const long long* __restri
     }
 }
 
-// out[c * group_stride + plane * out_ld + j] = the sums of group c's segments inside this batch [sb0, sb0 + nb), in ascending order,
-// continued from the value already there when the group began in an earlier batch.  Element (s, plane, j) of the batch's block is
-// part[(s - sb0) * seg_stride + (plane0 + plane) * plane_stride + j * gene_stride].
-__global__ __launch_bounds__(256) void expr_fold_kernel(const double* __restrict__ part, long long seg_stride, long long plane_stride,
-                                                        long long gene_stride, int plane0, int G, const int* __restrict__ group_seg,
-                                                        int sb0, int nb, double* out, long long group_stride, long long out_ld) {
-    const int j = blockIdx.x * 256 + threadIdx.x, plane = blockIdx.y, c = blockIdx.z;
-    if (j >= G) return;
-    const int g_lo = group_seg[c], g_hi = group_seg[c + 1];
-    const int lo = max(g_lo, sb0), hi = min(g_hi, sb0 + nb);
-    double* o = out + (size_t)c * group_stride + (size_t)plane * out_ld + j;
-    double sum = sb0 <= g_lo ? 0.0 : *o;
-    const double* in = part + (size_t)(plane0 + plane) * plane_stride + (size_t)j * gene_stride;
-    int s = lo;
-    for (; s + 8 <= hi; s += 8) {                   // eight loads in flight, added in ascending order
-        double v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = in[(size_t)(s + i - sb0) * seg_stride];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) sum += v[i];
-    }
-    for (; s < hi; ++s) sum += in[(size_t)(s - sb0) * seg_stride];
-    *o = sum;
-}
-
 __device__ __forceinline__ double readlane_f64(double v, int l) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
     return __hiloint2double(hi, lo);
@@ -330,97 +306,68 @@ __global__ __launch_bounds__(256) void nnls_gram_kernel(const double* __restrict
     }
 }
 
-int stripe_segments() {
-    const char* v = env("FDX_EXPR_STRIPE_SEGMENTS");
-    const int s = v ? atoi(v) : 1;
-    return s >= 1 ? s : 1;
+// The segments of the weighted sums on the device: {first, end} positions per segment, the C + 1 segment offsets of the groups
+struct ExprSegments { const int *seg, *group_seg; int n_seg, C; };
+// out (C, planes, G) = the planes plane0 .. of the batch b folded per group: sums only
+int fold_groups(const SegmentBlocks& b, int plane0, int planes, int G, const ExprSegments& sg, double* out, hipStream_t st) {
+    return launch_gene_fold(b, plane0, planes, G, sg.group_seg, sg.C, out, (long long)planes * G, (long long)G, -1, -1, st);
 }
 
 // One dense pass over `Yd` (n_sel positions through yrows) for all chunks of Wp, in batches of segments, folded into `out`
 // (planes 0 .. K - 1 -> out[c][k][g]) and, with q_out / u_out, the two moment planes.
 template <typename T>
-int dense_passes(const T* Yd, long long ldy, const int* yrows, const double* Wp, int K, int Kpad, const int* seg_dev,
-                 const int* gseg_dev, int n_seg, int C, int G, double* out, double* q_out, double* u_out, hipStream_t st) {
+int dense_passes(const T* Yd, long long ldy, const int* yrows, const double* Wp, int K, int Kpad, const ExprSegments& sg, int G,
+                 double* out, double* q_out, double* u_out, hipStream_t st) {
     const bool qu = q_out != nullptr;
     const int planes = Kpad + (qu ? 2 : 0);
     const int stripe = stripe_segments();
-    const size_t seg_bytes = (size_t)planes * G * sizeof(double);
-    const int batch = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_seg, PART_BUDGET_BYTES / seg_bytes));
-    DevBuf part;
-    FDX_TRY(part.alloc((size_t)batch * seg_bytes));
-    const unsigned gene_tiles = (unsigned)ceil_div(G, 256);
-    for (int sb0 = 0; sb0 < n_seg; sb0 += batch) {
-        const int nb = std::min(batch, n_seg - sb0);
+    return for_segment_batches(sg.n_seg, (size_t)planes * G * sizeof(double), [&](int sb0, int nb, double* part) {
         const dim3 grid((unsigned)ceil_div(nb, stripe), (unsigned)ceil_div(G, EXPR_GENES));
         for (int k0 = 0; k0 < Kpad;) {
-            const int with_qu = qu && k0 == 0;     // the moment planes ride with the first chunk
-            if (Kpad - k0 >= EXPR_KC) {
-                hipLaunchKernelGGL((expr_dense_kernel<T, EXPR_KC>), grid, dim3(256), 0, st, Yd, ldy, yrows ? yrows : nullptr, Wp, Kpad,
-                                   k0, seg_dev + 2 * (size_t)sb0, nb, stripe, G, with_qu, part.as<double>(), planes);
-                k0 += EXPR_KC;
-            } else {
-                hipLaunchKernelGGL((expr_dense_kernel<T, EXPR_KC_TAIL>), grid, dim3(256), 0, st, Yd, ldy, yrows ? yrows : nullptr, Wp,
-                                   Kpad, k0, seg_dev + 2 * (size_t)sb0, nb, stripe, G, with_qu, part.as<double>(), planes);
-                k0 += EXPR_KC_TAIL;
-            }
+            const bool full = Kpad - k0 >= EXPR_KC;
+            auto* kernel = full ? expr_dense_kernel<T, EXPR_KC> : expr_dense_kernel<T, EXPR_KC_TAIL>;
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, Yd, ldy, yrows, Wp, Kpad, k0, sg.seg + 2 * (size_t)sb0, nb, stripe, G,
+                               qu && k0 == 0, part, planes);      // the moment planes ride with the first chunk
             FDX_CHECK_LAUNCH();
+            k0 += full ? EXPR_KC : EXPR_KC_TAIL;
         }
-        const long long seg_stride = (long long)planes * G;
-        hipLaunchKernelGGL(expr_fold_kernel, dim3(gene_tiles, (unsigned)K, (unsigned)C), dim3(256), 0, st, part.as<double>(), seg_stride,
-                           (long long)G, 1LL, 0, G, gseg_dev, sb0, nb, out, (long long)K * G, (long long)G);
-        FDX_CHECK_LAUNCH();
-        if (qu) {
-            hipLaunchKernelGGL(expr_fold_kernel, dim3(gene_tiles, 1, (unsigned)C), dim3(256), 0, st, part.as<double>(), seg_stride,
-                               (long long)G, 1LL, Kpad, G, gseg_dev, sb0, nb, q_out, (long long)G, (long long)G);
-            FDX_CHECK_LAUNCH();
-            hipLaunchKernelGGL(expr_fold_kernel, dim3(gene_tiles, 1, (unsigned)C), dim3(256), 0, st, part.as<double>(), seg_stride,
-                               (long long)G, 1LL, Kpad + 1, G, gseg_dev, sb0, nb, u_out, (long long)G, (long long)G);
-            FDX_CHECK_LAUNCH();
-        }
-    }
-    return 0;
+        const SegmentBlocks b{part, (long long)planes * G, (long long)G, 1LL, sb0, nb};
+        FDX_TRY(fold_groups(b, 0, K, G, sg, out, st));
+        if (!qu) return 0;
+        FDX_TRY(fold_groups(b, Kpad, 1, G, sg, q_out, st));
+        return fold_groups(b, Kpad + 1, 1, G, sg, u_out, st);
+    });
 }
 
+// The CSR pass: a batch's scratch is [segment][gene][type] for the batch's segments, then [segment][{q, u}][gene]
 template <typename T>
-int csr_passes(const fdx_csr_view* Y, const int* yrows, const double* Wp, int K, int Kpad, const int* seg_dev, const int* gseg_dev,
-               int n_seg, int C, double* B, double* q_out, double* u_out, hipStream_t st) {
+int csr_passes(const fdx_csr_view* Y, const T* values, const int* yrows, const double* Wp, int K, int Kpad, const ExprSegments& sg, double* B,
+               double* q_out, double* u_out, hipStream_t st) {
     const int G = Y->G;
     const int stripe = stripe_segments();
     const size_t seg_bytes = (size_t)(Kpad + 2) * G * sizeof(double);
-    const int batch = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_seg, PART_BUDGET_BYTES / seg_bytes));
-    DevBuf part;
-    FDX_TRY(part.alloc((size_t)batch * seg_bytes));
-    double* qu_part = part.as<double>() + (size_t)batch * G * Kpad;
-    const unsigned gene_tiles = (unsigned)ceil_div(G, 256);
-    for (int sb0 = 0; sb0 < n_seg; sb0 += batch) {
-        const int nb = std::min(batch, n_seg - sb0);
+    const size_t qu_offset = (size_t)segment_batch(sg.n_seg, seg_bytes) * G * Kpad;
+    return for_segment_batches(sg.n_seg, seg_bytes, [&](int sb0, int nb, double* part) {
+        double* qu_part = part + qu_offset;
         hipLaunchKernelGGL(expr_csr_kernel<T>, dim3((unsigned)ceil_div(nb, stripe), (unsigned)(Kpad / EXPR_CSR_KC)), dim3(256), 0, st,
-                           (const long long*)Y->indptr, Y->indices, (const T*)Y->data, yrows, Wp, Kpad, seg_dev + 2 * (size_t)sb0, nb,
-                           stripe, G, part.as<double>(), qu_part);
+                           (const long long*)Y->indptr, Y->indices, values, yrows, Wp, Kpad, sg.seg + 2 * (size_t)sb0, nb,
+                           stripe, G, part, qu_part);
         FDX_CHECK_LAUNCH();
-        hipLaunchKernelGGL(expr_fold_kernel, dim3(gene_tiles, (unsigned)K, (unsigned)C), dim3(256), 0, st, part.as<double>(),
-                           (long long)G * Kpad, 1LL, (long long)Kpad, 0, G, gseg_dev, sb0, nb, B, (long long)K * G, (long long)G);
-        FDX_CHECK_LAUNCH();
-        hipLaunchKernelGGL(expr_fold_kernel, dim3(gene_tiles, 1, (unsigned)C), dim3(256), 0, st, qu_part, 2LL * G, (long long)G, 1LL, 0,
-                           G, gseg_dev, sb0, nb, q_out, (long long)G, (long long)G);
-        FDX_CHECK_LAUNCH();
-        hipLaunchKernelGGL(expr_fold_kernel, dim3(gene_tiles, 1, (unsigned)C), dim3(256), 0, st, qu_part, 2LL * G, (long long)G, 1LL, 1,
-                           G, gseg_dev, sb0, nb, u_out, (long long)G, (long long)G);
-        FDX_CHECK_LAUNCH();
-    }
-    return 0;
+        const SegmentBlocks b{part, (long long)G * Kpad, 1LL, (long long)Kpad, sb0, nb}, m{qu_part, 2LL * G, (long long)G, 1LL, sb0, nb};
+        FDX_TRY(fold_groups(b, 0, K, G, sg, B, st));
+        FDX_TRY(fold_groups(m, 0, 1, G, sg, q_out, st));
+        return fold_groups(m, 1, 1, G, sg, u_out, st);
+    });
 }
 
-}  // namespace
-
-int launch_weighted_gene_sums(const void* Y, int dtype, long long n, int G, long long ldy, const fdx_csr_view* csr, const double* W,
-                              long long ldw, int K, const int* rows, const int* group_off, int C, double* A, double* B, double* q,
-                              double* u, hipStream_t st) {
+// group_off on the HOST (fdx.h).  Everything queued on st; scratch from the pool.
+int launch_weighted_gene_sums(const GeneMatrix& y, const double* W, long long ldw, int K, const int* rows, const int* group_off, int C,
+                              double* A, double* B, double* q, double* u, hipStream_t st) {
     // the segments of every group, as positions of the sorted row list
     std::vector<int> tab;                          // {first, end} per segment, then the C + 1 segment offsets of the groups
     std::vector<int> gseg((size_t)C + 1);
     for (int c = 0; c < C; ++c) {
-        const long long lo = rows ? group_off[c] : 0, hi = rows ? group_off[c + 1] : n;
+        const long long lo = rows ? group_off[c] : 0, hi = rows ? group_off[c + 1] : y.n;
         gseg[c] = (int)(tab.size() / 2);
         for (long long p = lo; p < hi; p += SEG) {
             tab.push_back((int)p);
@@ -429,12 +376,12 @@ int launch_weighted_gene_sums(const void* Y, int dtype, long long n, int G, long
     }
     const int n_seg = (int)(tab.size() / 2);
     gseg[C] = n_seg;
-    const long long n_sel = rows ? group_off[C] : n;
+    const long long n_sel = rows ? group_off[C] : y.n;
     if (n_seg == 0) {                              // nothing listed: every sum is empty
         FDX_HIP(hipMemsetAsync(A, 0, (size_t)C * K * K * sizeof(double), st));
-        FDX_HIP(hipMemsetAsync(B, 0, (size_t)C * K * G * sizeof(double), st));
-        FDX_HIP(hipMemsetAsync(q, 0, (size_t)C * G * sizeof(double), st));
-        FDX_HIP(hipMemsetAsync(u, 0, (size_t)C * G * sizeof(double), st));
+        FDX_HIP(hipMemsetAsync(B, 0, (size_t)C * K * y.G * sizeof(double), st));
+        FDX_HIP(hipMemsetAsync(q, 0, (size_t)C * y.G * sizeof(double), st));
+        FDX_HIP(hipMemsetAsync(u, 0, (size_t)C * y.G * sizeof(double), st));
         return 0;
     }
     tab.insert(tab.end(), gseg.begin(), gseg.end());
@@ -444,21 +391,16 @@ int launch_weighted_gene_sums(const void* Y, int dtype, long long n, int G, long
     FDX_TRY(tab_dev.alloc(tab.size() * sizeof(int)));
     FDX_TRY(wp.alloc((size_t)n_sel * Kpad * sizeof(double)));
     FDX_TRY(copy_h2d(tab_dev.p, tab.data(), tab.size() * sizeof(int), st));
-    const int* seg_dev = tab_dev.as<int>();
-    const int* gseg_dev = seg_dev + 2 * (size_t)n_seg;
+    const ExprSegments sg{tab_dev.as<int>(), tab_dev.as<int>() + 2 * (size_t)n_seg, n_seg, C};
     double* Wp = wp.as<double>();
     hipLaunchKernelGGL(expr_gather_w_kernel, dim3((unsigned)ceil_div(n_sel * Kpad, 256)), dim3(256), 0, st, W, ldw, rows, n_sel, K, Kpad,
                        Wp);
     FDX_CHECK_LAUNCH();
     // A = W'W: the dense pass with Y := Wp (already in segment order)
-    FDX_TRY(dense_passes<double>(Wp, (long long)Kpad, nullptr, Wp, K, Kpad, seg_dev, gseg_dev, n_seg, C, K, A, nullptr, nullptr, st));
-    if (csr) {
-        if (csr->dtype == FDX_F32) return csr_passes<float>(csr, rows, Wp, K, Kpad, seg_dev, gseg_dev, n_seg, C, B, q, u, st);
-        return csr_passes<double>(csr, rows, Wp, K, Kpad, seg_dev, gseg_dev, n_seg, C, B, q, u, st);
-    }
-    if (dtype == FDX_F32)
-        return dense_passes<float>((const float*)Y, ldy, rows, Wp, K, Kpad, seg_dev, gseg_dev, n_seg, C, G, B, q, u, st);
-    return dense_passes<double>((const double*)Y, ldy, rows, Wp, K, Kpad, seg_dev, gseg_dev, n_seg, C, G, B, q, u, st);
+    FDX_TRY(dense_passes(Wp, (long long)Kpad, nullptr, Wp, K, Kpad, sg, K, A, nullptr, nullptr, st));
+    return dispatch_gene_matrix(
+        y, [&](auto* Yd) { return dense_passes(Yd, y.ldy, rows, Wp, K, Kpad, sg, y.G, B, q, u, st); },
+        [&](auto* values) { return csr_passes(y.csr, values, rows, Wp, K, Kpad, sg, B, q, u, st); });
 }
 
 int launch_nnls_gram(const double* A, const double* B, const double* q, int C, int K, int G, double ridge, int max_iter, double tol,
@@ -481,11 +423,6 @@ int launch_nnls_gram(const double* A, const double* B, const double* q, int C, i
     return 0;
 }
 
-}  // namespace fdx
-
-using namespace fdx;
-
-namespace {
 int check_groups(const char* who, int64_t n, int32_t K, int64_t ldw, const int32_t* rows_dev, const int32_t* group_off, int32_t C) {
     const std::string w(who);
     FDX_REQUIRE(K >= 1 && K <= FDX_EXPRESSION_MAX_K, w + ": K must be 1 .. 272");
@@ -501,35 +438,35 @@ int check_groups(const char* who, int64_t n, int32_t K, int64_t ldw, const int32
     FDX_REQUIRE(group_off[C] <= n, w + ": more rows listed than Y has");
     return 0;
 }
+
+int weighted_gene_sums_entry(const char* who, const GeneMatrix& y, const double* W_dev, int64_t ldw, int32_t K, const int32_t* rows_dev,
+                             const int32_t* group_off, int32_t C, double* A_dev, double* B_dev, double* q_dev, double* u_dev,
+                             void* stream) {
+    FDX_TRY(check_gene_matrix(who, y, A_dev && B_dev && q_dev && u_dev && (y.n == 0 || W_dev), true, "bad shape"));
+    FDX_TRY(check_groups(who, y.n, K, ldw, rows_dev, group_off, C));
+    PoolStream pool_stream((hipStream_t)stream);
+    return launch_weighted_gene_sums(y, W_dev, ldw, K, rows_dev, group_off, C, A_dev, B_dev, q_dev, u_dev, (hipStream_t)stream);
+}
+
 }  // namespace
+}  // namespace fdx
+
+using namespace fdx;
 
 extern "C" {
 
 int fdx_weighted_gene_sums_dev(const void* Y_dev, int32_t dtype, int64_t n, int32_t G, int64_t ldy, const double* W_dev, int64_t ldw,
                                int32_t K, const int32_t* rows_dev, const int32_t* group_off, int32_t C, double* A_dev, double* B_dev,
                                double* q_dev, double* u_dev, void* stream) {
-    FDX_REQUIRE(A_dev && B_dev && q_dev && u_dev && (n == 0 || (Y_dev && W_dev)), "fdx_weighted_gene_sums_dev: null argument");
-    FDX_REQUIRE(G >= 1 && ldy >= G, "fdx_weighted_gene_sums_dev: bad shape");
-    FDX_REQUIRE(dtype == FDX_F32 || dtype == FDX_F64, "fdx_weighted_gene_sums_dev: dtype must be FDX_F32 or FDX_F64");
-    FDX_TRY(check_groups("fdx_weighted_gene_sums_dev", n, K, ldw, rows_dev, group_off, C));
-    hipStream_t st = (hipStream_t)stream;
-    PoolStream pool_stream(st);
-    return launch_weighted_gene_sums(Y_dev, dtype, n, G, ldy, nullptr, W_dev, ldw, K, rows_dev, group_off, C, A_dev, B_dev, q_dev, u_dev,
-                                     st);
+    return weighted_gene_sums_entry("fdx_weighted_gene_sums_dev", GeneMatrix(Y_dev, dtype, n, G, ldy), W_dev, ldw, K, rows_dev, group_off, C,
+                                    A_dev, B_dev, q_dev, u_dev, stream);
 }
 
 int fdx_weighted_gene_sums_csr_dev(const fdx_csr_view* Y, const double* W_dev, int64_t ldw, int32_t K, const int32_t* rows_dev,
                                    const int32_t* group_off, int32_t C, double* A_dev, double* B_dev, double* q_dev, double* u_dev,
                                    void* stream) {
-    FDX_REQUIRE(Y && A_dev && B_dev && q_dev && u_dev && (Y->n == 0 || (Y->indptr && W_dev)),
-                "fdx_weighted_gene_sums_csr_dev: null argument");
-    FDX_REQUIRE(Y->G >= 1 && (Y->nnz == 0 || (Y->indices && Y->data)), "fdx_weighted_gene_sums_csr_dev: bad view");
-    FDX_REQUIRE(Y->dtype == FDX_F32 || Y->dtype == FDX_F64, "fdx_weighted_gene_sums_csr_dev: dtype must be FDX_F32 or FDX_F64");
-    FDX_TRY(check_groups("fdx_weighted_gene_sums_csr_dev", Y->n, K, ldw, rows_dev, group_off, C));
-    hipStream_t st = (hipStream_t)stream;
-    PoolStream pool_stream(st);
-    return launch_weighted_gene_sums(nullptr, Y->dtype, Y->n, Y->G, 0, Y, W_dev, ldw, K, rows_dev, group_off, C, A_dev, B_dev, q_dev,
-                                     u_dev, st);
+    return weighted_gene_sums_entry("fdx_weighted_gene_sums_csr_dev", GeneMatrix(Y), W_dev, ldw, K, rows_dev, group_off, C, A_dev, B_dev,
+                                    q_dev, u_dev, stream);
 }
 
 int fdx_nnls_gram_dev(const double* A_dev, const double* B_dev, const double* q_dev, int32_t C, int32_t K, int32_t G, double ridge,

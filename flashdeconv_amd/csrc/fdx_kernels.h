@@ -149,8 +149,7 @@ SpatialStatsPlan spatial_stats_plan(long long n, int K);
 int launch_spatial_stats(const SpatialStatsPlan& s, const double* V, long long ldv, int K, const GraphTables& g, double* scratch,
                          int batch, double* out, double* nbr_mean, double* m4, hipStream_t st);
 
-// What correlogram_kernels.cpp takes from the kernels of spatial_stats_kernels.cpp.
-size_t spatial_scratch_budget_bytes();       // the permutation batches' scratch budget (1 GiB)
+// What correlogram_kernels.cpp takes from the kernels of spatial_stats_kernels.cpp (and SCRATCH_BUDGET_BYTES of gene_pass.h).
 // column sums -> mean, centre -> Z (K, s.ld) in the order `perm` gives (null: the caller's) and m2, m4 (null: not computed) from Z;
 // part: s.partials_doubles doubles.  mean, m2, m4 on the device.
 int launch_spatial_moments(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* perm, double* Z,
@@ -174,26 +173,6 @@ struct CorrelogramPlan {
     size_t scratch_doubles;      // [Z K planes | lag bands_per_pass * K planes | partials]
 };
 CorrelogramPlan correlogram_plan(long long n, int K, int B, int max_bands_per_pass);
-
-// ---- expression_kernels.cpp
-// Weighted gene sums (fdx_weighted_gene_sums_dev / _csr_dev): the rows of a group, in the order of the sorted row list, are cut into
-// segments of FDX_EXPRESSION_SEGMENT_ROWS; a segment is summed row after row and the segment sums are folded in ascending order.
-constexpr int EXPR_KC = 32, EXPR_KC_TAIL = 16;   // accumulators a thread of the dense kernel keeps: full chunks, and a last chunk of <= 16
-constexpr int EXPR_CSR_KC = 8;                   // types a workgroup of the CSR kernel adds per pass over its rows
-constexpr int EXPR_NNLS_LDS_MAX_K = 88;          // the solve keeps A_c in LDS up to here (88 * 88 doubles < 64 KB), reads it through L2 above
-// Y dense (csr null) or CSR; group_off on the HOST (fdx.h).  Everything queued on st; scratch from the pool.
-int launch_weighted_gene_sums(const void* Y, int dtype, long long n, int G, long long ldy, const fdx_csr_view* csr, const double* W,
-                              long long ldw, int K, const int* rows, const int* group_off, int C, double* A, double* B, double* q,
-                              double* u, hipStream_t st);
-int launch_nnls_gram(const double* A, const double* B, const double* q, int C, int K, int G, double ridge, int max_iter, double tol,
-                     double* S, int* n_iter, int* converged, double* rss, hipStream_t st);
-
-// ---- gene_spatial_kernels.cpp
-// The nine per-gene planes of fdx_gene_spatial_sums_dev / _csr_dev (fdx.h) over a whole graph of t.n >= 1 spots: Y dense (csr null)
-// or CSR; sums (9, G), deg_out (t.n, may be null) and counts = {sum deg, sum deg^2} on the device.  Everything queued on st; the
-// segment sums live in the pool.
-int launch_gene_spatial_sums(const GraphTables& t, const void* Y, int dtype, int G, long long ldy, const fdx_csr_view* csr,
-                             double* sums, int* deg_out, long long* counts, hipStream_t st);
 
 // ---- bcd_kernels.cpp
 int launch_bcd_sweep(const BcdSweepArgs& a, double* generic_scratch, size_t scratch_ld, hipStream_t st);

@@ -8,9 +8,9 @@
 //
 // Order of the sums.  The graph's positions 0 .. n - 1 (position p holds the caller's spot perm[p]) are cut into SEGMENTS of
 // FDX_GENE_SPATIAL_SEGMENT_POSITIONS positions; a segment is summed position after position into zeroed accumulators, its sums go
-// to a scratch block, and gs_fold_kernel adds the segment sums in ascending order.  That order is a function of the graph alone:
-// how many segments a workgroup takes (its stripe, FDX_EXPR_STRIPE_SEGMENTS) and how many segments are in flight at once (the
-// scratch budget: the fold continues from the sums of the batch before) change no bit.  No floating-point atomics.
+// to a scratch block, and the fold adds the segment sums in ascending order (planes 7 and 8: keeps the smaller / larger).  That
+// order is a function of the graph alone; gene_pass.h has the rule for what changes no bit of it (stripe, batches of segments)
+// and the fold.
 //
 // A workgroup first stages its segment's index tables in LDS, one thread per position: the caller's row, the degree and the caller's
 // rows of the first GS_NB neighbours (the chain perm[p], deg[p], slice_off, ell, perm[j] is walked by 256 threads at once, not
@@ -25,14 +25,13 @@
 //          tenth plane counts the stored entries of a column: with fewer than n of them the implicit 0 takes part in min / max.
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <limits>
 #include <vector>
 
-#include "fdx_env.h"
 #include "fdx_graph.h"
 #include "fdx_internal.h"
 #include "fdx_kernels.h"
+#include "gene_pass.h"
 
 namespace fdx {
 namespace {
@@ -42,7 +41,6 @@ constexpr int GS_NB = 8;                                     // neighbours of a 
 constexpr int GS_GENES = 512;                                // genes of a dense workgroup, two per thread
 constexpr int GS_PLANES = 9, GS_CSR_PLANES = 10;             // CSR: plane 9 counts the stored entries
 constexpr int GS_MIN = 7, GS_MAX = 8;
-constexpr size_t GS_PART_BUDGET_BYTES = (size_t)1 << 30;
 static_assert(GS_SEG == 256, "a segment is staged by one workgroup of 256 threads");
 
 struct GsSegmentTables {
@@ -256,29 +254,6 @@ __global__ __launch_bounds__(256) void gs_csr_kernel(const long long* __restrict
     }
 }
 
-// out[plane][j] = the batch's nb segment values of (plane, j) folded in ascending order - added, or for the planes GS_MIN / GS_MAX
-// the smaller / larger kept - starting from nothing (first) or from what the batches before left in out.
-__global__ __launch_bounds__(256) void gs_fold_kernel(const double* __restrict__ part, int nb, int planes, int G, int first,
-                                                      double* __restrict__ out) {
-    const int j = blockIdx.x * 256 + threadIdx.x, plane = blockIdx.y;
-    if (j >= G) return;
-    const double* in = part + (size_t)plane * G + j;
-    const size_t seg_stride = (size_t)planes * G;
-    double* o = out + (size_t)plane * G + j;
-    double acc = first ? (plane == GS_MIN ? INFINITY : plane == GS_MAX ? -INFINITY : 0.0) : *o;
-    auto take = [&](double v) { acc = plane == GS_MIN ? fmin(acc, v) : plane == GS_MAX ? fmax(acc, v) : acc + v; };
-    int s = 0;
-    for (; s + 8 <= nb; s += 8) {                   // eight loads in flight, folded in ascending order
-        double v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = in[(size_t)(s + i) * seg_stride];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) take(v[i]);
-    }
-    for (; s < nb; ++s) take(in[(size_t)s * seg_stride]);
-    *o = acc;
-}
-
 // CSR: the nine planes from the ten folded ones; a column that stores fewer than n entries holds an implicit 0
 __global__ __launch_bounds__(256) void gs_csr_finish_kernel(const double* __restrict__ folded, int G, double n,
                                                             double* __restrict__ sums) {
@@ -315,94 +290,71 @@ __global__ __launch_bounds__(256) void gs_counts_kernel(const long long* __restr
     if (threadIdx.x < 2) counts[threadIdx.x] = red[threadIdx.x][0];
 }
 
-int stripe_segments() {                            // the knob of the weighted gene sums: segments per workgroup
-    const char* v = env("FDX_EXPR_STRIPE_SEGMENTS");
-    const int s = v ? atoi(v) : 1;
-    return s >= 1 ? s : 1;
-}
-
 template <typename T>
-void launch_dense(const T* Y, long long ldy, const GraphTables& t, int sb0, int nb, int stripe, int G, double* part, int* deg_out,
-                  long long* deg_part, hipStream_t st) {
-    hipLaunchKernelGGL(gs_dense_kernel<T>, dim3((unsigned)ceil_div(nb, stripe), (unsigned)ceil_div(G, GS_GENES)), dim3(256), 0, st, Y,
-                       ldy, t, sb0, nb, stripe, G, part, deg_out, deg_part);
-}
-
-template <typename T>
-void launch_csr(const fdx_csr_view* Y, const GraphTables& t, int sb0, int nb, int stripe, double* part, int* deg_out,
+void launch_csr(const fdx_csr_view* Y, const T* values, const GraphTables& t, int sb0, int nb, int stripe, double* part, int* deg_out,
                 long long* deg_part, hipStream_t st) {
-    const dim3 grid((unsigned)ceil_div(nb, stripe));
-    if (Y->sorted_rows)
-        hipLaunchKernelGGL((gs_csr_kernel<T, true>), grid, dim3(256), 0, st, (const long long*)Y->indptr, Y->indices,
-                           (const T*)Y->data, t, sb0, nb, stripe, Y->G, part, deg_out, deg_part);
-    else
-        hipLaunchKernelGGL((gs_csr_kernel<T, false>), grid, dim3(256), 0, st, (const long long*)Y->indptr, Y->indices,
-                           (const T*)Y->data, t, sb0, nb, stripe, Y->G, part, deg_out, deg_part);
+    auto* kernel = Y->sorted_rows ? gs_csr_kernel<T, true> : gs_csr_kernel<T, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)ceil_div(nb, stripe)), dim3(256), 0, st, (const long long*)Y->indptr, Y->indices, values, t,
+                       sb0, nb, stripe, Y->G, part, deg_out, deg_part);
 }
 
-}  // namespace
-
-// Everything queued on st: the nine planes to sums (device), deg_out (device, may be null), {sum deg, sum deg^2} to counts (device).
-int launch_gene_spatial_sums(const GraphTables& t, const void* Y, int dtype, int G, long long ldy, const fdx_csr_view* csr,
-                             double* sums, int* deg_out, long long* counts, hipStream_t st) {
-    const int n_seg = ceil_div(t.n, GS_SEG);
-    const int planes = csr ? GS_CSR_PLANES : GS_PLANES;
+// The nine planes of fdx.h over a whole graph of t.n >= 1 spots.  Everything queued on st: the planes to sums (device), deg_out
+// (device, may be null), {sum deg, sum deg^2} to counts (device); the segment sums live in the pool.
+int launch_gene_spatial_sums(const GraphTables& t, const GeneMatrix& y, double* sums, int* deg_out, long long* counts, hipStream_t st) {
+    const int n_seg = ceil_div(t.n, GS_SEG), G = y.G;
+    const int planes = y.sparse ? GS_CSR_PLANES : GS_PLANES;
     const int stripe = stripe_segments();
     const size_t seg_bytes = (size_t)planes * G * sizeof(double);
-    const int batch = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_seg, GS_PART_BUDGET_BYTES / seg_bytes));
-    DevBuf part, deg_part, folded;
-    FDX_TRY(part.alloc((size_t)batch * seg_bytes));
-    FDX_TRY(deg_part.alloc((size_t)n_seg * 2 * sizeof(long long)));
-    if (csr) FDX_TRY(folded.alloc(seg_bytes));
-    double* fold_out = csr ? folded.as<double>() : sums;
-    for (int sb0 = 0; sb0 < n_seg; sb0 += batch) {
-        const int nb = std::min(batch, n_seg - sb0);
-        if (csr) {
-            if (csr->dtype == FDX_F32) launch_csr<float>(csr, t, sb0, nb, stripe, part.as<double>(), deg_out, deg_part.as<long long>(), st);
-            else launch_csr<double>(csr, t, sb0, nb, stripe, part.as<double>(), deg_out, deg_part.as<long long>(), st);
-        } else if (dtype == FDX_F32) {
-            launch_dense<float>((const float*)Y, ldy, t, sb0, nb, stripe, G, part.as<double>(), deg_out, deg_part.as<long long>(), st);
-        } else {
-            launch_dense<double>((const double*)Y, ldy, t, sb0, nb, stripe, G, part.as<double>(), deg_out, deg_part.as<long long>(), st);
-        }
+    DevBuf deg_buf, folded;
+    FDX_TRY(deg_buf.alloc((size_t)n_seg * 2 * sizeof(long long)));
+    if (y.sparse) FDX_TRY(folded.alloc(seg_bytes));
+    long long* deg_part = deg_buf.as<long long>();
+    double* fold_out = y.sparse ? folded.as<double>() : sums;
+    FDX_TRY(for_segment_batches(n_seg, seg_bytes, [&](int sb0, int nb, double* part) {
+        dispatch_gene_matrix(
+            y, [&](auto* Yd) {
+                hipLaunchKernelGGL(gs_dense_kernel, dim3((unsigned)ceil_div(nb, stripe), (unsigned)ceil_div(G, GS_GENES)), dim3(256), 0,
+                                   st, Yd, y.ldy, t, sb0, nb, stripe, G, part, deg_out, deg_part);
+                return 0;
+            },
+            [&](auto* values) { return launch_csr(y.csr, values, t, sb0, nb, stripe, part, deg_out, deg_part, st), 0; });
         FDX_CHECK_LAUNCH();
-        hipLaunchKernelGGL(gs_fold_kernel, dim3((unsigned)ceil_div(G, 256), (unsigned)planes), dim3(256), 0, st, part.as<double>(), nb,
-                           planes, G, sb0 == 0 ? 1 : 0, fold_out);
-        FDX_CHECK_LAUNCH();
-    }
-    if (csr) {
-        hipLaunchKernelGGL(gs_csr_finish_kernel, dim3((unsigned)ceil_div(G, 256)), dim3(256), 0, st, folded.as<double>(), G,
-                           (double)t.n, sums);
+        const SegmentBlocks b{part, (long long)planes * G, (long long)G, 1LL, sb0, nb};
+        return launch_gene_fold(b, 0, planes, G, nullptr, 1, fold_out, 0, (long long)G, GS_MIN, GS_MAX, st);
+    }));
+    if (y.sparse) {
+        hipLaunchKernelGGL(gs_csr_finish_kernel, dim3((unsigned)ceil_div(G, 256)), dim3(256), 0, st, fold_out, G, (double)t.n, sums);
         FDX_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(gs_counts_kernel, dim3(1), dim3(256), 0, st, deg_part.as<long long>(), n_seg, counts);
+    hipLaunchKernelGGL(gs_counts_kernel, dim3(1), dim3(256), 0, st, deg_part, n_seg, counts);
     FDX_CHECK_LAUNCH();
     return 0;
 }
 
-static int gene_spatial_entry(const char* who, const fdx_graph* g, const void* Y, int dtype, long long n, int G, long long ldy,
-                       const fdx_csr_view* csr, double* sums_dev, int* deg_dev, int64_t* counts_out, hipStream_t st) {
+int gene_spatial_entry(const char* who, const fdx_graph* g, const GeneMatrix& y, double* sums_dev, int* deg_dev, int64_t* counts_out,
+                       void* stream) {
     const std::string w(who);
-    FDX_REQUIRE(dtype == FDX_F32 || dtype == FDX_F64, w + ": dtype must be FDX_F32 or FDX_F64");
-    FDX_REQUIRE(G >= 1, w + ": G must be at least 1");
-    FDX_REQUIRE(G <= GS_GENES * 65535, w + ": too many genes for one call");
-    FDX_REQUIRE(n >= 0 && n < (1LL << 31) - 128, w + ": n must be between 0 and 2^31 - 129");
+    hipStream_t st = (hipStream_t)stream;
+    FDX_TRY(check_gene_matrix(who, y, g && sums_dev && counts_out, false, "ldy < G"));
+    FDX_REQUIRE(y.G >= 1, w + ": G must be at least 1");
+    FDX_REQUIRE(y.G <= GS_GENES * 65535, w + ": too many genes for one call");
+    FDX_REQUIRE(y.n >= 0 && y.n < (1LL << 31) - 128, w + ": n must be between 0 and 2^31 - 129");
     GraphTables t;
     FDX_TRY(whole_graph_tables(g, who, &t));
-    FDX_REQUIRE(n == t.n, w + ": Y has " + std::to_string(n) + " rows but the graph has " + std::to_string(t.n) + " spots");
+    FDX_REQUIRE(y.n == t.n, w + ": Y has " + std::to_string(y.n) + " rows but the graph has " + std::to_string(t.n) + " spots");
     PoolStream pool_stream(st);
     counts_out[0] = t.n;
     counts_out[1] = counts_out[2] = 0;
     if (t.n == 0) {                                 // empty sums; no value to be the smallest or the largest
-        std::vector<double> h((size_t)GS_PLANES * G, 0.0);
-        std::fill(h.begin() + (size_t)GS_MIN * G, h.end(), std::numeric_limits<double>::quiet_NaN());
+        std::vector<double> h((size_t)GS_PLANES * y.G, 0.0);
+        std::fill(h.begin() + (size_t)GS_MIN * y.G, h.end(), std::numeric_limits<double>::quiet_NaN());
         FDX_TRY(copy_h2d(sums_dev, h.data(), h.size() * sizeof(double), st));
         FDX_HIP(hipStreamSynchronize(st));
         return 0;
     }
     DevBuf counts;
     FDX_TRY(counts.alloc(2 * sizeof(long long)));
-    FDX_TRY(launch_gene_spatial_sums(t, Y, dtype, G, ldy, csr, sums_dev, deg_dev, counts.as<long long>(), st));
+    FDX_TRY(launch_gene_spatial_sums(t, y, sums_dev, deg_dev, counts.as<long long>(), st));
     long long host[2];
     FDX_TRY(copy_d2h(host, counts.p, sizeof(host), st));         // the call's one host synchronisation
     counts_out[1] = host[0];
@@ -410,6 +362,7 @@ static int gene_spatial_entry(const char* who, const fdx_graph* g, const void* Y
     return 0;
 }
 
+}  // namespace
 }  // namespace fdx
 
 using namespace fdx;
@@ -418,18 +371,12 @@ extern "C" {
 
 int fdx_gene_spatial_sums_dev(const fdx_graph* g, const void* Y_dev, int32_t dtype, int64_t n, int32_t G, int64_t ldy,
                               double* sums_dev, int32_t* deg_dev, int64_t* counts_out, void* stream) {
-    FDX_REQUIRE(g && Y_dev && sums_dev && counts_out, "fdx_gene_spatial_sums_dev: null argument");
-    FDX_REQUIRE(ldy >= G, "fdx_gene_spatial_sums_dev: ldy < G");
-    return gene_spatial_entry("fdx_gene_spatial_sums_dev", g, Y_dev, dtype, n, G, ldy, nullptr, sums_dev, deg_dev, counts_out,
-                              (hipStream_t)stream);
+    return gene_spatial_entry("fdx_gene_spatial_sums_dev", g, GeneMatrix(Y_dev, dtype, n, G, ldy), sums_dev, deg_dev, counts_out, stream);
 }
 
 int fdx_gene_spatial_sums_csr_dev(const fdx_graph* g, const fdx_csr_view* Y, double* sums_dev, int32_t* deg_dev, int64_t* counts_out,
                                   void* stream) {
-    FDX_REQUIRE(g && Y && sums_dev && counts_out && Y->indptr, "fdx_gene_spatial_sums_csr_dev: null argument");
-    FDX_REQUIRE(Y->nnz == 0 || (Y->indices && Y->data), "fdx_gene_spatial_sums_csr_dev: bad view");
-    return gene_spatial_entry("fdx_gene_spatial_sums_csr_dev", g, nullptr, Y->dtype, Y->n, Y->G, 0, Y, sums_dev, deg_dev, counts_out,
-                              (hipStream_t)stream);
+    return gene_spatial_entry("fdx_gene_spatial_sums_csr_dev", g, GeneMatrix(Y), sums_dev, deg_dev, counts_out, stream);
 }
 
 }  // extern "C"

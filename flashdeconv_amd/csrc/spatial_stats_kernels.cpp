@@ -33,6 +33,7 @@
 #include "fdx_graph.h"
 #include "fdx_internal.h"
 #include "fdx_kernels.h"
+#include "gene_pass.h"
 #include "perm_device.h"
 
 #include <algorithm>
@@ -45,8 +46,7 @@ constexpr int SS_KT = 32;                // centre: types staged at a time
 constexpr int SS_KS = SS_KT + 1;         //         odd row stride of the [spot][type] tile (column reads hit 64 banks)
 constexpr int SS_CT = 32;                // cross: edge of a pair-space tile
 constexpr int SS_CP = 64;                //        positions staged at a time (one slice)
-constexpr size_t SS_PERM_SCRATCH_BYTES = (size_t)1 << 30;   // permutation batches: scratch budget that sizes B (one at the least)
-constexpr int SS_PERM_MAX_BATCH = 512;                      //                      and its cap (a grid dimension)
+constexpr int SS_PERM_MAX_BATCH = 512;   // permutation batches: SCRATCH_BUDGET_BYTES sizes B (one at the least), this caps it (a grid dimension)
 
 // same-wave LDS hand-off: a wave's ds operations execute in order; this keeps the compiler from moving them across
 __device__ __forceinline__ void wave_lds_handoff() {
@@ -368,8 +368,6 @@ static void launch_lag_for(const SpatialStatsPlan& s, int batch, long long batch
     else launch_lag<32>(s, batch, batch_stride, Z, g, mean, K, lag, nbr_mean, deg_part, st);
 }
 
-size_t spatial_scratch_budget_bytes() { return SS_PERM_SCRATCH_BYTES; }
-
 // the passes that do not look at the graph: mean, Z in the order of `perm`, m2 and (m4 != null) m4
 int launch_spatial_moments(const SpatialStatsPlan& s, const double* V, long long ldv, int n, int K, const int* perm, double* Z,
                            double* part, double* mean, double* m2, double* m4, hipStream_t st) {
@@ -466,7 +464,7 @@ static SpatialPermPlan spatial_perm_plan(long long n, int K, long long n_perm, i
     p.cross_part_doubles = (size_t)p.s.cross_blocks * KK;
     // per permutation in flight: its Z and lag planes, its cross partials and, where the caller keeps no null, its C_r
     const size_t per_perm = (2 * p.plane_doubles + p.cross_part_doubles + KK) * sizeof(double);
-    long long B = (long long)std::max<size_t>(1, SS_PERM_SCRATCH_BYTES / per_perm);
+    long long B = (long long)std::max<size_t>(1, SCRATCH_BUDGET_BYTES / per_perm);
     B = std::min<long long>(B, SS_PERM_MAX_BATCH);
     if (max_batch > 0) B = std::min<long long>(B, max_batch);
     B = std::max<long long>(1, std::min<long long>(B, std::max<long long>(1, n_perm)));

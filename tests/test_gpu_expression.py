@@ -151,6 +151,40 @@ def test_two_calls_and_another_stripe_count_return_the_same_bits(route, monkeypa
             assert np.array_equal(first[key], other[key]), (stripe, key)
 
 
+@pytest.mark.parametrize("route", ["dev_f32", "csr_scipy"])
+def test_sums_continue_across_a_scratch_batch(route, monkeypatch):
+    """More segments than the scratch holds at once (include/fdx.h: about 1 GiB of segment sums, of round_up(K, 16) + 2 planes of
+    G float64 per segment): a group whose third segment is the first of the second batch continues from what the first batch
+    left, the groups after it start afresh there, and another stripe count returns the same bits.  A segment never crosses a
+    group, so 1790 one-row groups make 1790 segments.  Exact data: every sum must EQUAL the reference.  The budget is no switch,
+    so this cannot compare with a one-batch run of the same data: that the bits do not depend on the batch follows from the
+    fold's fixed ascending order; what is shown here is that no batch is dropped, doubled or started from the wrong value."""
+    from flashdeconv_amd.utils.expression import weighted_gene_sums
+    K, G = 130, 513
+    batch = (1 << 30) // (((K + 15) // 16 * 16 + 2) * G * 8)
+    sizes = [1] * 1790 + [2 * SEG + 100, 5, 0, SEG + 1]
+    first_seg = np.concatenate([[0], np.cumsum([-(-s // SEG) for s in sizes])])
+    long_group = 1790
+    assert batch == 1792 and first_seg[-1] > batch
+    assert first_seg[long_group] < batch <= first_seg[long_group + 1] - 1
+    rs = np.random.RandomState(11)
+    g = rs.permutation(np.concatenate([np.repeat(np.arange(len(sizes)), sizes), np.full(7, -1)])).astype(np.int64)
+    n, C = g.size, len(sizes)
+    W = er.dyadic_weights(n, K, 11)
+    Y = er.integer_counts(n, G, 11, density=0.3 if route.startswith("csr") else 1.0, dtype=np.float64)
+    want = dict(zip(("A", "B", "q", "u", "n_rows"), er.sums(Y, W, g, C)))
+    Yc = _route_Y(Y, route)
+    first = weighted_gene_sums(Yc, W, groups=g, n_groups=C)
+    for key in want:
+        have = np.asarray(first[key])
+        assert have.shape == want[key].shape, (key, have.shape)
+        assert np.array_equal(have, want[key]), (key, float(np.abs(have - want[key]).max()))
+    monkeypatch.setenv("FDX_EXPR_STRIPE_SEGMENTS", "5")
+    other = weighted_gene_sums(Yc, W, groups=g, n_groups=C)
+    for key in want:
+        assert np.array_equal(np.asarray(first[key]), np.asarray(other[key])), key
+
+
 # ---------------------------------------------------------------- the solve, exact
 @pytest.mark.parametrize("K", [1, 5, 64, 65, 130])
 def test_one_hot_weights_solve_exactly_in_two_sweeps(K):
