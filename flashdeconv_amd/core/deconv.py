@@ -748,6 +748,18 @@ class FlashDeconv:
         from ..utils.spatial_genes import spatially_variable_genes
         return spatially_variable_genes(Y, self, weights=W if residual else None, n_top=n_top, **kw)
 
+    def get_gene_pair_colocalisation(self, Y, pairs, local=False, n_top=None):
+        """Which pairs of genes - a ligand and its receptor - are expressed next to each other in this tissue, and where (additive,
+        not in the reference): the bivariate Moran's R of every pair of ``pairs`` ((P, 2) column indices of ``Y``) over the graph
+        the fit used, with Pearson's r, z scores under the exact permutation variance, p and q values and, with ``local=True``,
+        the per-spot score ``local`` (n_spots, P) - ``utils.gene_pairs.spatial_gene_pairs``.  ``Y``: ``n_spots_`` rows, dense or
+        CSR, ANY gene set, scored as it is passed.  ``n_top``: also ``top``, the first pairs of ``order``.  After
+        ``fit(output="torch")`` ``local`` stays a CUDA tensor."""
+        self._weights_for(Y, "proportions", None)              # fitted, and Y has the fit's spots as rows
+        from ..utils.gene_pairs import spatial_gene_pairs
+        return spatial_gene_pairs(Y, self, pairs, local=local, n_top=n_top,
+                                  output="torch" if _lib.is_cuda_tensor(self.proportions_) else "numpy")
+
     def get_dominant_cell_type(self):
         self._require_fitted()
         if hasattr(self.proportions_, "argmax") and not isinstance(self.proportions_, np.ndarray):

@@ -14,8 +14,8 @@
 //
 // A workgroup first stages its segment's index tables in LDS, one thread per position: the caller's row, the degree and the caller's
 // rows of the first GS_NB neighbours (the chain perm[p], deg[p], slice_off, ell, perm[j] is walked by 256 threads at once, not
-// once per row).  Walking in the graph's order keeps the neighbours' rows close for device-built (Morton-ordered) graphs: the
-// 1 + deg reads of a row are then served by L2 / Infinity Cache.
+// once per row; gene_walk.h, shared with the gene-pair sums).  Walking in the graph's order keeps the neighbours' rows close for
+// device-built (Morton-ordered) graphs: the 1 + deg reads of a row are then served by L2 / Infinity Cache.
 //   dense  a thread owns two gene columns (j, j + 256: rows are read coalesced), a workgroup 512; row and neighbour indices are
 //          read from LDS by broadcast; the 1 + GS_NB loads of the next position are issued before this position's are consumed.
 //          Neighbours past GS_NB (a hub) are read from the ELL, eight loads at a time.
@@ -32,65 +32,14 @@
 #include "fdx_internal.h"
 #include "fdx_kernels.h"
 #include "gene_pass.h"
+#include "gene_walk.h"
 
 namespace fdx {
 namespace {
 
-constexpr int GS_SEG = FDX_GENE_SPATIAL_SEGMENT_POSITIONS;   // = the workgroup: one thread stages one position
-constexpr int GS_NB = 8;                                     // neighbours of a position staged in LDS / loaded ahead
 constexpr int GS_GENES = 512;                                // genes of a dense workgroup, two per thread
 constexpr int GS_PLANES = 9, GS_CSR_PLANES = 10;             // CSR: plane 9 counts the stored entries
 constexpr int GS_MIN = 7, GS_MAX = 8;
-static_assert(GS_SEG == 256, "a segment is staged by one workgroup of 256 threads");
-
-struct GsSegmentTables {
-    int row[GS_SEG];                 // the caller's row of position p0 + r, -1 past the segment's end
-    int deg[GS_SEG];
-    int nbr[GS_NB * GS_SEG];         // [m][r]: the caller's row of neighbour m, -1 where there is none
-};
-
-// The caller's row of entry m of position p's neighbour list (m < deg[p]); -1 for an index outside the graph.
-__device__ __forceinline__ int gs_neighbour_row(const GraphTables& g, int w0, int p, int m) {
-    const int j = g.ell[((size_t)w0 + m) * 64 + (p & 63)];
-    if (j < 0 || j >= g.n) return -1;
-    return g.perm ? g.perm[j] : j;
-}
-
-// Stages positions [p0, p1) (at most GS_SEG) and, in the workgroups told to (`owner`), writes deg_out in the caller's order and
-// the segment's {sum deg, sum deg^2}.  Barriers: one on entry (the previous segment's readers), one on exit.
-__device__ __forceinline__ void gs_stage_segment(const GraphTables& g, int p0, int p1, GsSegmentTables& sh, long long (*red)[4],
-                                                 bool owner, int* __restrict__ deg_out, long long* __restrict__ deg_part_seg) {
-    __syncthreads();
-    const int t = threadIdx.x, p = p0 + t;
-    int row = -1, dg = 0;
-    if (p < p1) {
-        row = g.perm ? g.perm[p] : p;
-        const int w0 = g.slice_off[p >> 6];
-        dg = min(g.deg[p], g.slice_off[(p >> 6) + 1] - w0);      // (never more entries than the slice is wide)
-#pragma unroll
-        for (int m = 0; m < GS_NB; ++m) sh.nbr[m * GS_SEG + t] = m < dg ? gs_neighbour_row(g, w0, p, m) : -1;
-        if (owner && deg_out) deg_out[row] = dg;
-    } else {
-#pragma unroll
-        for (int m = 0; m < GS_NB; ++m) sh.nbr[m * GS_SEG + t] = -1;
-    }
-    sh.row[t] = row;
-    sh.deg[t] = dg;
-    if (owner) {
-        long long sd = dg, sd2 = (long long)dg * dg;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            sd += __shfl_xor(sd, off, 64);
-            sd2 += __shfl_xor(sd2, off, 64);
-        }
-        if ((t & 63) == 0) {
-            red[0][t >> 6] = sd;
-            red[1][t >> 6] = sd2;
-        }
-    }
-    __syncthreads();
-    if (owner && t < 2) deg_part_seg[t] = red[t][0] + red[t][1] + red[t][2] + red[t][3];
-}
 
 // part[s][plane][j] for the segments seg0 + s, s < n_seg, of this launch; workgroup x takes segments [x * stripe, (x + 1) * stripe),
 // workgroup row y the genes [512 y, 512 y + 512).
@@ -113,47 +62,8 @@ __global__ __launch_bounds__(256) void gs_dense_kernel(const T* __restrict__ Y, 
         double u0 = 0.0, q0 = 0.0, t0 = 0.0, f0 = 0.0, D0 = 0.0, H0 = 0.0, P0 = 0.0;
         double u1 = 0.0, q1 = 0.0, t1 = 0.0, f1 = 0.0, D1 = 0.0, H1 = 0.0, P1 = 0.0;
         double mn0 = INFINITY, mx0 = -INFINITY, mn1 = INFINITY, mx1 = -INFINITY;
-        T ca[1 + GS_NB], cb[1 + GS_NB], na[1 + GS_NB], nb[1 + GS_NB];   // [0]: the row itself, [1 + m]: neighbour m (0 where none)
-        auto load = [&](int r, T (&a)[1 + GS_NB], T (&b)[1 + GS_NB]) {
-            const long long row = sh.row[r];
-            a[0] = y0p[row * ldy];
-            b[0] = y1p[row * ldy];
-#pragma unroll
-            for (int m = 0; m < GS_NB; ++m) {
-                const long long nr = sh.nbr[m * GS_SEG + r];
-                a[1 + m] = nr >= 0 ? y0p[nr * ldy] : (T)0;
-                b[1 + m] = nr >= 0 ? y1p[nr * ldy] : (T)0;
-            }
-        };
-        load(0, ca, cb);
-        for (int r = 0; r < cnt; ++r) {
-            if (r + 1 < cnt) load(r + 1, na, nb);
-            const int dg = sh.deg[r];
-            double lag0 = 0.0, lag1 = 0.0;
-#pragma unroll
-            for (int m = 0; m < GS_NB; ++m) {                    // (x + 0 = x: the slots past the degree change nothing)
-                lag0 += (double)ca[1 + m];
-                lag1 += (double)cb[1 + m];
-            }
-            if (dg > GS_NB) {                                    // a hub: the rest of its list from the ELL, eight loads at a time
-                const int p = p0 + r, w0 = g.slice_off[p >> 6];
-                for (int m0 = GS_NB; m0 < dg; m0 += 8) {
-                    T ea[8], eb[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const long long nr = m0 + i < dg ? gs_neighbour_row(g, w0, p, m0 + i) : -1;
-                        ea[i] = nr >= 0 ? y0p[nr * ldy] : (T)0;
-                        eb[i] = nr >= 0 ? y1p[nr * ldy] : (T)0;
-                    }
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        lag0 += (double)ea[i];
-                        lag1 += (double)eb[i];
-                    }
-                }
-            }
+        gs_walk_segment(y0p, y1p, ldy, g, p0, cnt, sh, [&](int, int dg, double ya, double yb, double lag0, double lag1) {
             const double d = (double)dg;
-            const double ya = (double)ca[0], yb = (double)cb[0];
             const double ya2 = ya * ya, yb2 = yb * yb;
             u0 += ya;                 u1 += yb;
             q0 += ya2;                q1 += yb2;
@@ -164,12 +74,7 @@ __global__ __launch_bounds__(256) void gs_dense_kernel(const T* __restrict__ Y, 
             P0 += ya * lag0;          P1 += yb * lag1;
             mn0 = fmin(mn0, ya);      mn1 = fmin(mn1, yb);
             mx0 = fmax(mx0, ya);      mx1 = fmax(mx1, yb);
-#pragma unroll
-            for (int i = 0; i < 1 + GS_NB; ++i) {
-                ca[i] = na[i];
-                cb[i] = nb[i];
-            }
-        }
+        });
         double* out = part + (size_t)s * GS_PLANES * G;
         if (ok0) {
             const double v[GS_PLANES] = {u0, q0, t0, f0, D0, H0, P0, mn0, mx0};
@@ -326,9 +231,7 @@ int launch_gene_spatial_sums(const GraphTables& t, const GeneMatrix& y, double* 
         hipLaunchKernelGGL(gs_csr_finish_kernel, dim3((unsigned)ceil_div(G, 256)), dim3(256), 0, st, fold_out, G, (double)t.n, sums);
         FDX_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(gs_counts_kernel, dim3(1), dim3(256), 0, st, deg_part, n_seg, counts);
-    FDX_CHECK_LAUNCH();
-    return 0;
+    return launch_segment_degree_counts(deg_part, n_seg, counts, st);
 }
 
 int gene_spatial_entry(const char* who, const fdx_graph* g, const GeneMatrix& y, double* sums_dev, int* deg_dev, int64_t* counts_out,
@@ -363,6 +266,13 @@ int gene_spatial_entry(const char* who, const fdx_graph* g, const GeneMatrix& y,
 }
 
 }  // namespace
+
+int launch_segment_degree_counts(const long long* deg_part, int n_seg, long long* counts, hipStream_t st) {
+    hipLaunchKernelGGL(gs_counts_kernel, dim3(1), dim3(256), 0, st, deg_part, n_seg, counts);
+    FDX_CHECK_LAUNCH();
+    return 0;
+}
+
 }  // namespace fdx
 
 using namespace fdx;

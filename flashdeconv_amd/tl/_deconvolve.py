@@ -7,7 +7,7 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
                n_hvg=2000, n_markers_per_type=50, spatial_method="knn", k_neighbors=6, radius=None, preprocess="log_cpm",
                layer_st=None, layer_ref=None, spatial_key="spatial", key_added="flashdeconv", random_state=0, copy=False,
                spot_diagnostics=False, spatial_stats=False, n_niches=None, spatial_permutations=0, local_stats=False,
-               correlogram=False, celltype_expression=False, spatial_genes=False):
+               correlogram=False, celltype_expression=False, spatial_genes=False, gene_pairs=None):
     """Writes ``.obsm[key_added]`` (proportions DataFrame), ``.obs[key_added + '_dominant']`` and
     ``.uns[key_added + '_params']``; returns the modified copy when ``copy=True``, else ``None``.  ``spot_diagnostics=True``
     (additive) also writes ``.obs[key_added + '_residual']`` (relative sketch residual per spot) and
@@ -37,7 +37,12 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
     Moran's ``I`` and Geary's ``C`` of each gene of the spot matrix over the fit's graph, the ``z_score`` under normality, the
     one-sided ``p_value`` under randomisation and its Benjamini-Hochberg ``q_value``, and - regressed on the proportions scaled by
     each spot's row sum over the mean row sum - ``residual_I``, ``residual_z_score`` of what the composition leaves and the
-    ``r2`` it explains, ``FlashDeconv.get_spatially_variable_genes``)."""
+    ``r2`` it explains, ``FlashDeconv.get_spatially_variable_genes``).
+    ``gene_pairs`` (additive): a non-empty sequence of ``(name_a, name_b)`` - a ligand and its receptor - of ``var_names`` common
+    to both objects (an unknown name is a ``ValueError`` before the fit) also writes ``.uns[key_added + '_gene_pairs']``, a
+    DataFrame with one row per pair in the caller's order and the columns ``gene_a``, ``gene_b``, ``R`` (the bivariate Moran's R
+    of the two genes of the spot matrix over the fit's graph), ``pearson``, ``z_score`` (under the exact permutation variance),
+    the one-sided ``p_value`` and its Benjamini-Hochberg ``q_value`` (``FlashDeconv.get_gene_pair_colocalisation``)."""
     from ..core.deconv import FlashDeconv
     from ..io import prepare_data, result_to_anndata
     from ..utils.correlogram import correlogram_request
@@ -46,6 +51,10 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
         raise ValueError(f"celltype_expression must be True or False, got {celltype_expression!r}")
     if not isinstance(spatial_genes, (bool, np.bool_)):
         raise ValueError(f"spatial_genes must be True or False, got {spatial_genes!r}")
+    if gene_pairs is not None:
+        gene_pairs = [tuple(pair) for pair in gene_pairs]
+        if not gene_pairs or any(len(pair) != 2 for pair in gene_pairs):
+            raise ValueError(f"gene_pairs must be a non-empty sequence of (name_a, name_b), got {gene_pairs!r}")
 
     adata = adata_st.copy() if copy else adata_st
     Y, X, coords, names, genes = prepare_data(adata, adata_ref, cell_type_key=cell_type_key, layer_st=layer_st,
@@ -56,6 +65,14 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
     if spatial_genes:
         from ..utils.spatial_genes import check_request as check_spatial_genes
         check_spatial_genes(tuple(Y.shape), len(names))
+    if gene_pairs is not None:
+        from ..utils.gene_pairs import check_request as check_gene_pairs
+        column = {str(name): j for j, name in enumerate(genes)}
+        for pair in gene_pairs:
+            for name in pair:
+                if str(name) not in column:
+                    raise ValueError(f"gene_pairs names the gene {name!r}, which is not among the genes common to both objects")
+        pair_idx = check_gene_pairs(tuple(Y.shape), np.array([[column[str(a)], column[str(b)]] for a, b in gene_pairs], dtype=np.int64))
     # like the reference, max_iter / tol / verbose are not exposed here (tl/_deconvolve.py:132-144)
     model = FlashDeconv(sketch_dim=sketch_dim, lambda_spatial=lambda_spatial, rho_sparsity=rho_sparsity, n_hvg=n_hvg,
                         n_markers_per_type=n_markers_per_type, spatial_method=spatial_method, k_neighbors=k_neighbors,
@@ -141,6 +158,13 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
              "residual_I": sv["residual_morans_i"], "residual_z_score": sv["residual_z_score"], "r2": sv["r2"]},
             index=[str(g) for g in genes])
         adata.uns[f"{key_added}_params"]["spatial_genes"] = True
+    if gene_pairs is not None:
+        import pandas as pd
+        gp = model.get_gene_pair_colocalisation(Y, pair_idx)
+        adata.uns[f"{key_added}_gene_pairs"] = pd.DataFrame(
+            {"gene_a": [str(a) for a, _ in gene_pairs], "gene_b": [str(b) for _, b in gene_pairs], "R": gp["morans_r"],
+             "pearson": gp["pearson_r"], "z_score": gp["z_score"], "p_value": gp["p_value"], "q_value": gp["q_value"]})
+        adata.uns[f"{key_added}_params"]["gene_pairs"] = len(gene_pairs)
     return adata if copy else None
 
 

@@ -753,6 +753,38 @@ int fdx_gene_spatial_sums_dev(const fdx_graph* g, const void* Y_dev, int32_t dty
                               double* sums_dev, int32_t* deg_dev, int64_t* counts_out, void* stream);
 int fdx_gene_spatial_sums_csr_dev(const fdx_graph* g, const fdx_csr_view* Y, double* sums_dev, int32_t* deg_dev, int64_t* counts_out,
                                   void* stream);
+/* ---- gene-pair spatial co-expression (additive, not in the reference; csrc/gene_pair_kernels.cpp) -------------------------------- *
+ * Per pair (a, b) of columns of Y (n, G) - Y, g, deg_i and counts_out as for fdx_gene_spatial_sums_dev; lag_g,i = sum_{j in N(i)} y_jg
+ * added in the graph's stored neighbour order - the sums from which the bivariate Moran's R, Pearson's r and the exact permutation
+ * variances of R are assembled.  pairs: P x 2 int32 on the HOST, row p = (a_p, b_p) with 0 <= a_p, b_p < G; a_p == b_p and
+ * repeated rows are legal.  sums_dev: (17, P) row-major float64 on the DEVICE, all arithmetic float64 on the value converted from its
+ * storage type:
+ *   0 ua = sum_i y_a     1 ub = sum_i y_b     2 qa = sum_i y_a*y_a     3 qb = sum_i y_b*y_b     4 Da = sum_i deg_i*y_a     5 Db = sum_i deg_i*y_b
+ *   6 S = sum_i y_a*y_b  7 Xab = sum_i y_a*lag_b                       8 Xba = sum_i y_b*lag_a
+ *   9 La = sum_i lag_a*lag_a     10 Lb = sum_i lag_b*lag_b     11 DLa = sum_i deg_i*lag_a     12 DLb = sum_i deg_i*lag_b
+ *   13 amin = min_i y_a     14 amax = max_i y_a     15 bmin = min_i y_b     16 bmax = max_i y_b
+ * A CSR entry that is not stored is the value 0, a stored zero a value like any other.  n = 0: zeros, NaN in planes 13-16.
+ * The order of every sum is that of fdx_gene_spatial_sums_dev (segments of FDX_GENE_SPATIAL_SEGMENT_POSITIONS positions, folded in
+ * ascending order; no floating-point atomics; the same bits from two calls, from another FDX_EXPR_STRIPE_SEGMENTS and from fewer
+ * segment sums in flight), and A PAIR'S SEVENTEEN NUMBERS DEPEND ONLY ON THE GRAPH AND ITS TWO COLUMNS: not on the other pairs of the
+ * call, their order, or - CSR - on how the call was cut.  The CSR entries gather the distinct genes of a chunk of consecutive pairs
+ * into a dense (n, S) matrix of the storage type in the library's pool and run the dense kernels on it; the chunks are cut so that
+ * n * S * sizeof(dtype) <= max_gather_bytes (0: about 1 GiB), one pair a chunk at the least.
+ * The local entries write, for every spot i (the CALLER's order) and pair p, to out_dev[i * ldo + p] (float64, DEVICE, ldo >= P)
+ *   coef_p * [ (y_a,i - mean_a_p) (lag_b,i - mean_b_p deg_i) + (y_b,i - mean_b_p) (lag_a,i - mean_a_p deg_i) ]
+ * from mean_a_dev, mean_b_dev, coef_dev (P float64 each, DEVICE); asynchronous on `stream`, no host synchronisation.
+ * Refused with a message: what fdx_gene_spatial_sums_dev refuses, P < 1 ("P must be at least 1"), an index outside [0, G) ("pair
+ * index out of range"), ldo < P. */
+int fdx_gene_pair_sums_dev(const fdx_graph* g, const void* Y_dev, int32_t dtype, int64_t n, int32_t G, int64_t ldy, const int32_t* pairs,
+                           int32_t P, double* sums_dev, int64_t* counts_out, void* stream);
+int fdx_gene_pair_sums_csr_dev(const fdx_graph* g, const fdx_csr_view* Y, const int32_t* pairs, int32_t P, int64_t max_gather_bytes,
+                               double* sums_dev, int64_t* counts_out, void* stream);
+int fdx_gene_pair_local_dev(const fdx_graph* g, const void* Y_dev, int32_t dtype, int64_t n, int32_t G, int64_t ldy, const int32_t* pairs,
+                            int32_t P, const double* mean_a_dev, const double* mean_b_dev, const double* coef_dev, double* out_dev,
+                            int64_t ldo, void* stream);
+int fdx_gene_pair_local_csr_dev(const fdx_graph* g, const fdx_csr_view* Y, const int32_t* pairs, int32_t P, int64_t max_gather_bytes,
+                                const double* mean_a_dev, const double* mean_b_dev, const double* coef_dev, double* out_dev, int64_t ldo,
+                                void* stream);
 /* beta (K, ld) type-major -> beta_out / prop_out (n, K) row-major in solver order of the own spots. */
 int fdx_normalize_dev(const double* beta_dev, int64_t ld, int64_t n, int32_t K, double* beta_out_dev, double* prop_out_dev,
                       void* stream);
