@@ -760,6 +760,16 @@ class FlashDeconv:
         return spatial_gene_pairs(Y, self, pairs, local=local, n_top=n_top,
                                   output="torch" if _lib.is_cuda_tensor(self.proportions_) else "numpy")
 
+    def get_spatial_gene_modules(self, Y, **kw):
+        """Which genes vary together over this tissue, and where (additive, not in the reference): the spatial co-expression matrix
+        of ``genes`` (None: the spatially variable genes of ``Y``, at most ``n_genes``) over the graph the fit used, the gene
+        modules cut from it and every module's score per spot - ``utils.gene_modules.spatial_gene_modules``, which takes the
+        keywords (``genes``, ``n_genes``, ``fdr``, ``n_modules``, ``min_module_size``, ``scores``).  ``Y``: ``n_spots_`` rows, dense
+        or CSR, ANY gene set, scored as it is passed.  After ``fit(output="torch")`` ``scores`` stays a CUDA tensor."""
+        self._weights_for(Y, "proportions", None)              # fitted, and Y has the fit's spots as rows
+        from ..utils.gene_modules import spatial_gene_modules
+        return spatial_gene_modules(Y, self, output="torch" if _lib.is_cuda_tensor(self.proportions_) else "numpy", **kw)
+
     def get_dominant_cell_type(self):
         self._require_fitted()
         if hasattr(self.proportions_, "argmax") and not isinstance(self.proportions_, np.ndarray):

@@ -7,7 +7,8 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
                n_hvg=2000, n_markers_per_type=50, spatial_method="knn", k_neighbors=6, radius=None, preprocess="log_cpm",
                layer_st=None, layer_ref=None, spatial_key="spatial", key_added="flashdeconv", random_state=0, copy=False,
                spot_diagnostics=False, spatial_stats=False, n_niches=None, spatial_permutations=0, local_stats=False,
-               correlogram=False, celltype_expression=False, spatial_genes=False, gene_pairs=None):
+               correlogram=False, celltype_expression=False, spatial_genes=False, gene_pairs=None,
+               gene_modules=False):
     """Writes ``.obsm[key_added]`` (proportions DataFrame), ``.obs[key_added + '_dominant']`` and
     ``.uns[key_added + '_params']``; returns the modified copy when ``copy=True``, else ``None``.  ``spot_diagnostics=True``
     (additive) also writes ``.obs[key_added + '_residual']`` (relative sketch residual per spot) and
@@ -42,7 +43,14 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
     to both objects (an unknown name is a ``ValueError`` before the fit) also writes ``.uns[key_added + '_gene_pairs']``, a
     DataFrame with one row per pair in the caller's order and the columns ``gene_a``, ``gene_b``, ``R`` (the bivariate Moran's R
     of the two genes of the spot matrix over the fit's graph), ``pearson``, ``z_score`` (under the exact permutation variance),
-    the one-sided ``p_value`` and its Benjamini-Hochberg ``q_value`` (``FlashDeconv.get_gene_pair_colocalisation``)."""
+    the one-sided ``p_value`` and its Benjamini-Hochberg ``q_value`` (``FlashDeconv.get_gene_pair_colocalisation``).
+    ``gene_modules`` (additive): ``True`` (the 500 most spatially variable of the common genes at most) or an int (that many)
+    groups the spatially variable genes of the spot matrix into modules - genes that vary together over the fit's graph,
+    ``FlashDeconv.get_spatial_gene_modules`` - and also writes ``.var[key_added + '_module']`` (the module of every gene, -1 for
+    one not selected or not assigned), ``.obsm[key_added + '_module_scores']`` (DataFrame, ``obs_names`` x module: the mean
+    standardised expression of the module's genes), ``.uns[key_added + '_gene_modules']`` (DataFrame with one row per module:
+    ``size``, ``mean_R`` - the mean bivariate Moran's R between its genes - and ``genes``, their names) and
+    ``.uns[key_added + '_params']['gene_modules']``; anything else is a ``ValueError`` before the fit."""
     from ..core.deconv import FlashDeconv
     from ..io import prepare_data, result_to_anndata
     from ..utils.correlogram import correlogram_request
@@ -51,6 +59,13 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
         raise ValueError(f"celltype_expression must be True or False, got {celltype_expression!r}")
     if not isinstance(spatial_genes, (bool, np.bool_)):
         raise ValueError(f"spatial_genes must be True or False, got {spatial_genes!r}")
+    if not isinstance(gene_modules, (bool, np.bool_)):
+        from ..utils.gene_modules import check_selection
+        if not isinstance(gene_modules, (int, np.integer)):
+            raise ValueError(f"gene_modules must be True, False or the number of genes to group, got {gene_modules!r}")
+        module_genes = check_selection(gene_modules)
+    else:
+        module_genes = 500 if gene_modules else None
     if gene_pairs is not None:
         gene_pairs = [tuple(pair) for pair in gene_pairs]
         if not gene_pairs or any(len(pair) != 2 for pair in gene_pairs):
@@ -165,7 +180,32 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
             {"gene_a": [str(a) for a, _ in gene_pairs], "gene_b": [str(b) for _, b in gene_pairs], "R": gp["morans_r"],
              "pearson": gp["pearson_r"], "z_score": gp["z_score"], "p_value": gp["p_value"], "q_value": gp["q_value"]})
         adata.uns[f"{key_added}_params"]["gene_pairs"] = len(gene_pairs)
+    if module_genes is not None:
+        import pandas as pd
+        gm = model.get_spatial_gene_modules(Y, n_genes=module_genes)
+        gene_names = [str(g) for g in genes]
+        C, labels, R = gm["n_modules"], gm["labels"], gm["morans_r"]
+        first = {}                                                # a duplicated name: the first occurrence is the gene used
+        for i, name in enumerate(adata.var_names):
+            first.setdefault(str(name), i)
+        module_of = np.full(len(adata.var_names), -1, dtype=np.int64)
+        module_of[[first[gene_names[j]] for j in gm["genes"]]] = labels
+        adata.var[f"{key_added}_module"] = module_of
+        adata.obsm[f"{key_added}_module_scores"] = pd.DataFrame(np.asarray(_host(gm["scores"])), index=adata.obs_names,
+                                                                 columns=list(range(C)))
+        within = []
+        for c in range(C):
+            block = R[np.ix_(labels == c, labels == c)]
+            within.append(float(block[~np.eye(block.shape[0], dtype=bool)].mean()) if block.shape[0] > 1 else float("nan"))
+        adata.uns[f"{key_added}_gene_modules"] = pd.DataFrame(
+            {"size": gm["module_sizes"], "mean_R": within, "genes": [[gene_names[j] for j in members] for members in gm["modules"]]},
+            index=list(range(C)))
+        adata.uns[f"{key_added}_params"]["gene_modules"] = module_genes
     return adata if copy else None
+
+
+def _host(x):
+    return x.cpu().numpy() if hasattr(x, "cpu") else x
 
 
 def _library_scale(Y):

@@ -3,7 +3,8 @@
 ``spatial_autocorrelation`` / ``spatial_permutation_test`` (``utils.spatial_stats``), ``local_spatial_statistics`` (``utils.local_stats``), ``spatial_correlogram`` (``utils.correlogram``) and ``spatial_niches`` / ``kmeans`` / ``kmeans_plusplus`` (``utils.niches``) and
 ``celltype_expression`` / ``weighted_gene_sums`` / ``nnls_gram`` (``utils.expression``) and ``spatially_variable_genes`` /
 ``gene_spatial_sums`` / ``assemble_genes`` (``utils.spatial_genes``) and ``spatial_gene_pairs`` / ``gene_pair_sums`` /
-``assemble_pairs`` (``utils.gene_pairs``) are additive."""
+``assemble_pairs`` (``utils.gene_pairs``) and ``spatial_gene_modules`` / ``spatial_coexpression`` / ``gene_coexpression_sums`` /
+``assemble_coexpression`` (``utils.gene_modules``) are additive."""
 from .genes import select_hvg, select_markers, compute_leverage_scores  # noqa: F401
 from .graph import build_knn_graph, build_radius_graph, coords_to_adjacency  # noqa: F401
 from .random import check_random_state  # noqa: F401
@@ -15,10 +16,12 @@ from .niches import spatial_niches, kmeans, kmeans_plusplus  # noqa: F401
 from .expression import celltype_expression, weighted_gene_sums, nnls_gram  # noqa: F401
 from .spatial_genes import spatially_variable_genes, gene_spatial_sums, assemble_genes  # noqa: F401
 from .gene_pairs import spatial_gene_pairs, gene_pair_sums, assemble_pairs  # noqa: F401
+from .gene_modules import spatial_gene_modules, spatial_coexpression, gene_coexpression_sums, assemble_coexpression  # noqa: F401
 
 __all__ = ["select_hvg", "select_markers", "compute_leverage_scores", "build_knn_graph", "build_radius_graph",
            "coords_to_adjacency", "check_random_state", "compute_rmse", "compute_correlation",
            "spatial_autocorrelation", "spatial_niches", "kmeans", "kmeans_plusplus", "spatial_permutation_test",
            "permutation_indices", "randomization_variance", "local_spatial_statistics", "conditional_indices",
            "spatial_correlogram", "celltype_expression", "weighted_gene_sums", "nnls_gram", "spatially_variable_genes",
-           "gene_spatial_sums", "assemble_genes", "spatial_gene_pairs", "gene_pair_sums", "assemble_pairs"]
+           "gene_spatial_sums", "assemble_genes", "spatial_gene_pairs", "gene_pair_sums", "assemble_pairs",
+           "spatial_gene_modules", "spatial_coexpression", "gene_coexpression_sums", "assemble_coexpression"]

@@ -152,16 +152,12 @@ def gene_pair_sums(Y, graph, pairs):
         return _on_graph(Y, g, n, G, pairs, None)[0]
 
 
-def assemble_pairs(n, W, sum_deg_sq, ua, ub, qa, qb, Da, Db, S, Xab, Xba, La, Lb, DLa, DLb, amin, amax, bmin, bmax):
-    """The statistics of the module docstring from the sums of one call (pure host arithmetic): a dict of ``mean_a``, ``mean_b``,
-    ``m2_a``, ``m2_b``, ``morans_r``, ``pearson_r``, ``variance_b_moved``, ``variance_a_moved``, ``z_score``, ``p_value``,
-    ``q_value`` (P,) and ``order`` (P,) int64."""
-    n, W, sum_deg_sq = int(n), int(W), int(sum_deg_sq)
-    planes = [np.asarray(a, dtype=np.float64) for a in (ua, ub, qa, qb, Da, Db, S, Xab, Xba, La, Lb, DLa, DLb, amin, amax, bmin, bmax)]
-    if planes[0].ndim != 1 or any(a.shape != planes[0].shape for a in planes):
-        raise ValueError(f"the seventeen sums must be 1-D arrays of one length, got shapes {[a.shape for a in planes]}")
-    ua, ub, qa, qb, Da, Db, S, Xab, Xba, La, Lb, DLa, DLb, amin, amax, bmin, bmax = planes
-    nan = np.full(ua.shape, np.nan)
+def _pair_arithmetic(n, W, sum_deg_sq, ua, ub, qa, qb, Da, Db, S, Xab, Xba, La, Lb, DLa, DLb, amin, amax, bmin, bmax):
+    """The arithmetic of the module docstring, element by element over float64 arrays that broadcast against each other (the (P,)
+    planes of ``assemble_pairs``; (S, 1) / (1, S) / (S, S) for ``gene_modules.assemble_coexpression``): ``(mean_a, mean_b, m2_a,
+    m2_b, morans_r, pearson_r, variance_b_moved, variance_a_moved, z_score)``, NaN by the rules stated there."""
+    shape = np.broadcast(ua, ub).shape
+    nan = np.full(shape, np.nan)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         if n > 0:
             m_a, m_b, m2_a, m2_b = ua / n, ub / n, qa - ua * ua / n, qb - ub * ub / n
@@ -183,9 +179,21 @@ def assemble_pairs(n, W, sum_deg_sq, ua, ub, qa, qb, Da, Db, S, Xab, Xba, La, Lb
             dead = dead | ~(np.isfinite(var) & (var > 0))
             z = R / np.sqrt(np.where(dead, 1.0, var))
         else:
-            dead = np.ones(ua.shape, dtype=bool)
+            dead = np.ones(shape, dtype=bool)
             R = pearson = var_b_moved = var_a_moved = z = nan
     R, pearson, var_b_moved, var_a_moved, z = (np.where(dead, np.nan, x) for x in (R, pearson, var_b_moved, var_a_moved, z))
+    return m_a, m_b, m2_a, m2_b, R, pearson, var_b_moved, var_a_moved, z
+
+
+def assemble_pairs(n, W, sum_deg_sq, ua, ub, qa, qb, Da, Db, S, Xab, Xba, La, Lb, DLa, DLb, amin, amax, bmin, bmax):
+    """The statistics of the module docstring from the sums of one call (pure host arithmetic): a dict of ``mean_a``, ``mean_b``,
+    ``m2_a``, ``m2_b``, ``morans_r``, ``pearson_r``, ``variance_b_moved``, ``variance_a_moved``, ``z_score``, ``p_value``,
+    ``q_value`` (P,) and ``order`` (P,) int64."""
+    n, W, sum_deg_sq = int(n), int(W), int(sum_deg_sq)
+    planes = [np.asarray(a, dtype=np.float64) for a in (ua, ub, qa, qb, Da, Db, S, Xab, Xba, La, Lb, DLa, DLb, amin, amax, bmin, bmax)]
+    if planes[0].ndim != 1 or any(a.shape != planes[0].shape for a in planes):
+        raise ValueError(f"the seventeen sums must be 1-D arrays of one length, got shapes {[a.shape for a in planes]}")
+    m_a, m_b, m2_a, m2_b, R, pearson, var_b_moved, var_a_moved, z = _pair_arithmetic(n, W, sum_deg_sq, *planes)
     p = np.array([0.5 * math.erfc(v / math.sqrt(2.0)) if not math.isnan(v) else math.nan for v in z.tolist()], dtype=np.float64)
     return {"mean_a": m_a, "mean_b": m_b, "m2_a": m2_a, "m2_b": m2_b, "morans_r": R, "pearson_r": pearson,
             "variance_b_moved": var_b_moved, "variance_a_moved": var_a_moved, "z_score": z, "p_value": p,

@@ -785,6 +785,42 @@ int fdx_gene_pair_local_dev(const fdx_graph* g, const void* Y_dev, int32_t dtype
 int fdx_gene_pair_local_csr_dev(const fdx_graph* g, const fdx_csr_view* Y, const int32_t* pairs, int32_t P, int64_t max_gather_bytes,
                                 const double* mean_a_dev, const double* mean_b_dev, const double* coef_dev, double* out_dev, int64_t ldo,
                                 void* stream);
+/* ---- spatial gene modules: all-pairs co-expression (additive, not in the reference; csrc/gene_module_kernels.cpp) ----------------- *
+ * For S distinct columns `genes` (int32 on the HOST, 1 <= S <= 4096) of Y (n, G) - Y, g, deg_i, lag and counts_out as for
+ * fdx_gene_pair_sums_dev - the raw sums of every pair of them, all arithmetic float64 on the value converted from its storage type:
+ *   gene_sums_dev (6, S) row-major, DEVICE:   0 u = sum_i y    1 D = sum_i deg_i*y    2 L = sum_i lag*lag    3 DL = sum_i deg_i*lag
+ *                                             4 ymin           5 ymax
+ *   cross_dev (2, S, S) row-major, DEVICE:    0 S_ab = sum_i y_a,i*y_b,i           1 X_ab = sum_i y_a,i*lag_b,i
+ * (a, b: places in `genes`), so sum y_a^2 = S_aa and sum y_a*lag_a = X_aa; entry for entry the planes S, Xab, Xba, ua, Da, La, DLa,
+ * amin, amax of fdx_gene_pair_sums_dev.  A CSR entry that is not stored is the value 0.  n = 0: zeros, NaN in planes 4 and 5.
+ * The columns are first gathered into a dense (n, S_pad) matrix of the storage type in the graph's order (S_pad: S rounded up to a
+ * multiple of 64) - one matrix, never chunked, refused above max_gather_bytes (0: 16 GiB).  The graph's positions are then cut into
+ * SPLITS of split_segments segments of FDX_GENE_SPATIAL_SEGMENT_POSITIONS positions (0: 16 segments); a split is summed position
+ * after position - the matrices on the float64 matrix cores, four positions an instruction; the per-gene sums in four quarter sums,
+ * quarter w over the positions [64 w, 64 w + 64) of every segment of the split, added in the order w = 0 .. 3 - and the split sums
+ * are added in ascending order.
+ * Order: no floating-point atomics; two calls return the same bits; so does a call with fewer split sums in flight; EVERY NUMBER
+ * DEPENDS ONLY ON THE GRAPH, ITS ONE OR TWO COLUMNS AND split_segments - not on which other genes are listed or on their order; S is
+ * bitwise symmetric.  Another split_segments moves the boundaries at which the sums are reassociated: other roundings, and no
+ * change where every partial sum is exactly representable.
+ * The score entries write, for every spot i (the CALLER's order) and module c < C, to out_dev[i * ldo + c] (float64, DEVICE)
+ *   sum over the genes s with label[s] == c, in the order of `genes`, of  y_s,i * scale_dev[s] - shift_dev[s]
+ * label: S int32 on the HOST, -1: the gene takes no part; scale_dev, shift_dev: S float64 each on the DEVICE; a module without
+ * genes scores 0.  Asynchronous on `stream`.
+ * Refused with a message: what fdx_gene_spatial_sums_dev refuses, then "S must be in [1, 4096]", "gene index out of range",
+ * "gene listed twice", "gathered matrix needs <bytes> bytes, max_gather_bytes is <bytes>", and for the scores "ldo < C",
+ * "C must be at least 1", "label outside [-1, C)". */
+int fdx_gene_coexpr_sums_dev(const fdx_graph* g, const void* Y_dev, int32_t dtype, int64_t n, int32_t G, int64_t ldy, const int32_t* genes,
+                             int32_t S, int32_t split_segments, int64_t max_gather_bytes, double* gene_sums_dev, double* cross_dev,
+                             int64_t* counts_out, void* stream);
+int fdx_gene_coexpr_sums_csr_dev(const fdx_graph* g, const fdx_csr_view* Y, const int32_t* genes, int32_t S, int32_t split_segments,
+                                 int64_t max_gather_bytes, double* gene_sums_dev, double* cross_dev, int64_t* counts_out, void* stream);
+int fdx_gene_module_scores_dev(const fdx_graph* g, const void* Y_dev, int32_t dtype, int64_t n, int32_t G, int64_t ldy, const int32_t* genes,
+                               const int32_t* label, int32_t S, int32_t C, const double* scale_dev, const double* shift_dev,
+                               double* out_dev, int64_t ldo, void* stream);
+int fdx_gene_module_scores_csr_dev(const fdx_graph* g, const fdx_csr_view* Y, const int32_t* genes, const int32_t* label, int32_t S,
+                                   int32_t C, int64_t max_gather_bytes, const double* scale_dev, const double* shift_dev, double* out_dev,
+                                   int64_t ldo, void* stream);
 /* beta (K, ld) type-major -> beta_out / prop_out (n, K) row-major in solver order of the own spots. */
 int fdx_normalize_dev(const double* beta_dev, int64_t ld, int64_t n, int32_t K, double* beta_out_dev, double* prop_out_dev,
                       void* stream);
