@@ -770,6 +770,25 @@ class FlashDeconv:
         from ..utils.gene_modules import spatial_gene_modules
         return spatial_gene_modules(Y, self, output="torch" if _lib.is_cuda_tensor(self.proportions_) else "numpy", **kw)
 
+    def get_niche_genes(self, Y, groups=None, n_niches=None, **kw):
+        """Which genes mark each niche of this tissue (additive, not in the reference): per group of spots and gene of ``Y`` the
+        Wilcoxon rank-sum test and the Welch t test of the group against all other spots, with effect sizes, q values and the
+        ranking - ``utils.group_genes.rank_genes_groups``.  Exactly one of ``groups`` ((n_spots,) integer labels, ``-1`` = left
+        out) and ``n_niches`` (the ``labels`` of ``get_spatial_niches(n_niches)``) is given.  ``Y``: ``n_spots_`` rows, dense or
+        CSR, ANY gene set, tested as it is passed.  Further keywords (``n_groups``, ``pseudocount``, ``n_top``, ``output``) go to
+        ``rank_genes_groups``."""
+        if (groups is None) == (n_niches is None):
+            raise ValueError("exactly one of groups and n_niches must be given")
+        self._weights_for(Y, "proportions", None)              # fitted, and Y has the fit's spots as rows
+        from ..utils.group_genes import MAX_GROUPS, check_request, rank_genes_groups
+        if n_niches is not None:
+            if isinstance(n_niches, (int, np.integer)) and n_niches > MAX_GROUPS:
+                raise ValueError(f"marker genes are built for at most {MAX_GROUPS} niches, got {n_niches}")
+            check_request(tuple(Y.shape), None, None, kw.get("pseudocount", 1e-9), kw.get("n_top"))      # before the k-means
+            kw.setdefault("n_groups", n_niches)
+            groups = self.get_spatial_niches(n_niches)["labels"]
+        return rank_genes_groups(Y, groups, **kw)
+
     def get_dominant_cell_type(self):
         self._require_fitted()
         if hasattr(self.proportions_, "argmax") and not isinstance(self.proportions_, np.ndarray):

@@ -360,7 +360,10 @@ int csr_passes(const fdx_csr_view* Y, const T* values, const int* yrows, const d
     });
 }
 
-// group_off on the HOST (fdx.h).  Everything queued on st; scratch from the pool.
+}  // namespace
+
+// group_off on the HOST (fdx.h).  Everything queued on st; scratch from the pool.  Declared in gene_pass.h: the marker-gene sums
+// (gene_group_kernels.cpp) take their u and q from here.
 int launch_weighted_gene_sums(const GeneMatrix& y, const double* W, long long ldw, int K, const int* rows, const int* group_off, int C,
                               double* A, double* B, double* q, double* u, hipStream_t st) {
     // the segments of every group, as positions of the sorted row list
@@ -402,6 +405,8 @@ int launch_weighted_gene_sums(const GeneMatrix& y, const double* W, long long ld
         y, [&](auto* Yd) { return dense_passes(Yd, y.ldy, rows, Wp, K, Kpad, sg, y.G, B, q, u, st); },
         [&](auto* values) { return csr_passes(y.csr, values, rows, Wp, K, Kpad, sg, B, q, u, st); });
 }
+
+namespace {
 
 int launch_nnls_gram(const double* A, const double* B, const double* q, int C, int K, int G, double ridge, int max_iter, double tol,
                      double* S, int* n_iter, int* converged, double* rss, hipStream_t st) {

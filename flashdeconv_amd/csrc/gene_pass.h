@@ -63,4 +63,8 @@ int dispatch_gene_matrix(const GeneMatrix& y, Dense&& dense, Csr&& csr) {
     return y.dtype == FDX_F32 ? dense((const float*)y.dense) : dense((const double*)y.dense);
 }
 
+// The weighted gene sums (expression_kernels.cpp; fdx.h: fdx_weighted_gene_sums_dev, whose arguments these are, already checked).
+int launch_weighted_gene_sums(const GeneMatrix& y, const double* W, long long ldw, int K, const int* rows, const int* group_off, int C,
+                              double* A, double* B, double* q, double* u, hipStream_t st);
+
 }  // namespace fdx

@@ -8,7 +8,7 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
                layer_st=None, layer_ref=None, spatial_key="spatial", key_added="flashdeconv", random_state=0, copy=False,
                spot_diagnostics=False, spatial_stats=False, n_niches=None, spatial_permutations=0, local_stats=False,
                correlogram=False, celltype_expression=False, spatial_genes=False, gene_pairs=None,
-               gene_modules=False):
+               gene_modules=False, niche_genes=False):
     """Writes ``.obsm[key_added]`` (proportions DataFrame), ``.obs[key_added + '_dominant']`` and
     ``.uns[key_added + '_params']``; returns the modified copy when ``copy=True``, else ``None``.  ``spot_diagnostics=True``
     (additive) also writes ``.obs[key_added + '_residual']`` (relative sketch residual per spot) and
@@ -50,7 +50,13 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
     one not selected or not assigned), ``.obsm[key_added + '_module_scores']`` (DataFrame, ``obs_names`` x module: the mean
     standardised expression of the module's genes), ``.uns[key_added + '_gene_modules']`` (DataFrame with one row per module:
     ``size``, ``mean_R`` - the mean bivariate Moran's R between its genes - and ``genes``, their names) and
-    ``.uns[key_added + '_params']['gene_modules']``; anything else is a ``ValueError`` before the fit."""
+    ``.uns[key_added + '_params']['gene_modules']``; anything else is a ``ValueError`` before the fit.
+    ``niche_genes=True`` (additive; needs ``n_niches``, a ``ValueError`` before the fit otherwise) also writes
+    ``.uns[key_added + '_niche_genes']``, a long DataFrame of the 50 genes that mark each niche best - the columns ``niche``,
+    ``gene``, ``z_score`` and ``auc`` (Wilcoxon rank-sum test of the niche's spots against all others on the spot matrix),
+    ``log2_fold_change``, ``pct``, ``pct_rest`` (the share of spots that express the gene, inside and outside the niche) and
+    ``q_value`` (Benjamini-Hochberg over the genes), by decreasing ``z_score`` inside a niche
+    (``FlashDeconv.get_niche_genes``) - and ``.uns[key_added + '_params']['niche_genes']``."""
     from ..core.deconv import FlashDeconv
     from ..io import prepare_data, result_to_anndata
     from ..utils.correlogram import correlogram_request
@@ -66,6 +72,10 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
         module_genes = check_selection(gene_modules)
     else:
         module_genes = 500 if gene_modules else None
+    if not isinstance(niche_genes, (bool, np.bool_)):
+        raise ValueError(f"niche_genes must be True or False, got {niche_genes!r}")
+    if niche_genes and n_niches is None:
+        raise ValueError("niche_genes=True needs n_niches: the niches whose marker genes are asked for")
     if gene_pairs is not None:
         gene_pairs = [tuple(pair) for pair in gene_pairs]
         if not gene_pairs or any(len(pair) != 2 for pair in gene_pairs):
@@ -80,6 +90,11 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
     if spatial_genes:
         from ..utils.spatial_genes import check_request as check_spatial_genes
         check_spatial_genes(tuple(Y.shape), len(names))
+    if niche_genes:
+        from ..utils.group_genes import MAX_GROUPS, check_request as check_niche_genes
+        check_niche_genes(tuple(Y.shape))
+        if isinstance(n_niches, (int, np.integer)) and n_niches > MAX_GROUPS:
+            raise ValueError(f"niche_genes is built for at most {MAX_GROUPS} niches, got n_niches = {n_niches}")
     if gene_pairs is not None:
         from ..utils.gene_pairs import check_request as check_gene_pairs
         column = {str(name): j for j, name in enumerate(genes)}
@@ -136,6 +151,17 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
         adata.uns[f"{key_added}_niche_composition"] = pd.DataFrame(niches["composition"], index=index,
                                                                    columns=[str(t) for t in names])
         adata.uns[f"{key_added}_params"]["n_niches"] = int(n_niches)
+    if niche_genes:
+        import pandas as pd
+        ng = model.get_niche_genes(Y, groups=np.asarray(_host(niches["labels"])), n_groups=int(n_niches), n_top=50, output="numpy")
+        top = ng["top"]
+        niche_of = np.repeat(np.arange(top.shape[0]), top.shape[1])
+        flat = top.ravel()
+        table = {"niche": niche_of, "gene": [str(genes[j]) for j in flat]}
+        for name in ("z_score", "auc", "log2_fold_change", "pct", "pct_rest", "q_value"):
+            table[name] = ng[name][niche_of, flat]
+        adata.uns[f"{key_added}_niche_genes"] = pd.DataFrame(table)
+        adata.uns[f"{key_added}_params"]["niche_genes"] = True
     if local_stats:
         import pandas as pd
         local = model.get_local_spatial_statistics(n_permutations=spatial_permutations)

@@ -821,6 +821,33 @@ int fdx_gene_module_scores_dev(const fdx_graph* g, const void* Y_dev, int32_t dt
 int fdx_gene_module_scores_csr_dev(const fdx_graph* g, const fdx_csr_view* Y, const int32_t* genes, const int32_t* label, int32_t S,
                                    int32_t C, int64_t max_gather_bytes, const double* scale_dev, const double* shift_dev, double* out_dev,
                                    int64_t ldo, void* stream);
+/* ---- marker genes of spot groups: rank-sum and Welch sums per (group, gene) (additive, not in the reference; ----------------------- *
+ * csrc/gene_group_kernels.cpp).  Y (n, G) as for fdx_weighted_gene_sums_dev (dense FDX_F32 / FDX_F64 with row stride ldy, or a CSR
+ * view with rows in any order; an entry that is not stored is the value 0), n <= FDX_GENE_GROUP_MAX_ROWS; labels_dev: n int32 on the
+ * DEVICE in [-1, C), -1 leaves the spot out; 1 <= C <= 256.  With N the number of used spots, n_c the size of group c and a gene's
+ * values compared as converted to float64 from their storage type (all 64 bits of a float64 count), to DEVICE memory:
+ *   u_dev, q_dev (C, G) float64   sum y, sum y*y over group c: the planes u and q of fdx_weighted_gene_sums_dev called with W = 1 and
+ *                                 the rows sorted stably by label, bit for bit (the same pass runs)
+ *   nnz_dev (C, G) int64          spots of group c with y != 0 (-0.0 and a stored zero are zeros)
+ *   R2_dev (C, G) int64           sum over the spots i of group c of 2 * midrank_i, midrank_i the 1-based average rank of y_ig among
+ *                                 the N used values of gene g (ties share the mean of their ranks)
+ *   T_dev (G) int64               sum over the tie runs of gene g's N used values of t^3 - t, t the run's length
+ * and to HOST memory n_c_out (C) and *N_out.  The integers are exact, so any accumulation order gives the same bits (integer
+ * atomics carry them; no floating-point atomic anywhere).  Zeros are never sorted: the nonzeros of a STRIPE of consecutive genes are
+ * compacted, sorted by value and then stably by gene (rocPRIM radix sorts), and the zero run's ranks follow from the counts.  The
+ * stripes are cut from the per-gene counts so that keys, payloads and sort workspace - 24 bytes an entry for float32, 32 for float64,
+ * plus rocPRIM's - stay within max_sort_bytes (0: about 1 GiB), one gene a stripe at the least; a stripe never changes a result.
+ * info_out (HOST, may be NULL): {stripes, entries of the largest stripe, bytes of its ranking workspace}.  NaN in Y is not
+ * supported.  Two host synchronisations (the group sizes, the per-gene counts).  Refused with a message: what
+ * fdx_weighted_gene_sums_dev refuses of Y, "C must be 1 .. 256", "at most 2000000 rows" (sum t^3 - t stays below 2^63),
+ * "max_sort_bytes < 0", "a label lies outside [-1, C)". */
+#define FDX_GENE_GROUP_MAX_ROWS 2000000
+int fdx_gene_group_sums_dev(const void* Y_dev, int32_t dtype, int64_t n, int32_t G, int64_t ldy, const int32_t* labels_dev, int32_t C,
+                            int64_t max_sort_bytes, double* u_dev, double* q_dev, int64_t* nnz_dev, int64_t* R2_dev, int64_t* T_dev,
+                            int64_t* n_c_out, int64_t* N_out, int64_t* info_out, void* stream);
+int fdx_gene_group_sums_csr_dev(const fdx_csr_view* Y, const int32_t* labels_dev, int32_t C, int64_t max_sort_bytes, double* u_dev,
+                                double* q_dev, int64_t* nnz_dev, int64_t* R2_dev, int64_t* T_dev, int64_t* n_c_out, int64_t* N_out,
+                                int64_t* info_out, void* stream);
 /* beta (K, ld) type-major -> beta_out / prop_out (n, K) row-major in solver order of the own spots. */
 int fdx_normalize_dev(const double* beta_dev, int64_t ld, int64_t n, int32_t K, double* beta_out_dev, double* prop_out_dev,
                       void* stream);
