@@ -180,6 +180,10 @@ SIGNATURES = {
                                            c_void_p, c_i64, c_void_p]),
     "fdx_gene_module_scores_csr_dev": (c_int, [c_void_p, ctypes.POINTER(CsrView), p_i32, p_i32, c_i32, c_i32, c_i64, c_void_p, c_void_p,
                                                c_void_p, c_i64, c_void_p]),
+    "fdx_gene_spatial_perm_dev": (c_int, [c_void_p, c_void_p, c_i32, c_i64, c_i32, c_i64, p_i32, c_i32, ctypes.c_uint64, c_i64, c_i64, c_i64,
+                                          c_i64, c_i64, c_void_p, c_void_p, p_i64, p_i64, c_void_p]),
+    "fdx_gene_spatial_perm_csr_dev": (c_int, [c_void_p, ctypes.POINTER(CsrView), p_i32, c_i32, ctypes.c_uint64, c_i64, c_i64, c_i64, c_i64,
+                                              c_i64, c_void_p, c_void_p, p_i64, p_i64, c_void_p]),
     "fdx_gene_group_sums_dev": (c_int, [c_void_p, c_i32, c_i64, c_i32, c_i64, c_void_p, c_i32, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, p_i64, p_i64, p_i64, c_void_p]),
     "fdx_gene_group_sums_csr_dev": (c_int, [ctypes.POINTER(CsrView), c_void_p, c_i32, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -733,20 +733,39 @@ class FlashDeconv:
                 W = W * sc[:, None]
         return W
 
-    def get_spatially_variable_genes(self, Y, residual=False, what="proportions", spot_scale=None, n_top=None, **kw):
+    def get_spatially_variable_genes(self, Y, residual=False, what="proportions", spot_scale=None, n_top=None, n_permutations=0,
+                                     random_state=None, permutation_genes=None, **kw):
         """Which genes vary over this tissue, and which still do once the fitted composition is accounted for (additive, not in
         the reference): Moran's I and Geary's C per gene of ``Y`` over the graph the fit used, with z scores, p and q values -
         ``utils.spatial_genes.spatially_variable_genes``.  ``Y``: ``n_spots_`` rows, dense or CSR, ANY gene set, scored as it is
         passed.  ``residual=True`` also regresses every gene on ``proportions_`` (``what="proportions"``) or ``beta_``
         (``what="abundances"``), their rows multiplied by ``spot_scale`` as in ``get_celltype_expression``, and reports Moran's I
         of what the composition leaves (``residual_morans_i``, ``residual_z_score``, ``r2``, ``expression``): high for genes with
-        a gradient or a state of their own inside a cell type.  ``n_top``: also ``top``, the first genes of ``order``.  Further
+        a gradient or a state of their own inside a cell type.  ``n_top``: also ``top``, the first genes of ``order``.
+        ``n_permutations=R`` > 0 also ranks Moran's I and Geary's C of the genes ``permutation_genes`` (column indices of ``Y``,
+        None: every gene) against R random reassignments of each gene's values to the spots, on the GPU
+        (``utils.gene_permutations.spatial_gene_permutation_test``, seeded by ``random_state``, None: the model's), and adds
+        ``p_sim``, ``p_sim_less``, ``gearys_p_sim``, ``z_sim``, ``null_mean``, ``null_std``, ``q_sim`` (G,) - NaN for the genes
+        that were not tested - and ``n_permutations``; with 0 the result is what it is without these arguments.  Further
         keywords (``ridge``, ``max_iter``, ``tol``) go to the solve.  Works for both ``output`` kinds of ``fit``."""
         if not isinstance(residual, (bool, np.bool_)):
             raise ValueError(f"residual must be True or False, got {residual!r}")
+        from ..utils._device import check_count
+        from ..utils.gene_permutations import STAT_KEYS, check_request, spatial_gene_permutation_test
+        if check_count("n_permutations", n_permutations):      # (0: exactly today's call, today's errors in today's order)
+            check_request(tuple(Y.shape) if hasattr(Y, "shape") else np.shape(Y), permutation_genes, n_permutations)
         W = self._weights_for(Y, what, spot_scale)
         from ..utils.spatial_genes import spatially_variable_genes
-        return spatially_variable_genes(Y, self, weights=W if residual else None, n_top=n_top, **kw)
+        out = spatially_variable_genes(Y, self, weights=W if residual else None, n_top=n_top, **kw)
+        if n_permutations:
+            seed = self.random_state if random_state is None else random_state
+            perm = spatial_gene_permutation_test(Y, self, genes=permutation_genes, n_permutations=n_permutations, random_state=seed)
+            for key in STAT_KEYS:
+                full = np.full(out["morans_i"].shape[0], np.nan)
+                full[perm["genes"]] = perm[key]
+                out[key] = full
+            out["n_permutations"] = int(n_permutations)
+        return out
 
     def get_gene_pair_colocalisation(self, Y, pairs, local=False, n_top=None):
         """Which pairs of genes - a ligand and its receptor - are expressed next to each other in this tissue, and where (additive,

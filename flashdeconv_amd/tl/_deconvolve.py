@@ -8,7 +8,7 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
                layer_st=None, layer_ref=None, spatial_key="spatial", key_added="flashdeconv", random_state=0, copy=False,
                spot_diagnostics=False, spatial_stats=False, n_niches=None, spatial_permutations=0, local_stats=False,
                correlogram=False, celltype_expression=False, spatial_genes=False, gene_pairs=None,
-               gene_modules=False, niche_genes=False):
+               gene_modules=False, niche_genes=False, gene_permutations=0):
     """Writes ``.obsm[key_added]`` (proportions DataFrame), ``.obs[key_added + '_dominant']`` and
     ``.uns[key_added + '_params']``; returns the modified copy when ``copy=True``, else ``None``.  ``spot_diagnostics=True``
     (additive) also writes ``.obs[key_added + '_residual']`` (relative sketch residual per spot) and
@@ -38,7 +38,11 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
     Moran's ``I`` and Geary's ``C`` of each gene of the spot matrix over the fit's graph, the ``z_score`` under normality, the
     one-sided ``p_value`` under randomisation and its Benjamini-Hochberg ``q_value``, and - regressed on the proportions scaled by
     each spot's row sum over the mean row sum - ``residual_I``, ``residual_z_score`` of what the composition leaves and the
-    ``r2`` it explains, ``FlashDeconv.get_spatially_variable_genes``).
+    ``r2`` it explains, ``FlashDeconv.get_spatially_variable_genes``); with ``gene_permutations=R`` > 0 beside it (an int >= 0,
+    more than 0 only with ``spatial_genes=True``: a ``ValueError`` before the fit otherwise) every gene's values are reassigned to
+    the spots R times on the GPU (``utils.gene_permutations.spatial_gene_permutation_test``, seeded by ``random_state``): the
+    table gains the columns ``p_sim`` (the one-sided permutation p value of Moran's I), ``q_sim`` and ``z_sim``, and
+    ``.uns[key_added + '_params']['gene_permutations']`` holds R.
     ``gene_pairs`` (additive): a non-empty sequence of ``(name_a, name_b)`` - a ligand and its receptor - of ``var_names`` common
     to both objects (an unknown name is a ``ValueError`` before the fit) also writes ``.uns[key_added + '_gene_pairs']``, a
     DataFrame with one row per pair in the caller's order and the columns ``gene_a``, ``gene_b``, ``R`` (the bivariate Moran's R
@@ -65,6 +69,10 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
         raise ValueError(f"celltype_expression must be True or False, got {celltype_expression!r}")
     if not isinstance(spatial_genes, (bool, np.bool_)):
         raise ValueError(f"spatial_genes must be True or False, got {spatial_genes!r}")
+    if isinstance(gene_permutations, (bool, np.bool_)) or not isinstance(gene_permutations, (int, np.integer)) or gene_permutations < 0:
+        raise ValueError(f"gene_permutations must be an int >= 0, got {gene_permutations!r}")
+    if gene_permutations > 0 and not spatial_genes:
+        raise ValueError("gene_permutations > 0 needs spatial_genes=True: the table the permutation columns are added to")
     if not isinstance(gene_modules, (bool, np.bool_)):
         from ..utils.gene_modules import check_selection
         if not isinstance(gene_modules, (int, np.integer)):
@@ -193,12 +201,16 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
         adata.uns[f"{key_added}_params"]["celltype_expression"] = True
     if spatial_genes:
         import pandas as pd
-        sv = model.get_spatially_variable_genes(Y, residual=True, spot_scale=_library_scale(Y))
-        adata.uns[f"{key_added}_spatial_genes"] = pd.DataFrame(
-            {"I": sv["morans_i"], "C": sv["gearys_c"], "z_score": sv["z_score"], "p_value": sv["p_value"], "q_value": sv["q_value"],
-             "residual_I": sv["residual_morans_i"], "residual_z_score": sv["residual_z_score"], "r2": sv["r2"]},
-            index=[str(g) for g in genes])
+        sv = model.get_spatially_variable_genes(Y, residual=True, spot_scale=_library_scale(Y), n_permutations=int(gene_permutations),
+                                                random_state=random_state)
+        columns = {"I": sv["morans_i"], "C": sv["gearys_c"], "z_score": sv["z_score"], "p_value": sv["p_value"], "q_value": sv["q_value"],
+                   "residual_I": sv["residual_morans_i"], "residual_z_score": sv["residual_z_score"], "r2": sv["r2"]}
+        if gene_permutations:
+            columns.update(p_sim=sv["p_sim"], q_sim=sv["q_sim"], z_sim=sv["z_sim"])
+        adata.uns[f"{key_added}_spatial_genes"] = pd.DataFrame(columns, index=[str(g) for g in genes])
         adata.uns[f"{key_added}_params"]["spatial_genes"] = True
+        if gene_permutations:
+            adata.uns[f"{key_added}_params"]["gene_permutations"] = int(gene_permutations)
     if gene_pairs is not None:
         import pandas as pd
         gp = model.get_gene_pair_colocalisation(Y, pair_idx)

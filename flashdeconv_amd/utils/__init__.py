@@ -4,7 +4,8 @@
 ``celltype_expression`` / ``weighted_gene_sums`` / ``nnls_gram`` (``utils.expression``) and ``spatially_variable_genes`` /
 ``gene_spatial_sums`` / ``assemble_genes`` (``utils.spatial_genes``) and ``spatial_gene_pairs`` / ``gene_pair_sums`` /
 ``assemble_pairs`` (``utils.gene_pairs``) and ``spatial_gene_modules`` / ``spatial_coexpression`` / ``gene_coexpression_sums`` /
-``assemble_coexpression`` (``utils.gene_modules``) and ``rank_genes_groups`` / ``gene_group_sums`` / ``assemble_group_tests``
+``assemble_coexpression`` (``utils.gene_modules``) and ``spatial_gene_permutation_test`` / ``gene_permutation_sums`` /
+``assemble_gene_permutation`` (``utils.gene_permutations``) and ``rank_genes_groups`` / ``gene_group_sums`` / ``assemble_group_tests``
 (``utils.group_genes``) are additive."""
 from .genes import select_hvg, select_markers, compute_leverage_scores  # noqa: F401
 from .graph import build_knn_graph, build_radius_graph, coords_to_adjacency  # noqa: F401
@@ -18,6 +19,7 @@ from .expression import celltype_expression, weighted_gene_sums, nnls_gram  # no
 from .spatial_genes import spatially_variable_genes, gene_spatial_sums, assemble_genes  # noqa: F401
 from .gene_pairs import spatial_gene_pairs, gene_pair_sums, assemble_pairs  # noqa: F401
 from .gene_modules import spatial_gene_modules, spatial_coexpression, gene_coexpression_sums, assemble_coexpression  # noqa: F401
+from .gene_permutations import spatial_gene_permutation_test, gene_permutation_sums, assemble_gene_permutation  # noqa: F401
 from .group_genes import rank_genes_groups, gene_group_sums, assemble_group_tests  # noqa: F401
 
 __all__ = ["select_hvg", "select_markers", "compute_leverage_scores", "build_knn_graph", "build_radius_graph",
@@ -26,5 +28,6 @@ __all__ = ["select_hvg", "select_markers", "compute_leverage_scores", "build_knn
            "permutation_indices", "randomization_variance", "local_spatial_statistics", "conditional_indices",
            "spatial_correlogram", "celltype_expression", "weighted_gene_sums", "nnls_gram", "spatially_variable_genes",
            "gene_spatial_sums", "assemble_genes", "rank_genes_groups", "gene_group_sums", "assemble_group_tests",
+           "spatial_gene_permutation_test", "gene_permutation_sums", "assemble_gene_permutation",
            "spatial_gene_pairs", "gene_pair_sums", "assemble_pairs",
            "spatial_gene_modules", "spatial_coexpression", "gene_coexpression_sums", "assemble_coexpression"]

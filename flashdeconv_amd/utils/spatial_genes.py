@@ -49,7 +49,7 @@ A gene with a spatial pattern of its own - a gradient or a state inside a cell t
 pattern is where its cell types sit does not.
 
 **Out of scope.**  Normalising ``Y`` (the caller passes the matrix they want scored; ``log1p`` on a CSR's data keeps it sparse);
-permutation p values per gene; Geary's C and the randomisation variance of the residual; ``ShardedFlashDeconv``.
+permutation p values per gene (``utils.gene_permutations`` has them); Geary's C and the randomisation variance of the residual; ``ShardedFlashDeconv``.
 """
 import ctypes
 import math

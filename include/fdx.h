@@ -821,6 +821,43 @@ int fdx_gene_module_scores_dev(const fdx_graph* g, const void* Y_dev, int32_t dt
 int fdx_gene_module_scores_csr_dev(const fdx_graph* g, const fdx_csr_view* Y, const int32_t* genes, const int32_t* label, int32_t S,
                                    int32_t C, int64_t max_gather_bytes, const double* scale_dev, const double* shift_dev, double* out_dev,
                                    int64_t ldo, void* stream);
+/* ---- permutation test per gene for Moran's I and Geary's C (additive, not in the reference; csrc/gene_perm_kernels.cpp) ------------ *
+ * For S distinct columns `genes` (int32 on the HOST, S >= 1) of Y (n, G) - Y, g, deg_i and counts_out = {n, W, sum deg^2} as for
+ * fdx_gene_spatial_sums_dev - and the permutations pi_r of fdx_spatial_perm_dev (utils/spatial_stats.py:permutation_indices of
+ * `seed`), r = first_perm .. first_perm + n_perm - 1, with v_i = y[pi_r(i)] in the CALLER's spot order, all arithmetic float64 on
+ * the value converted from its storage type:
+ *   null_dev (n_perm, 3, S) row-major, DEVICE (may be NULL when n_perm = 0):
+ *       0 P_r = sum_i v_i * sum_{j in N(i)} v_j        1 D_r = sum_i deg_i*v_i        2 H_r = sum_i deg_i*v_i*v_i
+ *   obs_dev (7, S) row-major, DEVICE:   0 u = sum y   1 q = sum y*y   2 D   3 H   4 P (the identity in place of pi_r)   5 ymin   6 ymax
+ * A CSR entry that is not stored is the value 0.  n = 0: zeros, NaN in planes 5 and 6, and no permutation kernel is launched; nor
+ * is one for n_perm = 0 (the observed planes only).
+ * The columns are gathered once, in the storage type and the graph's order, into tiles of TILE genes (position-major inside a
+ * tile; genes in STRIPES of whole tiles, one tile at the least, when the copy would exceed max_gather_bytes - 0: about 1 GiB);
+ * per permutation of a BATCH a table of n int32 - the
+ * position whose value lands at each position - is computed once and shared by every gene (max_batch caps the batch, 0: what
+ * about 1 GiB of tables holds).  A workgroup owns a tile and a range of the batch's permutations; by how much LDS the tile needs
+ * against max_lds_bytes (0: the device's 160 KiB per workgroup) a call takes one ROUTE:
+ *   2  the tile's columns and the permutation's table in LDS (TILE = the largest of 4, 2, 1 - float64: of 2, 1 - with
+ *      TILE*elem*n + 4*n bytes fitting)
+ *   1  one column in LDS, the table read through L2        0  columns and table read through L2 (any n), TILE = 4 (float64: 2)
+ * On route 2 the LDS left beside the tile holds up to four tables, and every 256 threads of a workgroup walk a permutation of their
+ * own (WAYS); a workgroup takes CHUNK permutations of the batch, never fewer than it has ways.
+ * info_out (6 int64 on the HOST, may be NULL): {TILE, batch, route, stripes, ways and chunk of the first permutation launch}.
+ * Order: no floating-point atomics; thread t of 256 adds the graph's positions p = t, t + 256, ... in ascending order, a
+ * neighbour sum in the stored neighbour order, and a fixed tree combines the 256 partial sums - so EVERY (gene, permutation) SUM
+ * DEPENDS ONLY ON THE GRAPH, THE COLUMN AND THE PERMUTATION: not on the tile, the ways, the batch, the stripe, the route, the other genes,
+ * their order or max_batch; two calls and a range of permutations split into several calls return the same bits.
+ * One host synchronisation (the counts).  Refused with a message: what fdx_gene_spatial_sums_dev refuses ("null argument",
+ * "ldy < G", "dtype must be FDX_F32 or FDX_F64", "G must be at least 1", "Y has <n> rows but the graph has <m> spots"), then
+ * "S must be at least 1", "gene index out of range", "gene listed twice", "first_perm must not be negative", "n_perm must not be
+ * negative", "max_batch must not be negative", "max_lds_bytes must not be negative", "max_gather_bytes must not be negative". */
+int fdx_gene_spatial_perm_dev(const fdx_graph* g, const void* Y_dev, int32_t dtype, int64_t n, int32_t G, int64_t ldy, const int32_t* genes,
+                              int32_t S, uint64_t seed, int64_t first_perm, int64_t n_perm, int64_t max_batch, int64_t max_lds_bytes,
+                              int64_t max_gather_bytes, double* obs_dev, double* null_dev, int64_t* counts_out, int64_t* info_out,
+                              void* stream);
+int fdx_gene_spatial_perm_csr_dev(const fdx_graph* g, const fdx_csr_view* Y, const int32_t* genes, int32_t S, uint64_t seed,
+                                  int64_t first_perm, int64_t n_perm, int64_t max_batch, int64_t max_lds_bytes, int64_t max_gather_bytes,
+                                  double* obs_dev, double* null_dev, int64_t* counts_out, int64_t* info_out, void* stream);
 /* ---- marker genes of spot groups: rank-sum and Welch sums per (group, gene) (additive, not in the reference; ----------------------- *
  * csrc/gene_group_kernels.cpp).  Y (n, G) as for fdx_weighted_gene_sums_dev (dense FDX_F32 / FDX_F64 with row stride ldy, or a CSR
  * view with rows in any order; an entry that is not stored is the value 0), n <= FDX_GENE_GROUP_MAX_ROWS; labels_dev: n int32 on the
