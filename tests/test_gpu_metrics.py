@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from metrics_ref import rankdata_spearman as _rankdata_spearman
 
 pytestmark = pytest.mark.gpu
 
@@ -141,11 +142,6 @@ def test_numpy_and_device_inputs_bit_identical_and_repeatable(gold, case):
     _bits_equal(a, b)
     _bits_equal(b, c)
     _bits_equal(M.compute_jsd(p, t), _host(M.compute_jsd(_torch(p), _torch(t))))
-
-
-def _rankdata_spearman(a, b):
-    from scipy.stats import rankdata
-    return np.corrcoef(rankdata(a), rankdata(b))[0, 1]
 
 
 def test_large_heavily_tied_against_numpy_scipy():
