@@ -808,6 +808,45 @@ class FlashDeconv:
             groups = self.get_spatial_niches(n_niches)["labels"]
         return rank_genes_groups(Y, groups, **kw)
 
+    def get_neighborhood_enrichment(self, labels=None, n_niches=None, n_permutations=999, random_state=None, **kw):
+        """Which niches or cell types border each other more often than chance over the graph the fit used, and which avoid each
+        other (additive, not in the reference): the join counts of spot labels with their exact moments, the analytic z score,
+        the interaction matrix and a permutation test on the GPU - ``utils.neighborhoods.neighborhood_enrichment``.  One source
+        of labels: ``labels`` ((n_spots,) integers in ``[-1, C)``, ``-1`` = not counted; ``n_labels`` may be passed beside them),
+        ``n_niches`` (the ``labels`` of ``get_spatial_niches(n_niches)``, which takes the further keywords) or neither - each
+        spot's dominant cell type, with ``C = n_cell_types_``; giving both is a ``ValueError``.  ``random_state``: None is the
+        model's.  ``return_null=True`` also returns ``null``.  Works for both ``output`` kinds of ``fit``: labels stay on the
+        device where they are."""
+        self._require_fitted()
+        if labels is not None and n_niches is not None:
+            raise ValueError("at most one of labels and n_niches may be given")
+        from ..utils._device import check_count
+        from ..utils.neighborhoods import _check_flag, check_labels, neighborhood_enrichment
+        check_count("n_permutations", n_permutations)
+        return_null = _check_flag("return_null", kw.pop("return_null", False))
+        n_labels = kw.pop("n_labels", None)
+        if n_niches is None and kw:
+            raise TypeError(f"unexpected keyword arguments without n_niches: {sorted(kw)}")
+        if labels is not None:
+            if check_labels(labels, n_labels)[0] != self.n_spots_:
+                raise ValueError(f"labels must have the {self.n_spots_} spots of the fit, got {tuple(labels.shape)}")
+        elif n_niches is not None:
+            if n_labels is not None:
+                raise ValueError("n_labels goes with labels: with n_niches the number of labels is n_niches")
+            from ..utils.niches import _check_n_niches
+            n_labels = _check_n_niches(n_niches, self.n_spots_)              # at most 64 niches: the labels this entry takes
+            labels = self.get_spatial_niches(n_niches, **kw)["labels"]
+        else:
+            if n_labels is not None:
+                raise ValueError("n_labels goes with labels: the dominant cell types are n_cell_types_ labels")
+            if self.n_cell_types_ > 64:
+                raise ValueError(f"neighbourhood enrichment is built for at most 64 labels, got {self.n_cell_types_} cell types")
+            n_labels = int(self.n_cell_types_)
+            labels = self.get_dominant_cell_type()
+        return neighborhood_enrichment(labels, self, n_labels=n_labels, n_permutations=n_permutations,
+                                       random_state=self.random_state if random_state is None else random_state,
+                                       return_null=return_null)
+
     def get_dominant_cell_type(self):
         self._require_fitted()
         if hasattr(self.proportions_, "argmax") and not isinstance(self.proportions_, np.ndarray):

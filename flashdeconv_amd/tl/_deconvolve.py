@@ -8,7 +8,7 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
                layer_st=None, layer_ref=None, spatial_key="spatial", key_added="flashdeconv", random_state=0, copy=False,
                spot_diagnostics=False, spatial_stats=False, n_niches=None, spatial_permutations=0, local_stats=False,
                correlogram=False, celltype_expression=False, spatial_genes=False, gene_pairs=None,
-               gene_modules=False, niche_genes=False, gene_permutations=0):
+               gene_modules=False, niche_genes=False, gene_permutations=0, nhood_enrichment=False):
     """Writes ``.obsm[key_added]`` (proportions DataFrame), ``.obs[key_added + '_dominant']`` and
     ``.uns[key_added + '_params']``; returns the modified copy when ``copy=True``, else ``None``.  ``spot_diagnostics=True``
     (additive) also writes ``.obs[key_added + '_residual']`` (relative sketch residual per spot) and
@@ -60,7 +60,14 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
     ``gene``, ``z_score`` and ``auc`` (Wilcoxon rank-sum test of the niche's spots against all others on the spot matrix),
     ``log2_fold_change``, ``pct``, ``pct_rest`` (the share of spots that express the gene, inside and outside the niche) and
     ``q_value`` (Benjamini-Hochberg over the genes), by decreasing ``z_score`` inside a niche
-    (``FlashDeconv.get_niche_genes``) - and ``.uns[key_added + '_params']['niche_genes']``."""
+    (``FlashDeconv.get_niche_genes``) - and ``.uns[key_added + '_params']['niche_genes']``.
+    ``nhood_enrichment=True`` (additive; anything but a bool is a ``ValueError`` before the fit) also writes
+    ``.uns[key_added + '_nhood_enrichment']``, a dict of three DataFrames indexed both ways by niche index when ``n_niches`` is
+    given, else by cell type (each spot labelled by its dominant one): ``count`` (how often a spot of the row's label has a
+    neighbour of the column's over the fit's graph), ``zscore`` (the count against ``spatial_permutations`` random reassignments of
+    the labels to the spots on the GPU, 999 when that is 0, seeded by ``random_state``) and ``pvalue`` (two-sided)
+    (``FlashDeconv.get_neighborhood_enrichment``) - and ``.uns[key_added + '_params']['nhood_enrichment']``, the number of
+    permutations."""
     from ..core.deconv import FlashDeconv
     from ..io import prepare_data, result_to_anndata
     from ..utils.correlogram import correlogram_request
@@ -82,6 +89,8 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
         module_genes = 500 if gene_modules else None
     if not isinstance(niche_genes, (bool, np.bool_)):
         raise ValueError(f"niche_genes must be True or False, got {niche_genes!r}")
+    if not isinstance(nhood_enrichment, (bool, np.bool_)):
+        raise ValueError(f"nhood_enrichment must be True or False, got {nhood_enrichment!r}")
     if niche_genes and n_niches is None:
         raise ValueError("niche_genes=True needs n_niches: the niches whose marker genes are asked for")
     if gene_pairs is not None:
@@ -170,6 +179,21 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
             table[name] = ng[name][niche_of, flat]
         adata.uns[f"{key_added}_niche_genes"] = pd.DataFrame(table)
         adata.uns[f"{key_added}_params"]["niche_genes"] = True
+    if nhood_enrichment:
+        import pandas as pd
+        n_perm = int(spatial_permutations) if spatial_permutations else 999
+        if n_niches is not None:
+            ne = model.get_neighborhood_enrichment(labels=niches["labels"], n_labels=int(n_niches), n_permutations=n_perm,
+                                                   random_state=random_state)
+            index = list(range(int(n_niches)))
+        else:
+            ne = model.get_neighborhood_enrichment(n_permutations=n_perm, random_state=random_state)
+            index = [str(t) for t in names]
+        adata.uns[f"{key_added}_nhood_enrichment"] = {
+            "count": pd.DataFrame(ne["count"], index=index, columns=index),
+            "zscore": pd.DataFrame(ne["z_sim"], index=index, columns=index),
+            "pvalue": pd.DataFrame(ne["p_value"], index=index, columns=index)}
+        adata.uns[f"{key_added}_params"]["nhood_enrichment"] = n_perm
     if local_stats:
         import pandas as pd
         local = model.get_local_spatial_statistics(n_permutations=spatial_permutations)

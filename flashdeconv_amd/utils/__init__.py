@@ -6,7 +6,8 @@
 ``assemble_pairs`` (``utils.gene_pairs``) and ``spatial_gene_modules`` / ``spatial_coexpression`` / ``gene_coexpression_sums`` /
 ``assemble_coexpression`` (``utils.gene_modules``) and ``spatial_gene_permutation_test`` / ``gene_permutation_sums`` /
 ``assemble_gene_permutation`` (``utils.gene_permutations``) and ``rank_genes_groups`` / ``gene_group_sums`` / ``assemble_group_tests``
-(``utils.group_genes``) are additive."""
+(``utils.group_genes``) and ``neighborhood_enrichment`` / ``label_pair_counts`` / ``join_count_moments`` / ``assemble_enrichment``
+(``utils.neighborhoods``) are additive."""
 from .genes import select_hvg, select_markers, compute_leverage_scores  # noqa: F401
 from .graph import build_knn_graph, build_radius_graph, coords_to_adjacency  # noqa: F401
 from .random import check_random_state  # noqa: F401
@@ -21,6 +22,7 @@ from .gene_pairs import spatial_gene_pairs, gene_pair_sums, assemble_pairs  # no
 from .gene_modules import spatial_gene_modules, spatial_coexpression, gene_coexpression_sums, assemble_coexpression  # noqa: F401
 from .gene_permutations import spatial_gene_permutation_test, gene_permutation_sums, assemble_gene_permutation  # noqa: F401
 from .group_genes import rank_genes_groups, gene_group_sums, assemble_group_tests  # noqa: F401
+from .neighborhoods import neighborhood_enrichment, label_pair_counts, join_count_moments, assemble_enrichment  # noqa: F401
 
 __all__ = ["select_hvg", "select_markers", "compute_leverage_scores", "build_knn_graph", "build_radius_graph",
            "coords_to_adjacency", "check_random_state", "compute_rmse", "compute_correlation",
@@ -29,5 +31,6 @@ __all__ = ["select_hvg", "select_markers", "compute_leverage_scores", "build_knn
            "spatial_correlogram", "celltype_expression", "weighted_gene_sums", "nnls_gram", "spatially_variable_genes",
            "gene_spatial_sums", "assemble_genes", "rank_genes_groups", "gene_group_sums", "assemble_group_tests",
            "spatial_gene_permutation_test", "gene_permutation_sums", "assemble_gene_permutation",
+           "neighborhood_enrichment", "label_pair_counts", "join_count_moments", "assemble_enrichment",
            "spatial_gene_pairs", "gene_pair_sums", "assemble_pairs",
            "spatial_gene_modules", "spatial_coexpression", "gene_coexpression_sums", "assemble_coexpression"]

@@ -614,6 +614,27 @@ int fdx_spatial_perm_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, i
 /* out_dev[i] (n int32, DEVICE) = pi_r(i) of `seed` for i < n, by the device function the kernels of fdx_spatial_perm_dev use.
  * Asynchronous on `stream`. */
 int fdx_permutation_indices_dev(uint64_t seed, int64_t r, int64_t n, int32_t* out_dev, void* stream);
+/* Neighbourhood enrichment of spot labels over a whole graph: join counts and their permutation null (additive, not in the
+ * reference).  labels_dev: g->n int32 on the DEVICE in the caller's spot order, each in [-1, C), -1 = not counted; 1 <= C <= 64.
+ * With A the graph's symmetric binary adjacency, to HOST memory:
+ *   label_counts_out[a] = n_a = #{i : l_i = a}                 pair_out (C, C) row-major = N_ab = #{(i, j) : A_ij = 1, l_i = a, l_j = b}
+ *   counts_out          = { n, W = sum_i deg_i, sum_i deg_i^2 }
+ * (ordered pairs: N is symmetric and N_aa is twice the number of undirected a-a edges).  Then permutations
+ * first_perm .. first_perm + n_perm - 1 of `seed` (pi_r as for fdx_spatial_perm_dev; n_perm = 0: the observed counts only): the
+ * labels l^r_i = l[pi_r(i)] - spots labelled -1 are shuffled like any other and never counted - give N^r, in batches of B per
+ * launch chain (groups of 8 or 16 permutations, one byte per spot and permutation, as many groups as a scratch budget of 1 GiB
+ * holds, at most 64, and at most max_batch permutations when that is positive; *batch_out, may be NULL, reports B).  To HOST
+ * memory, (C, C) row-major each:
+ *   count_ge_out / count_le_out = how many of the call's permutations have N^r >= N / N^r <= N
+ *   sum_d_out / sumsq_d_out     = the float64 sums over them of d = N^r - N and of d^2, added in permutation order
+ * null_dev (may be NULL): (n_perm, C, C) int64 DEVICE array that receives every N^r.  Every count is exact; N^r does not depend on
+ * B, on max_batch, on first_perm or on the call it ran in, so split calls add up exactly; no floating-point atomics, two calls
+ * return the same bits, one host synchronisation.  Refused with a message: a shard's local graph, n >= 2^31 - 128, C outside
+ * 1 .. 64, null pointers, negative counts, and - checked on the device, reported after the call - a label outside [-1, C). */
+int fdx_label_pair_counts_dev(const fdx_graph* g, const int32_t* labels_dev, int32_t C, uint64_t seed, int64_t first_perm,
+                              int64_t n_perm, int32_t max_batch, int64_t* null_dev, int64_t* label_counts_out, int64_t* pair_out,
+                              int64_t* counts_out, int64_t* count_ge_out, int64_t* count_le_out, double* sum_d_out,
+                              double* sumsq_d_out, int32_t* batch_out, void* stream);
 /* Local indicators of spatial association over a whole graph (additive, not in the reference): per spot and column the observed
  * neighbour sum and its conditional-permutation null.  V_dev as for fdx_spatial_autocorr_dev.  DEVICE outputs, rows in the
  * caller's spot order, overwritten:
