@@ -118,15 +118,14 @@ __global__ __launch_bounds__(256) void gp_inverse_kernel(const int* __restrict__
     if (p < n) inv[perm[p]] = p;
 }
 
-// tables[b][p] = inv[pi_{r0 + b}(perm[p])] for b < nb (identity: tables[0][p] = p); perm / inv null: the caller's order
-__global__ __launch_bounds__(256) void gp_tables_kernel(const int* __restrict__ perm, const int* __restrict__ inv, int n,
-                                                        unsigned long long seed_mixed, long long r0, int wl, int wr, bool identity,
-                                                        int* __restrict__ tables) {
+// tables[b][p] = inv[pi_r(perm[p])], r = keys' element b, for b < nb (identity: tables[0][p] = p); perm / inv null: the caller's order
+__global__ __launch_bounds__(256) void gp_tables_kernel(const int* __restrict__ perm, const int* __restrict__ inv, int n, PermKeys keys,
+                                                        bool identity, int* __restrict__ tables) {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
     int at = p;
     if (!identity) {
-        const int src = ss_permute_index(ss_perm_key(seed_mixed, r0 + blockIdx.y), perm ? perm[p] : p, n, wl, wr);
+        const int src = ss_permute_index(perm_key_at(keys, blockIdx.y), perm ? perm[p] : p, n, keys.wl, keys.wr);
         at = inv ? inv[src] : src;
     }
     tables[(size_t)blockIdx.y * n + p] = at;
@@ -437,9 +436,8 @@ int gp_run(const GraphTables& t, const GeneMatrix& y, const T* data, const GpReq
     const size_t tile_bytes = (size_t)n * tg * sizeof(T);
     // grid y of the null kernel and the copy's budget bound a stripe's tiles, one tile at the least
     const int stripe_tiles = (int)std::max<size_t>(1, std::min<size_t>({(size_t)tiles_all, (size_t)65535, q.gather_bytes / tile_bytes}));
-    const long long batch_fit = std::max<long long>(1, (long long)(SCRATCH_BUDGET_BYTES / ((size_t)n * sizeof(int))));
-    const long long batch = std::max<long long>(1, std::min<long long>({q.max_batch > 0 ? q.max_batch : batch_fit, batch_fit,
-                                                                       std::max<long long>(q.n_perm, 1), 65535LL}));   // (grid y of the tables kernel)
+    // a table of n positions per permutation in flight; 65535: grid y of the tables kernel
+    const long long batch = perm_batch((long long)(SCRATCH_BUDGET_BYTES / ((size_t)n * sizeof(int))), 65535, q.max_batch, q.n_perm);
     ran->batch = (int)batch;
     ran->stripes = ceil_div(tiles_all, stripe_tiles);
 
@@ -464,9 +462,7 @@ int gp_run(const GraphTables& t, const GeneMatrix& y, const T* data, const GpReq
     }
     GraphTables pos = t;
     pos.perm = nullptr;                                         // Yt is in the graph's order: rows are positions
-    int wl, wr;
-    ss_feistel_widths(n, &wl, &wr);
-    const unsigned long long seed_mixed = ss_mix64(q.seed);
+    PermKeys keys = perm_keys(q.seed, q.first_perm, n);
     T* Yt = yt_buf.as<T>();
     int* tables = tab_buf.as<int>();
     for (int t0 = 0; t0 < tiles_all; t0 += stripe_tiles) {
@@ -477,15 +473,16 @@ int gp_run(const GraphTables& t, const GeneMatrix& y, const T* data, const GpReq
         else FDX_TRY((gp_gather_as<T, 1>(t, y, data, genes_dev, slot_dev, S, s0, tiles, Yt, st)));
         FDX_TRY(gp_moments(tg, Yt, n, s0, tiles, S, q.obs, st));
         // the observed sums: the identity table through the null kernel
-        hipLaunchKernelGGL(gp_tables_kernel, dim3((unsigned)ceil_div(n, 256), 1), dim3(256), 0, st, t.perm, inv, n, seed_mixed, 0LL, wl, wr,
-                           true, tables);
+        hipLaunchKernelGGL(gp_tables_kernel, dim3((unsigned)ceil_div(n, 256), 1), dim3(256), 0, st, t.perm, inv, n, keys, true,
+                           tables);
         FDX_CHECK_LAUNCH();
         FDX_TRY(gp_launch_null(plan, Yt, tables, pos, s0, tiles, S, 1, q.obs + 4 * (size_t)S, q.obs + 2 * (size_t)S, q.obs + 3 * (size_t)S,
                                0LL, nullptr, st));
         for (long long done = 0; done < q.n_perm; done += batch) {
             const int nb = (int)std::min<long long>(batch, q.n_perm - done);
-            hipLaunchKernelGGL(gp_tables_kernel, dim3((unsigned)ceil_div(n, 256), (unsigned)nb), dim3(256), 0, st, t.perm, inv, n, seed_mixed,
-                               q.first_perm + done, wl, wr, false, tables);
+            keys.first = q.first_perm + done;
+            hipLaunchKernelGGL(gp_tables_kernel, dim3((unsigned)ceil_div(n, 256), (unsigned)nb), dim3(256), 0, st, t.perm, inv, n, keys, false,
+                               tables);
             FDX_CHECK_LAUNCH();
             double* row = q.null + (size_t)done * 3 * S;
             FDX_TRY(gp_launch_null(plan, Yt, tables, pos, s0, tiles, S, nb, row, row + S, row + 2 * (size_t)S, 3LL * S,

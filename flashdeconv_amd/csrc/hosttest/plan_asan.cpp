@@ -1,4 +1,5 @@
-// Host-only exerciser of the schedule builders (tile_plan.cpp) and of the packed spatial-sums layout (spatial_sums.h) for the sanitizer build: `make -C flashdeconv_amd/csrc asan-host`
+// Host-only exerciser of the schedule builders (tile_plan.cpp), of the packed spatial-sums layout (spatial_sums.h) and of the
+// permutation entries' host arithmetic (perm_plan.h) for the sanitizer build: `make -C flashdeconv_amd/csrc asan-host`
 // compiles this file and tile_plan.cpp with g++ -fsanitize=address,undefined and runs it.  No HIP, no GPU.
 // (GPU AddressSanitizer is not available on the build pool; the pure-host parts of the library are what can be sanitised.)
 #include <cstdio>
@@ -6,6 +7,7 @@
 #include <random>
 #include <vector>
 
+#include "../perm_plan.h"
 #include "../spatial_sums.h"
 #include "../tile_plan.h"
 
@@ -75,8 +77,80 @@ static int check_spatial_sums(int K) {
     return mean[0] == mean[0] || m2[k - 1] != 0.0 || C[kk - 1] != 0.0 || m4[k - 1] != 0.0 ? 6 : 0;
 }
 
+// wl = b / 2, wr = b - wl with b = max(2, bit_length(n - 1))
+static int check_feistel_widths() {
+    std::vector<long long> ns = {1, 2, 3, 4, 5, (1LL << 31) - 129};
+    for (int k : {3, 16, 30})
+        for (long long d : {-1, 0, 1}) ns.push_back((1LL << k) + d);
+    for (long long n : ns) {
+        int b = 0;
+        while (b < 62 && (1LL << b) <= n - 1) ++b;                 // bit_length(n - 1): the least b with n - 1 < 2^b
+        b = b < 2 ? 2 : b;
+        int wl = -1, wr = -1;
+        ss_feistel_widths(n, &wl, &wr);
+        if (wl != b / 2 || wr != b - b / 2) return 1;
+    }
+    return 0;
+}
+
+// the clamp against its rule written out step by step, over a grid that reaches every branch; the result always lies in [1, cap]
+static int check_perm_batch() {
+    for (long long fit : {0LL, 1LL, 7LL, 512LL, 1000000LL})
+        for (long long cap : {1LL, 512LL, 65535LL})
+            for (long long max_batch : {0LL, 1LL, 5LL, 1000000LL})
+                for (long long n_perm : {0LL, 1LL, 6LL, 999LL}) {
+                    long long want = fit;
+                    if (cap < want) want = cap;
+                    if (max_batch > 0) {
+                        if (max_batch < want) want = max_batch;
+                    }
+                    if (n_perm < 1) {
+                        if (1 < want) want = 1;
+                    } else if (n_perm < want) {
+                        want = n_perm;
+                    }
+                    if (want < 1) want = 1;
+                    const long long got = perm_batch(fit, cap, max_batch, n_perm);
+                    if (got != want || got < 1 || got > cap) return 1;
+                }
+    return 0;
+}
+
+// the four slices tile [base, end) without gap or overlap; a block holding its own indices unpacks into arrays exactly as long as
+// their slices (a copy that runs over ends in a redzone); fill_empty gives n_perm, n_perm, 0, 0
+static int check_null_sums(size_t X) {
+    const size_t base = 5;
+    const NullSumsLayout L(X, base);
+    const size_t at[] = {L.count_ge, L.count_le, L.sum_d, L.sumsq_d, L.end};
+    if (L.X != X || at[0] != base) return 1;
+    for (int i = 0; i < 4; ++i)
+        if (at[i] + X != at[i + 1]) return 2;
+    std::vector<double> h(L.end), sd(X), sq(X);
+    std::vector<int64_t> ge(X), le(X);
+    for (size_t i = 0; i < h.size(); ++i) {
+        const int64_t v = (int64_t)i;
+        if (i < L.sum_d) std::memcpy(&h[i], &v, 8);
+        else h[i] = (double)i;
+    }
+    L.unpack(h.data(), ge.data(), le.data(), sd.data(), sq.data());
+    for (size_t i = 0; i < X; ++i)
+        if (ge[i] != (int64_t)(L.count_ge + i) || le[i] != (int64_t)(L.count_le + i) || sd[i] != (double)(L.sum_d + i) ||
+            sq[i] != (double)(L.sumsq_d + i))
+            return 3;
+    L.fill_empty(7, ge.data(), le.data(), sd.data(), sq.data());
+    for (size_t i = 0; i < X; ++i)
+        if (ge[i] != 7 || le[i] != 7 || sd[i] != 0.0 || sq[i] != 0.0) return 4;
+    return 0;
+}
+
 int main() {
     int bad = 0;
+    if (check_feistel_widths()) { std::printf("Feistel widths: error\n"); ++bad; }
+    if (check_perm_batch()) { std::printf("permutation batch clamp: error\n"); ++bad; }
+    for (size_t X : {(size_t)1, (size_t)16, (size_t)33 * 33}) {
+        const int rc = check_null_sums(X);
+        if (rc) { std::printf("null sums layout X=%zu: error %d\n", X, rc); ++bad; }
+    }
     for (int K : {1, 4, 33}) {
         const int rc = check_spatial_sums(K);
         if (rc) { std::printf("spatial sums layout K=%d: error %d\n", K, rc); ++bad; }

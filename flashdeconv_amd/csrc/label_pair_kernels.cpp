@@ -32,7 +32,6 @@
 #include "perm_device.h"
 
 #include <algorithm>
-#include <cstring>
 #include <vector>
 
 namespace fdx {
@@ -43,9 +42,7 @@ constexpr int LP_MAX_GROUPS = 64;        // groups of B permutations per launch 
 constexpr int LP_TARGET_WAVES = 8192;    // waves of a count launch over all its groups: the chip's 256 CUs x 32
 
 struct LpPermArgs {
-    unsigned long long seed_mixed;       // mix64(seed)
-    long long first;                     // r of the batch's element 0
-    int wl, wr;                          // widths of the Feistel halves
+    PermKeys keys;
     int batch;                           // permutations of this launch (the last group may be ragged)
 };
 
@@ -103,8 +100,7 @@ __global__ __launch_bounds__(256) void lp_stage_kernel(const unsigned char* __re
 #pragma unroll
             for (int j = 0; j < B; ++j)
                 if (j0 + j < pa.batch) {
-                    const unsigned long long key = ss_perm_key(pa.seed_mixed, pa.first + j0 + j);
-                    const unsigned c = codes[ss_permute_index(key, row, n, pa.wl, pa.wr)];
+                    const unsigned c = codes[ss_permute_index(perm_key_at(pa.keys, j0 + j), row, n, pa.keys.wl, pa.keys.wr)];
                     w[j / 4] = (w[j / 4] & ~(0xffu << (8 * (j % 4)))) | (c << (8 * (j % 4)));
                 }
         }
@@ -215,8 +211,9 @@ struct LabelPairPlan {
     int n_slices, blocks;                // blocks: grid.x of a count launch with `groups` groups
     size_t lds_bytes;
     size_t CC;
-    // result words: [obs CC | label counts C | W, sum deg^2 | flag | count_ge CC | count_le CC | sum_d CC | sumsq_d CC]
-    size_t o_counts, o_deg, o_flag, o_ge, o_le, o_sd, o_sq, words;
+    // result words: [obs CC | label counts C | W, sum deg^2 | flag | null: count_ge CC | count_le CC | sum_d CC | sumsq_d CC]
+    size_t o_counts, o_deg, o_flag, words;
+    NullSumsLayout null;
 };
 
 static int count_blocks(const LabelPairPlan& p, int groups, long long ell_rows, int max_width) {
@@ -241,20 +238,15 @@ static LabelPairPlan label_pair_plan(long long n, int C, long long n_perm, int m
     p.ld = round_up(n + 1, 64);
     p.n_slices = ceil_div(n, 64);
     const size_t per_group = (size_t)p.ld * p.B + (size_t)p.B * p.CC * sizeof(long long);
-    long long groups = (long long)std::max<size_t>(1, std::min<size_t>(LP_MAX_GROUPS, SCRATCH_BUDGET_BYTES / per_group));
-    long long batch = groups * p.B;
-    if (max_batch > 0) batch = std::min<long long>(batch, max_batch);
-    batch = std::max<long long>(1, std::min<long long>(batch, std::max<long long>(1, n_perm)));
+    const long long fit_groups = (long long)std::max<size_t>(1, SCRATCH_BUDGET_BYTES / per_group);   // a whole group at the least
+    const long long batch = perm_batch(fit_groups * p.B, (long long)LP_MAX_GROUPS * p.B, max_batch, n_perm);
     p.batch = (int)batch;
     p.groups = ceil_div(batch, p.B);
     p.o_counts = p.CC;
     p.o_deg = p.o_counts + C;
     p.o_flag = p.o_deg + 2;
-    p.o_ge = p.o_flag + 1;
-    p.o_le = p.o_ge + p.CC;
-    p.o_sd = p.o_le + p.CC;
-    p.o_sq = p.o_sd + p.CC;
-    p.words = p.o_sq + p.CC;
+    p.null = NullSumsLayout(p.CC, p.o_flag + 1);
+    p.words = p.null.end;
     return p;
 }
 
@@ -290,20 +282,19 @@ static int launch_label_pairs(const LabelPairPlan& p, const fdx_graph* graph, co
     FDX_CHECK_LAUNCH();
     if (n_perm <= 0) return 0;
 
-    pa.seed_mixed = ss_mix64(seed);
-    ss_feistel_widths(n, &pa.wl, &pa.wr);
+    pa.keys = perm_keys(seed, first_perm, n);
     for (long long done = 0; done < n_perm; done += p.batch) {
         const int b = (int)std::min<long long>(p.batch, n_perm - done);     // the last batch may be ragged
         const int groups = ceil_div(b, B);
-        pa.first = first_perm + done;
+        pa.keys.first = first_perm + done;
         pa.batch = b;
         hipLaunchKernelGGL((lp_stage_kernel<B, false>), dim3(ceil_div(p.ld, 256), groups), dim3(256), 0, st, codes, g.perm, n, p.ld,
                            Lr, pa);
         FDX_CHECK_LAUNCH();
         FDX_TRY(launch_count<B>(p, groups, count_blocks(p, groups, graph->ell_rows, graph->max_deg), Lr, g, C, acc, st));
         hipLaunchKernelGGL(lp_accum_kernel, dim3(ceil_div((long long)p.CC, 256)), dim3(256), 0, st, acc, b, (long long)p.CC, obs,
-                           null_dev ? null_dev + (size_t)done * p.CC : nullptr, out + p.o_ge, out + p.o_le,
-                           reinterpret_cast<double*>(out + p.o_sd), reinterpret_cast<double*>(out + p.o_sq));
+                           null_dev ? null_dev + (size_t)done * p.CC : nullptr, out + p.null.count_ge, out + p.null.count_le,
+                           reinterpret_cast<double*>(out + p.null.sum_d), reinterpret_cast<double*>(out + p.null.sumsq_d));
         FDX_CHECK_LAUNCH();
     }
     return 0;
@@ -336,10 +327,7 @@ int fdx_label_pair_counts_dev(const fdx_graph* g, const int32_t* labels_dev, int
     if (t.n == 0) {                                     // nothing to count: every N^r equals N = 0
         std::fill(label_counts_out, label_counts_out + C, (int64_t)0);
         std::fill(pair_out, pair_out + CC, (int64_t)0);
-        std::fill(count_ge_out, count_ge_out + CC, n_perm);
-        std::fill(count_le_out, count_le_out + CC, n_perm);
-        std::fill(sum_d_out, sum_d_out + CC, 0.0);
-        std::fill(sumsq_d_out, sumsq_d_out + CC, 0.0);
+        NullSumsLayout(CC, 0).fill_empty(n_perm, count_ge_out, count_le_out, sum_d_out, sumsq_d_out);
         return 0;
     }
     const LabelPairPlan plan = label_pair_plan(t.n, C, n_perm, max_batch);
@@ -367,10 +355,7 @@ int fdx_label_pair_counts_dev(const fdx_graph* g, const int32_t* labels_dev, int
     std::copy(host.begin() + plan.o_counts, host.begin() + plan.o_counts + C, label_counts_out);
     counts_out[1] = host[plan.o_deg];
     counts_out[2] = host[plan.o_deg + 1];
-    std::copy(host.begin() + plan.o_ge, host.begin() + plan.o_ge + CC, count_ge_out);
-    std::copy(host.begin() + plan.o_le, host.begin() + plan.o_le + CC, count_le_out);
-    std::memcpy(sum_d_out, host.data() + plan.o_sd, CC * sizeof(double));
-    std::memcpy(sumsq_d_out, host.data() + plan.o_sq, CC * sizeof(double));
+    plan.null.unpack(host.data(), count_ge_out, count_le_out, sum_d_out, sumsq_d_out);
     return 0;
 }
 

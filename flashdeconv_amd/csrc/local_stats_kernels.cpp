@@ -37,12 +37,10 @@ namespace fdx {
 constexpr int LS_KC = 8;                 // columns per walk of a list / per evaluation of the draws
 constexpr int LS_CAP_BLOCKS = 1 << 18;   // cap of the null kernel's grid (4 spots per workgroup per stride)
 
-// what identifies the conditional permutations of a launch
+// the conditional permutations of a launch: the first n_perm of keys
 struct LsPermArgs {
-    unsigned long long seed_mixed;   // mix64(seed)
-    long long first;                 // r of the launch's first permutation
+    PermKeys keys;
     int n_perm;
-    int wl, wr;                      // widths of the Feistel halves
 };
 
 __host__ __device__ __forceinline__ unsigned long long ls_cond_key(unsigned long long key_r, int spot) {
@@ -122,12 +120,14 @@ __global__ __launch_bounds__(256) void ls_cond_null_kernel(const double* __restr
             }
             for (long long r0 = 0; r0 < pa.n_perm; r0 += 64) {                     // 64-bit: n_perm may be 2^31 - 1
                 const bool valid = r0 + lane < pa.n_perm;
+                PermKeys pass = pa.keys;                                           // the 64 permutations of this pass: their first
+                pass.first += r0;                                                  // is uniform, one scalar addition
                 double acc[LS_KC];
 #pragma unroll
                 for (int kk = 0; kk < LS_KC; ++kk) acc[kk] = 0.0;
                 if (valid) {
-                    const unsigned long long key = ls_cond_key(ss_perm_key(pa.seed_mixed, pa.first + r0 + lane), spot);
-                    ls_draw(key, spot, n, dg, pa.wl, pa.wr, [&](int, int c) {
+                    const unsigned long long key = ls_cond_key(perm_key_at(pass, lane), spot);
+                    ls_draw(key, spot, n, dg, pa.keys.wl, pa.keys.wr, [&](int, int c) {
                         const double* row = V + (size_t)c * ldv;
 #pragma unroll
                         for (int kk = 0; kk < LS_KC; ++kk) acc[kk] += row[k0 + kk < K ? k0 + kk : K - 1];
@@ -207,11 +207,7 @@ int fdx_local_stats_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, in
                        plan.n_slices, K, nbr_sum_dev, deg_dev);
     FDX_CHECK_LAUNCH();
     if (n_perm > 0) {
-        LsPermArgs pa;
-        pa.seed_mixed = ss_mix64(seed);
-        pa.first = first_perm;
-        pa.n_perm = (int)n_perm;
-        ss_feistel_widths(t.n, &pa.wl, &pa.wr);
+        const LsPermArgs pa{perm_keys(seed, first_perm, t.n), (int)n_perm};
         hipLaunchKernelGGL(ls_cond_null_kernel, dim3(std::min(LS_CAP_BLOCKS, ceil_div(t.n, 4))), dim3(256), 0, st, V_dev, ldv, t.n, K,
                            deg_dev, nbr_sum_dev, pa, count_ge_dev, count_le_dev, sum_d_dev, sumsq_d_dev);
         FDX_CHECK_LAUNCH();
@@ -230,10 +226,9 @@ int fdx_conditional_indices_dev(uint64_t seed, int64_t r, int64_t spot, int64_t 
     FDX_REQUIRE(count >= 0 && count <= n - 1, "fdx_conditional_indices_dev: count must be between 0 and n - 1");
     FDX_REQUIRE(count == 0 || out_dev, "fdx_conditional_indices_dev: null argument");
     if (count == 0) return 0;
-    int wl, wr;
-    ss_feistel_widths((int)n, &wl, &wr);
+    const PermKeys keys = perm_keys(seed, r, n);
     hipLaunchKernelGGL(ls_cond_indices_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream,
-                       ls_cond_key(ss_perm_key(ss_mix64(seed), r), (int)spot), (int)spot, (int)n, (int)count, wl, wr, out_dev);
+                       ls_cond_key(perm_key_at(keys, 0), (int)spot), (int)spot, (int)n, (int)count, keys.wl, keys.wr, out_dev);
     FDX_CHECK_LAUNCH();
     return 0;
 }

@@ -1,10 +1,12 @@
-// The keyed bijection of [0, n) that the permutation kernels evaluate instead of reading an index array (internal; one copy for
-// spatial_stats_kernels.cpp and local_stats_kernels.cpp).  utils/spatial_stats.py:permutation_indices is its definition: an
-// unbalanced Feistel network of 8 rounds on b = max(2, bit_length(n - 1)) bits (left half b / 2 bits, right half the rest, the
-// widths swap every round), the round function the splitmix64 finaliser, values >= n walked along their cycle until they fall
-// below n.
+// The keyed bijection of [0, n) that the permutation kernels evaluate instead of reading an index array, and the keys of a
+// launch's permutations (internal; the one copy of what a kernel evaluates - the host arithmetic beside it is perm_plan.h's).
+// utils/_permutation.py:permutation_indices is its definition: an unbalanced Feistel network of 8 rounds on
+// b = max(2, bit_length(n - 1)) bits (left half b / 2 bits, right half the rest, the widths swap every round), the round function
+// the splitmix64 finaliser, values >= n walked along their cycle until they fall below n.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "perm_plan.h"
 
 namespace fdx {
 
@@ -21,6 +23,23 @@ __host__ __device__ __forceinline__ unsigned long long ss_mix64(unsigned long lo
 // permutation r of a seed has the key mix64(seed_mixed + (r + 1) * golden), seed_mixed = mix64(seed)
 __host__ __device__ __forceinline__ unsigned long long ss_perm_key(unsigned long long seed_mixed, long long r) {
     return ss_mix64(seed_mixed + ((unsigned long long)r + 1ULL) * 0x9e3779b97f4a7c15ULL);
+}
+
+// What identifies the permutations of a launch: element j is permutation r = first + j of the seed.
+struct PermKeys {
+    unsigned long long seed_mixed;   // mix64(seed)
+    long long first;                 // r of element 0
+    int wl, wr;                      // widths of the Feistel halves of [0, n): wl = b / 2, wr = b - wl
+};
+
+inline PermKeys perm_keys(unsigned long long seed, long long first, long long n) {
+    PermKeys k{ss_mix64(seed), first, 0, 0};
+    ss_feistel_widths(n, &k.wl, &k.wr);
+    return k;
+}
+
+__host__ __device__ __forceinline__ unsigned long long perm_key_at(const PermKeys& k, long long j) {
+    return ss_perm_key(k.seed_mixed, k.first + j);
 }
 
 // pi(i) for i < n < 2^31: x = (L << wr) | R; a round sends (L, R) to (R, L ^ F(R)) and swaps the widths; 8 rounds restore them
@@ -42,15 +61,6 @@ __device__ __forceinline__ int ss_permute_index(unsigned long long key, int i, i
         x = (L << wr) | R;
     } while (x >= (unsigned)n);
     return (int)x;
-}
-
-// b = max(2, bit_length(n - 1)), split into the Feistel halves
-inline void ss_feistel_widths(long long n, int* wl, int* wr) {
-    int b = 0;
-    for (long long v = n - 1; v > 0; v >>= 1) ++b;
-    b = b < 2 ? 2 : b;
-    *wl = b / 2;
-    *wr = b - b / 2;
 }
 
 }  // namespace fdx

@@ -29,7 +29,7 @@
 //
 // pi_r is a keyed bijection of [0, n): an unbalanced Feistel network of 8 rounds on b = max(2, bit_length(n - 1)) bits (left half
 // b / 2 bits, right half the rest, the widths swap every round), the round function the splitmix64 finaliser, values >= n walked
-// along their cycle until they fall below n (perm_device.h).  utils/spatial_stats.py:permutation_indices is its definition.
+// along their cycle until they fall below n (perm_device.h).  utils/_permutation.py:permutation_indices is its definition.
 #include "fdx_graph.h"
 #include "fdx_internal.h"
 #include "fdx_kernels.h"
@@ -54,11 +54,9 @@ __device__ __forceinline__ void wave_lds_handoff() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// what identifies the permutations of a launch: permutation r has the key mix64(seed_mixed + (r + 1) * golden)
+// the permutations of a centre launch (batch element j is keys' element j) and where their planes go
 struct SsPermArgs {
-    unsigned long long seed_mixed;   // mix64(seed)
-    long long first;                 // r of batch element 0
-    int wl, wr;                      // widths of the Feistel halves: wl = b / 2, wr = b - wl
+    PermKeys keys;
     long long plane_stride;          // doubles between the planes of two batch elements (K * ld)
 };
 
@@ -100,7 +98,7 @@ __global__ __launch_bounds__(256) void ss_reduce_kernel(const T* __restrict__ pa
 
 // Z[k][p] = V[perm[p]][k] - mean[k] for p < n, 0 for n <= p < ld (n_slices_ld = ld / 64 slices are written);
 // m2_partials[block][k] = the block's share of sum_p Z[k][p]^2.
-// PERMUTED: batch element blockIdx.y reads row pi_r(perm[p]) instead, r = pa.first + blockIdx.y, into its own planes; whole rows of
+// PERMUTED: batch element blockIdx.y reads row pi_r(perm[p]) instead, r = pa.keys.first + blockIdx.y, into its own planes; whole rows of
 // V are still read as segments (the type-major planes are never gathered from); no m2 (it does not change) and no m2 tile.
 template <bool PERMUTED>
 __global__ __launch_bounds__(256) void ss_centre_kernel(const double* __restrict__ V, long long ldv, const double* __restrict__ mean,
@@ -116,7 +114,7 @@ __global__ __launch_bounds__(256) void ss_centre_kernel(const double* __restrict
     double* m2w = m2_all + (size_t)wib * K;
     unsigned long long key = 0;
     if constexpr (PERMUTED) {
-        key = ss_perm_key(pa.seed_mixed, pa.first + blockIdx.y);
+        key = perm_key_at(pa.keys, blockIdx.y);
         Z += (size_t)blockIdx.y * pa.plane_stride;
     } else {
         for (int k = lane; k < K; k += 64) m2w[k] = 0.0;
@@ -126,7 +124,7 @@ __global__ __launch_bounds__(256) void ss_centre_kernel(const double* __restrict
         wave_lds_handoff();                                        // the previous slice's readers of row_s are done
         int row = p < n ? (perm ? perm[p] : (int)p) : -1;
         if constexpr (PERMUTED)
-            if (row >= 0) row = ss_permute_index(key, row, n, pa.wl, pa.wr);
+            if (row >= 0) row = ss_permute_index(key, row, n, pa.keys.wl, pa.keys.wr);
         row_s[wib][lane] = row;
         for (int k0 = 0; k0 < K; k0 += SS_KT) {
             const int kc = K - k0 < SS_KT ? K - k0 : SS_KT;
@@ -464,10 +462,7 @@ static SpatialPermPlan spatial_perm_plan(long long n, int K, long long n_perm, i
     p.cross_part_doubles = (size_t)p.s.cross_blocks * KK;
     // per permutation in flight: its Z and lag planes, its cross partials and, where the caller keeps no null, its C_r
     const size_t per_perm = (2 * p.plane_doubles + p.cross_part_doubles + KK) * sizeof(double);
-    long long B = (long long)std::max<size_t>(1, SCRATCH_BUDGET_BYTES / per_perm);
-    B = std::min<long long>(B, SS_PERM_MAX_BATCH);
-    if (max_batch > 0) B = std::min<long long>(B, max_batch);
-    B = std::max<long long>(1, std::min<long long>(B, std::max<long long>(1, n_perm)));
+    const long long B = perm_batch((long long)(SCRATCH_BUDGET_BYTES / per_perm), SS_PERM_MAX_BATCH, max_batch, n_perm);
     p.batch = (int)B;
     p.part_doubles = std::max(p.s.partials_doubles, (size_t)B * p.cross_part_doubles);
     p.null_doubles = own_null ? (size_t)B * KK : 0;
@@ -501,16 +496,13 @@ static int launch_spatial_perm(const SpatialPermPlan& p, const double* V, long l
     FDX_HIP(hipMemsetAsync(count_ge, 0, (s.sums.perm_doubles - s.sums.count_ge) * sizeof(double), st));   // the counts and the sums of d
     if (n_perm <= 0) return 0;
 
-    SsPermArgs pa;
-    pa.seed_mixed = ss_mix64(seed);
-    ss_feistel_widths(n, &pa.wl, &pa.wr);
-    pa.plane_stride = (long long)p.plane_doubles;
+    SsPermArgs pa{perm_keys(seed, first_perm, n), (long long)p.plane_doubles};
     const size_t lds = (size_t)4 * 64 * SS_KS * sizeof(double);
     FDX_HIP(hipFuncSetAttribute((const void*)ss_centre_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int tiles = s.pair_tiles_1d * s.pair_tiles_1d;
     for (long long done = 0; done < n_perm; done += B) {
         const int b = (int)std::min<long long>(B, n_perm - done);       // the last batch may be ragged
-        pa.first = first_perm + done;
+        pa.keys.first = first_perm + done;
         hipLaunchKernelGGL(ss_centre_kernel<true>, dim3(s.centre_blocks, b), dim3(256), lds, st, V, ldv, mean, g.perm, n,
                            (int)(s.ld / 64), K, Zall, s.ld, (double*)nullptr, pa);
         FDX_CHECK_LAUNCH();
@@ -580,11 +572,9 @@ int fdx_spatial_perm_dev(const fdx_graph* g, const double* V_dev, int64_t ldv, i
     counts_out[1] = counts_out[2] = 0;
     if (batch_out) *batch_out = 0;
     if (t.n == 0) {                                     // nothing to permute: every C_r equals C_obs = 0
-        SpatialSumsLayout(K).fill_empty(mean_out, m2_out, C_out, m4_out);
-        std::fill(count_ge_out, count_ge_out + KK, n_perm);
-        std::fill(count_le_out, count_le_out + KK, n_perm);
-        std::fill(sum_d_out, sum_d_out + KK, 0.0);
-        std::fill(sumsq_d_out, sumsq_d_out + KK, 0.0);
+        const SpatialSumsLayout empty(K);
+        empty.fill_empty(mean_out, m2_out, C_out, m4_out);
+        empty.NullSumsLayout::fill_empty(n_perm, count_ge_out, count_le_out, sum_d_out, sumsq_d_out);
         if (null_dev && n_perm > 0) FDX_HIP(hipMemsetAsync(null_dev, 0, (size_t)n_perm * KK * sizeof(double), st));
         return 0;
     }
@@ -607,10 +597,9 @@ int fdx_permutation_indices_dev(uint64_t seed, int64_t r, int64_t n, int32_t* ou
     FDX_REQUIRE(r >= 0, "fdx_permutation_indices_dev: r must not be negative");
     FDX_REQUIRE(n == 0 || out_dev, "fdx_permutation_indices_dev: null argument");
     if (n == 0) return 0;
-    int wl, wr;
-    ss_feistel_widths((int)n, &wl, &wr);
-    hipLaunchKernelGGL(ss_perm_indices_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                       ss_perm_key(ss_mix64(seed), r), (int)n, wl, wr, out_dev);
+    const PermKeys keys = perm_keys(seed, r, n);
+    hipLaunchKernelGGL(ss_perm_indices_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, perm_key_at(keys, 0), (int)n,
+                       keys.wl, keys.wr, out_dev);
     FDX_CHECK_LAUNCH();
     return 0;
 }

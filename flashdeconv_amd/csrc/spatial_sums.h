@@ -8,26 +8,24 @@
 #include <cstdint>
 #include <cstring>
 
+#include "perm_plan.h"
+
 namespace fdx {
 
 // Offsets in doubles from the start of the block, for K columns (KK = K * K):
 //   observed     [mean K | m2 K | C KK | sum deg, sum deg^2 as int64]                                        observed_doubles
-//   permutation  the observed block, then [m4 K | count_ge KK int64 | count_le KK int64 | sum_d KK | sumsq_d KK]   perm_doubles
-struct SpatialSumsLayout {
+//   permutation  the observed block, then [m4 K | the base's count_ge, count_le, sum_d, sumsq_d of KK each]        perm_doubles
+struct SpatialSumsLayout : NullSumsLayout {
     size_t K, KK;
-    size_t mean = 0, m2 = 0, C = 0, deg_sums = 0, observed_doubles = 0;
-    size_t m4 = 0, count_ge = 0, count_le = 0, sum_d = 0, sumsq_d = 0, perm_doubles = 0;
+    size_t mean = 0, m2 = 0, C = 0, deg_sums = 0, observed_doubles = 0, m4 = 0, perm_doubles = 0;
     explicit SpatialSumsLayout(int k = 0) : K((size_t)k), KK((size_t)k * k) {
         m2 = mean + K;
         C = m2 + K;
         deg_sums = C + KK;
         observed_doubles = deg_sums + 2;
         m4 = observed_doubles;
-        count_ge = m4 + K;
-        count_le = count_ge + KK;
-        sum_d = count_le + KK;
-        sumsq_d = sum_d + KK;
-        perm_doubles = sumsq_d + KK;
+        NullSumsLayout::operator=(NullSumsLayout(KK, m4 + K));
+        perm_doubles = end;
     }
     // A downloaded block into the caller's arrays.  deg_sums_out: two int64.  C_out null: not wanted.  m4_out null: an observed
     // block, the five permutation arrays are not touched.
@@ -40,10 +38,7 @@ struct SpatialSumsLayout {
         std::memcpy(deg_sums_out, h + deg_sums, 2 * sizeof(int64_t));
         if (!m4_out) return;
         std::copy(h + m4, h + m4 + K, m4_out);
-        std::memcpy(count_ge_out, h + count_ge, KK * sizeof(int64_t));
-        std::memcpy(count_le_out, h + count_le, KK * sizeof(int64_t));
-        std::copy(h + sum_d, h + sum_d + KK, sum_d_out);
-        std::copy(h + sumsq_d, h + sumsq_d + KK, sumsq_d_out);
+        NullSumsLayout::unpack(h, count_ge_out, count_le_out, sum_d_out, sumsq_d_out);
     }
     // The answers without spots: no mean, zero sums (C_out, m4_out may be null).
     void fill_empty(double* mean_out, double* m2_out, double* C_out, double* m4_out = nullptr) const {

@@ -52,7 +52,8 @@ import numpy as np
 from .. import _lib
 from ._device import check_count, device_of, matrix_on_device, resolved_graph
 from .spatial_genes import _benjamini_hochberg, _check_n_top, _check_Y_rows
-from .spatial_stats import _NULL_CALL_BYTES, _permutation_seed
+from ._permutation import (_NULL_CALL_BYTES, _permutation_seed, check_permutation_counts, null_moments, p_from_count,
+                           permutation_chunks)
 
 __all__ = ["spatial_gene_permutation_test", "gene_permutation_sums", "assemble_gene_permutation", "merge_null_counts", "check_request",
            "OBS_PLANES", "NULL_PLANES", "ROUTES", "GENE_TILE"]
@@ -93,8 +94,7 @@ def check_request(Y_shape, genes=None, n_permutations=0, first_perm=0, max_batch
         values, counts = np.unique(a, return_counts=True)
         if values.size != a.size:
             raise ValueError(f"genes lists the gene index {int(values[counts > 1][0])} twice")
-    R = check_count("n_permutations", n_permutations)
-    first, batch = check_count("first_perm", first_perm), check_count("max_batch", max_batch)
+    R, first, batch = check_permutation_counts(n_permutations, first_perm, max_batch)
     lds = 0 if max_lds_bytes is None else check_count("max_lds_bytes", max_lds_bytes, 1)
     gather = 0 if max_gather_bytes is None else check_count("max_gather_bytes", max_gather_bytes, 1)
     return np.ascontiguousarray(a, dtype=np.int32), R, first, batch, lds, gather
@@ -177,12 +177,12 @@ def assemble_gene_permutation(n, W, u, q, D, H, P, ymin, ymax, null=None, counts
     if R < 1:
         return out
     nan = np.float64(np.nan)
-    out["p_sim"] = np.where(dead, nan, (1.0 + counts["count_ge"]) / (R + 1.0))
-    out["p_sim_less"] = np.where(dead, nan, (1.0 + counts["count_le"]) / (R + 1.0))
-    out["gearys_p_sim"] = np.where(dead, nan, (1.0 + counts["count_c_le"]) / (R + 1.0))
+    ge, le, c_le, s, sq = (np.asarray(counts[k], dtype=np.float64) for k in ("count_ge", "count_le", "count_c_le", "sum_i", "sumsq_i"))
+    out["p_sim"] = np.where(dead, nan, p_from_count(np, ge, R))
+    out["p_sim_less"] = np.where(dead, nan, p_from_count(np, le, R))
+    out["gearys_p_sim"] = np.where(dead, nan, p_from_count(np, c_le, R))
     with np.errstate(divide="ignore", invalid="ignore"):
-        mean = counts["sum_i"] / R
-        std = np.sqrt(np.maximum(counts["sumsq_i"] / R - mean * mean, 0.0))
+        mean, std = null_moments(np, s, sq, R)                  # of I_r itself, not of a difference: z_sim keeps its own form
         out["null_mean"] = np.where(dead, nan, mean)
         out["null_std"] = np.where(dead, nan, std)
         out["z_sim"] = np.where(dead | ~(std > 0), nan, (I - mean) / np.where(std > 0, std, 1.0))
@@ -214,7 +214,7 @@ def _sums_on_graph(Y, g, n, G, genes, seed, first, R, max_batch, max_lds, max_ga
     device_out = _lib.is_cuda_tensor(Y) and return_null
     S = genes.shape[0]
     chunk = max(1, min(R, _NULL_CALL_BYTES // (24 * S)))        # a call's null: what is copied to the host and counted in one piece
-    merged, batches, done = None, [0], 0
+    merged, batches = None, [0]
     with torch.cuda.device(device):
         stream = _lib.current_stream(device)
         obs = torch.empty((len(OBS_PLANES), S), dtype=torch.float64, device=device)
@@ -222,8 +222,7 @@ def _sums_on_graph(Y, g, n, G, genes, seed, first, R, max_batch, max_lds, max_ga
         null_dev = torch.empty((R if device_out else min(chunk, R), 3, S), dtype=torch.float64, device=device)
         null_host = np.empty((R, 3, S)) if return_null and not device_out else None
         with matrix_on_device(Y, device) as m:
-            while True:                                         # (one call even without permutations: the observed sums)
-                cnt = min(chunk, R - done)
+            for done, cnt in permutation_chunks(R, chunk):      # (one call even without permutations: the observed sums)
                 part = null_dev[done:done + cnt] if device_out else null_dev[:cnt]
                 counts, info = _one_call(lib, g, m, n, G, genes, seed, first + done, cnt, max_batch, max_lds, max_gather, obs, part, stream)
                 if done == 0:
@@ -238,9 +237,6 @@ def _sums_on_graph(Y, g, n, G, genes, seed, first, R, max_batch, max_lds, max_ga
                     if null_host is not None:
                         null_host[done:done + cnt] = block
                     merged = merge_null_counts(merged, out["n"], out["W"], *(out[name] for name in OBS_PLANES), block)
-                done += cnt
-                if done >= R:
-                    break
     out.update(n_permutations=R, batch=max(batches), counts=merged)
     if return_null:
         out["null"] = null_dev if device_out else null_host

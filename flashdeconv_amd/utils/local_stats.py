@@ -47,8 +47,9 @@ import ctypes
 import numpy as np
 
 from .. import _lib
-from ._device import check_count, check_values, device_of, resolved_graph, values_on_device
-from .spatial_stats import _GOLDEN, _keyed_bijection, _mix64_int, _permutation_seed
+from ._device import check_values, device_of, resolved_graph, values_on_device
+from ._permutation import (_GOLDEN, _keyed_bijection, _mix64_int, _permutation_seed, check_permutation_counts, permutation_key,
+                           rank_against_null)
 
 __all__ = ["local_spatial_statistics", "local_sums", "assemble_local", "conditional_indices"]
 
@@ -66,8 +67,7 @@ def conditional_indices(seed, r, spot, n, count):
         raise ValueError(f"spot must be in [0, n) and n below 2^31 - 128, got spot = {spot}, n = {n}")
     if not 0 <= count <= n - 1:
         raise ValueError(f"count must be in [0, n - 1] = [0, {n - 1}], got {count}")
-    key_r = _mix64_int(_mix64_int(seed) + (r + 1) * _GOLDEN)
-    key = _mix64_int(key_r + (spot + 1) * _GOLDEN)
+    key = _mix64_int(permutation_key(seed, r) + (spot + 1) * _GOLDEN)
     c = _keyed_bijection(key, np.arange(count + 1, dtype=np.uint64), n)
     return c[c != spot][:count]
 
@@ -75,7 +75,7 @@ def conditional_indices(seed, r, spot, n, count):
 def _assemble(xp, V, S, deg, mean, m2, n, W, perm):
     """The assembly in the array namespace ``xp`` (numpy, or torch on the device of the arrays): the same expressions in the same
     order for both.  Divisors are 0-d arrays of the namespace, never Python scalars: torch divides by a host scalar through its
-    reciprocal, which is not the quotient NumPy forms."""
+    reciprocal, which is not the quotient NumPy forms.  The ranking is ``_permutation.rank_against_null``."""
     nan = float("nan")
     nf, Wf = float(n), float(W)
 
@@ -100,19 +100,13 @@ def _assemble(xp, V, S, deg, mean, m2, n, W, perm):
     if perm is None:
         return out
     ge, le, sd, sq, R = perm
-    Rf = float(R)
     isolated = degf == 0
-    greater = xp.where(isolated, nan, (1.0 + ge) / c(Rf + 1.0))
-    less = xp.where(isolated, nan, (1.0 + le) / c(Rf + 1.0))
-    p = xp.where(isolated, nan, xp.minimum(greater * 0.0 + 1.0, 2.0 * xp.minimum(greater, less)))
-    mean_d = sd / c(Rf)
-    var_d = xp.maximum(sq / c(Rf) - mean_d * mean_d, sq * 0.0)
-    std_d = xp.sqrt(var_d)
-    spread = std_d > 0
-    z_sim = xp.where(isolated | ~spread, nan, -mean_d / xp.where(spread, std_d, std_d * 0.0 + 1.0))
+    greater, less, p, _, _, z_sim = rank_against_null(xp, ge, le, sd, sq, R)
     own = xp.where(Z > 0, greater, xp.where(Z < 0, less, greater * 0.0 + 1.0))
-    out.update({"n_permutations": int(R), "p_greater": greater, "p_less": less, "p_value": p, "z_sim": z_sim,
-                "local_i_p_greater": xp.where(isolated, nan, own)})
+    z_sim = xp.where(xp.isfinite(sq), z_sim, nan)                  # an overflowed sum of squares has no deviation to divide by
+    out.update({"n_permutations": int(R)})
+    out.update({k: xp.where(isolated, nan, v) for k, v in (("p_greater", greater), ("p_less", less), ("p_value", p),
+                                                           ("z_sim", z_sim), ("local_i_p_greater", own))})
     return out
 
 
@@ -189,7 +183,7 @@ def _local_calls(values, g, seed, first_perm, n_perm):
 
 def _device_sums(values, graph, seed, first_perm, n_permutations):
     n, _ = check_values(values)
-    n_perm, first_perm = check_count("n_permutations", n_permutations), check_count("first_perm", first_perm)
+    n_perm, first_perm, _ = check_permutation_counts(n_permutations, first_perm)
     if n_perm >= 1 << 31:
         raise ValueError(f"n_permutations must be below 2^31, got {n_perm}")
     seed = _permutation_seed(seed)

@@ -46,7 +46,7 @@ import numpy as np
 
 from .. import _lib
 from ._device import check_count, device_of, resolved_graph
-from .spatial_stats import _permutation_seed
+from ._permutation import _permutation_seed, check_permutation_counts, rank_against_null
 
 __all__ = ["neighborhood_enrichment", "label_pair_counts", "join_count_moments", "assemble_enrichment", "MAX_LABELS"]
 
@@ -136,14 +136,10 @@ def assemble_enrichment(count, label_counts, n, W, sum_deg_sq, count_ge=None, co
         if any(a.shape != (C, C) for a in arrs):
             raise ValueError(f"the counts and sums must be (C, C) = {(C, C)}, got shapes {[a.shape for a in arrs]}")
         ge, le, sd, sq = (a.astype(np.float64) for a in arrs)
-        greater = (1.0 + ge) / (R + 1.0)
-        less = (1.0 + le) / (R + 1.0)
-        mean_d = sd / R
-        null_std = np.sqrt(np.maximum(sq / R - mean_d * mean_d, 0.0))
         with np.errstate(divide="ignore", invalid="ignore"):
-            z_sim = np.where(null_std > 0, -mean_d / np.where(null_std > 0, null_std, 1.0), np.nan)
-        out.update({"p_greater": greater, "p_less": less, "p_value": np.minimum(1.0, 2.0 * np.minimum(greater, less)),
-                    "null_mean": cf + mean_d, "null_std": null_std, "z_sim": z_sim, "n_permutations": R})
+            greater, less, p, mean_d, null_std, z_sim = rank_against_null(np, ge, le, sd, sq, R)
+        out.update({"p_greater": greater, "p_less": less, "p_value": p, "null_mean": cf + mean_d, "null_std": null_std,
+                    "z_sim": z_sim, "n_permutations": R})
     return out
 
 
@@ -220,8 +216,7 @@ def label_pair_counts(labels, graph, n_labels=None, seed=0, first_perm=0, n_perm
     a scipy sparse adjacency, as ``spatial_autocorrelation`` takes it.  Every count is exact and depends neither on ``max_batch``
     nor on how a range of permutations is split into calls.  Everything checkable is checked before the GPU is touched."""
     n, labels, C = check_labels(labels, n_labels)
-    n_perm = check_count("n_permutations", n_permutations)
-    first_perm, max_batch = check_count("first_perm", first_perm), check_count("max_batch", max_batch)
+    n_perm, first_perm, max_batch = check_permutation_counts(n_permutations, first_perm, max_batch)
     return_null = _check_flag("return_null", return_null)
     seed = _permutation_seed(seed)
     with resolved_graph(graph, n) as g:

@@ -19,7 +19,7 @@ bits.  ``assemble`` forms the statistics from them on the host.  Entries whose d
 Significance without the normality assumption (``spatial_permutation_test``): the rows of ``V`` are reassigned to the spots at
 random, ``V_pi[i] = V[pi_r(i)]``, and ``C_r = Z_pi' (A Z_pi)`` is recomputed for r = 0 .. R - 1 (``fdx_spatial_perm_dev``; mean and
 m2 do not change).  ``pi_r`` is a keyed bijection of [0, n) evaluated inside the kernels - no index array, no host random stream -
-and ``permutation_indices`` below is its definition, in NumPy integer arithmetic::
+and ``permutation_indices`` (utils/_permutation.py) is its definition, in NumPy integer arithmetic::
 
     p_greater_ab = (1 + #{r: C_r,ab >= C_ab}) / (R + 1)      p_less likewise with <=      p_value = min(1, 2 min(greater, less))
     z_sim_ab     = (cross_ab - mean_r cross_r,ab) / std_r cross_r,ab                      (std with ddof = 0)
@@ -33,14 +33,11 @@ import numpy as np
 
 from .. import _lib
 from ._device import check_count, check_values, device_of, resolved_graph, values_on_device
+from ._permutation import (_NULL_CALL_BYTES, _permutation_seed, check_permutation_counts, permutation_chunks,
+                           permutation_indices, rank_against_null)
 
 __all__ = ["spatial_autocorrelation", "spatial_sums", "assemble", "spatial_permutation_test", "spatial_permutation_sums",
            "permutation_indices", "randomization_variance", "assemble_permutation"]
-
-_MASK64 = (1 << 64) - 1
-_GOLDEN = 0x9e3779b97f4a7c15
-_FEISTEL_ROUNDS = 8
-_NULL_CALL_BYTES = 256 << 20          # return_null on host arrays: the device holds this much of the null per call
 
 
 def assemble(n, W, sum_deg_sq, m2, C):
@@ -79,58 +76,6 @@ def assemble(n, W, sum_deg_sq, m2, C):
         z = np.full(K, nan)
     return {"cross": cross, "morans_i": morans, "expected_i": np.float64(expected), "variance_i": np.float64(variance),
             "z_score": z}
-
-
-def _mix64(x):
-    """The splitmix64 finaliser on a uint64 array (arithmetic modulo 2^64)."""
-    x = x ^ (x >> np.uint64(30))
-    x = x * np.uint64(0xbf58476d1ce4e5b9)
-    x = x ^ (x >> np.uint64(27))
-    x = x * np.uint64(0x94d049bb133111eb)
-    return x ^ (x >> np.uint64(31))
-
-
-def _mix64_int(x):
-    return int(_mix64(np.array([x & _MASK64], dtype=np.uint64))[0])
-
-
-def permutation_indices(seed, r, n):
-    """``pi_r(0 .. n - 1)`` of ``seed`` as an int64 array: the permutation ``fdx_spatial_perm_dev`` applies to the rows of V
-    (``V_pi[i] = V[pi_r(i)]``), defined here in NumPy uint64 arithmetic; the device matches it bit for bit.
-
-    An unbalanced Feistel network on ``b = max(2, bit_length(n - 1))`` bits: ``x = (L << wr) | R`` with ``wl = b // 2`` bits of L
-    and ``wr = b - wl`` of R; each of 8 rounds sends ``(L, R)`` to ``(R, L ^ (F(R) mod 2^width(L)))`` and swaps the two widths,
-    with ``F(R) = mix64(key ^ (round << 32 | R))``, ``mix64`` the splitmix64 finaliser and
-    ``key = mix64(mix64(seed) + (r + 1) * 0x9e3779b97f4a7c15)``.  That is a bijection of [0, 2^b); a value >= n is sent through it
-    again until it falls below n (cycle-walking: a start below n lies on a cycle that returns below n), which makes it a
-    bijection of [0, n).  ``2^b < 2 n`` for n >= 3, so a walk takes under two steps on average."""
-    seed, r, n = int(seed), int(r), int(n)
-    if r < 0 or n < 0 or n >= (1 << 31) - 128:
-        raise ValueError(f"r must not be negative and n must be in [0, 2^31 - 128), got r = {r}, n = {n}")
-    return _keyed_bijection(_mix64_int(_mix64_int(seed) + (r + 1) * _GOLDEN), np.arange(n, dtype=np.uint64), n)
-
-
-def _keyed_bijection(key, x, n):
-    """``F_key(x)`` for a uint64 array ``x`` of values below ``n``: the Feistel network of ``permutation_indices`` under ``key``
-    (a Python int below 2^64), cycle-walked below ``n``; int64."""
-    b = max(2, (n - 1).bit_length()) if n > 0 else 2
-    wl0, wr0 = b // 2, b - b // 2
-    key = np.uint64(key)
-    out = np.array(x, dtype=np.uint64)
-    todo = np.arange(out.size)
-    with np.errstate(over="ignore"):
-        while todo.size:
-            x = out[todo]
-            L, R = x >> np.uint64(wr0), x & np.uint64((1 << wr0) - 1)
-            wl, wr = wl0, wr0
-            for rnd in range(_FEISTEL_ROUNDS):
-                f = _mix64(key ^ (np.uint64(rnd << 32) | R)) & np.uint64((1 << wl) - 1)
-                L, R = R, L ^ f
-                wl, wr = wr, wl
-            x = (L << np.uint64(wr0)) | R
-            out[todo] = x
-            todo = todo[x >= np.uint64(n)]
-    return out.astype(np.int64)
 
 
 def randomization_variance(n, W, sum_deg_sq, m2, m4):
@@ -174,20 +119,16 @@ def assemble_permutation(n, W, m2, C, count_ge, count_le, sum_d, sumsq_d, n_perm
     sd, sq = arrs[2].astype(np.float64), arrs[3].astype(np.float64)
     dead = np.isnan(cross)
     nan = np.float64(np.nan)
-    greater = np.where(dead, nan, (1.0 + ge) / (R + 1.0))
-    less = np.where(dead, nan, (1.0 + le) / (R + 1.0))
-    p = np.where(dead, nan, np.minimum(1.0, 2.0 * np.minimum(greater, less)))
     m2 = np.asarray(m2, dtype=np.float64)
     C = np.asarray(C, dtype=np.float64)
     with np.errstate(divide="ignore", invalid="ignore"):
+        greater, less, p, mean_d, std_d, z_sim = rank_against_null(np, ge, le, sd, sq, R)
         scale = (float(n) / float(W)) / np.sqrt(np.outer(m2, m2)) if W > 0 else np.full((K, K), nan)   # cross = scale * C
-        mean_d = sd / R
-        var_d = np.maximum(sq / R - mean_d * mean_d, 0.0)
         null_mean = np.where(dead, nan, scale * (C + mean_d))
-        null_std = np.where(dead, nan, scale * np.sqrt(var_d))
-        z_sim = np.where(dead | ~(null_std > 0), nan, -mean_d / np.sqrt(var_d))
-    out = {"n_permutations": R, "cross_p_greater": greater, "cross_p_less": less, "cross_p_value": p, "cross_null_mean": null_mean,
-           "cross_null_std": null_std, "cross_z_sim": z_sim}
+        null_std = np.where(dead, nan, scale * std_d)
+        z_sim = np.where(dead | ~(null_std > 0), nan, z_sim)      # the scaled deviation decides: it is what is reported
+    out = {"n_permutations": R, "cross_p_greater": np.where(dead, nan, greater), "cross_p_less": np.where(dead, nan, less),
+           "cross_p_value": np.where(dead, nan, p), "cross_null_mean": null_mean, "cross_null_std": null_std, "cross_z_sim": z_sim}
     for name in ("p_value", "p_greater", "p_less", "z_sim"):
         out[name] = np.diagonal(out["cross_" + name]).copy()
     return out
@@ -235,18 +176,6 @@ def spatial_autocorrelation(values, graph, neighbor_mean=False):
     return out
 
 
-def _permutation_seed(random_state):
-    """A uint64 seed: a non-negative int as it stands, else one 63-bit draw from the ``RandomState`` that
-    ``utils.check_random_state`` makes of the argument."""
-    if isinstance(random_state, (int, np.integer)) and not isinstance(random_state, (bool, np.bool_)):
-        if not 0 <= int(random_state) <= _MASK64:
-            raise ValueError(f"random_state must be in [0, 2^64) when it is an int, got {random_state}")
-        return int(random_state)
-    from .random import check_random_state
-    rs = check_random_state(random_state)
-    return (int(rs.randint(0, 1 << 31)) << 32) | int(rs.randint(0, 1 << 32, dtype=np.int64))
-
-
 def _permutation_calls(values, g, seed, first_perm, n_perm, max_batch, return_null, chunk):
     """The calls of ``spatial_permutation_sums`` on a resolved graph: permutations ``first_perm .. first_perm + n_perm - 1`` in
     calls of at most ``chunk``, counts and sums merged in order."""
@@ -270,9 +199,7 @@ def _permutation_calls(values, g, seed, first_perm, n_perm, max_batch, return_nu
             else:
                 null = np.empty((n_perm, K, K))
                 buf = torch.empty((min(chunk, max(n_perm, 1)), K, K), dtype=torch.float64, device=device)
-        done = 0
-        while True:                                     # (one call even without permutations: the observed sums and m4)
-            cnt = min(chunk, n_perm - done)
+        for done, cnt in permutation_chunks(n_perm, chunk):   # (one call even without permutations: the observed sums and m4)
             if return_null and cnt > 0:
                 null_ptr = ctypes.c_void_p((null[done:] if device_out else buf).data_ptr())
             else:
@@ -289,9 +216,6 @@ def _permutation_calls(values, g, seed, first_perm, n_perm, max_batch, return_nu
             tot_sd += sd
             tot_sq += sq
             batches.append(int(batch.value))
-            done += cnt
-            if done >= n_perm:
-                break
     out = {"mean": mean, "m2": m2, "m4": m4, "C": C, "n": int(counts[0]), "W": int(counts[1]), "sum_deg_sq": int(counts[2]),
            "count_ge": tot_ge, "count_le": tot_le, "sum_d": tot_sd, "sumsq_d": tot_sq, "n_permutations": int(n_perm),
            "batch": max(batches)}
@@ -308,8 +232,7 @@ def spatial_permutation_sums(values, graph, seed=0, first_perm=0, n_permutations
     (n_permutations, K, K) holds every ``C_r`` - a CUDA tensor when ``values`` was one, else numpy.  The counts and the null do
     not depend on ``max_batch`` or on how a range of permutations is split into calls."""
     n, K = check_values(values)
-    n_perm = check_count("n_permutations", n_permutations)
-    first_perm, max_batch = check_count("first_perm", first_perm), check_count("max_batch", max_batch)
+    n_perm, first_perm, max_batch = check_permutation_counts(n_permutations, first_perm, max_batch)
     seed = _permutation_seed(seed)
     with resolved_graph(graph, n) as g:
         chunk = max(1, n_perm)
