@@ -156,6 +156,12 @@ SIGNATURES = {
     "fdx_permutation_indices_dev": (c_int, [ctypes.c_uint64, c_i64, c_i64, c_void_p, c_void_p]),
     "fdx_label_pair_counts_dev": (c_int, [c_void_p, c_void_p, c_i32, ctypes.c_uint64, c_i64, c_i64, c_i32, c_void_p, p_i64, p_i64, p_i64,
                                           p_i64, p_i64, p_double, p_double, p_i32, c_void_p]),
+    "fdx_label_gene_sums_dev": (c_int, [c_void_p, c_i32, c_i64, c_i32, c_i64, c_void_p, c_i32, p_i32, c_i32, p_i32, c_i32, ctypes.c_uint64,
+                                        c_i64, c_i64, c_i32, c_i64, c_void_p, p_double, p_i64, p_i64, p_i64, p_i64, p_double, p_double,
+                                        p_i32, c_void_p]),
+    "fdx_label_gene_sums_csr_dev": (c_int, [ctypes.POINTER(CsrView), c_void_p, c_i32, p_i32, c_i32, p_i32, c_i32, ctypes.c_uint64, c_i64,
+                                            c_i64, c_i32, c_i64, c_void_p, p_double, p_i64, p_i64, p_i64, p_i64, p_double, p_double,
+                                            p_i32, c_void_p]),
     "fdx_local_stats_dev": (c_int, [c_void_p, c_void_p, c_i64, c_i32, ctypes.c_uint64, c_i64, c_i64, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, p_double, p_double, p_i64, c_void_p]),
     "fdx_spatial_correlogram_dev": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_i64, c_i32, p_double, c_i32, c_i32, c_i64, p_double,

@@ -821,31 +821,66 @@ class FlashDeconv:
         if labels is not None and n_niches is not None:
             raise ValueError("at most one of labels and n_niches may be given")
         from ..utils._device import check_count
-        from ..utils.neighborhoods import _check_flag, check_labels, neighborhood_enrichment
+        from ..utils.neighborhoods import _check_flag, neighborhood_enrichment
         check_count("n_permutations", n_permutations)
         return_null = _check_flag("return_null", kw.pop("return_null", False))
         n_labels = kw.pop("n_labels", None)
-        if n_niches is None and kw:
-            raise TypeError(f"unexpected keyword arguments without n_niches: {sorted(kw)}")
+        labels, n_labels = self._spot_labels(labels, n_niches, n_labels, kw, "neighbourhood enrichment")
+        return neighborhood_enrichment(labels, self, n_labels=n_labels, n_permutations=n_permutations,
+                                       random_state=self.random_state if random_state is None else random_state,
+                                       return_null=return_null)
+
+    def _spot_labels(self, labels, n_niches, n_labels, niche_kw, what):
+        """``(labels, n_labels)`` of the one label source of a fitted model that the entries on spot labels share (``what`` names
+        the entry in the messages): ``labels`` as given (checked, with the fit's spots), the ``labels`` of
+        ``get_spatial_niches(n_niches, **niche_kw)``, or - neither given - each spot's dominant cell type."""
+        if n_niches is None and niche_kw:
+            raise TypeError(f"unexpected keyword arguments without n_niches: {sorted(niche_kw)}")
         if labels is not None:
+            from ..utils.neighborhoods import check_labels
             if check_labels(labels, n_labels)[0] != self.n_spots_:
                 raise ValueError(f"labels must have the {self.n_spots_} spots of the fit, got {tuple(labels.shape)}")
         elif n_niches is not None:
             if n_labels is not None:
                 raise ValueError("n_labels goes with labels: with n_niches the number of labels is n_niches")
             from ..utils.niches import _check_n_niches
-            n_labels = _check_n_niches(n_niches, self.n_spots_)              # at most 64 niches: the labels this entry takes
-            labels = self.get_spatial_niches(n_niches, **kw)["labels"]
+            n_labels = _check_n_niches(n_niches, self.n_spots_)              # at most 64 niches: the labels these entries take
+            labels = self.get_spatial_niches(n_niches, **niche_kw)["labels"]
         else:
             if n_labels is not None:
                 raise ValueError("n_labels goes with labels: the dominant cell types are n_cell_types_ labels")
             if self.n_cell_types_ > 64:
-                raise ValueError(f"neighbourhood enrichment is built for at most 64 labels, got {self.n_cell_types_} cell types")
+                raise ValueError(f"{what} is built for at most 64 labels, got {self.n_cell_types_} cell types")
             n_labels = int(self.n_cell_types_)
             labels = self.get_dominant_cell_type()
-        return neighborhood_enrichment(labels, self, n_labels=n_labels, n_permutations=n_permutations,
-                                       random_state=self.random_state if random_state is None else random_state,
-                                       return_null=return_null)
+        return labels, n_labels
+
+    def get_ligand_receptor(self, Y, pairs, labels=None, n_niches=None, n_permutations=999, random_state=None, **kw):
+        """Between which niches or cell types of this tissue a ligand-receptor pair acts (additive, not in the reference): for every
+        pair of ``pairs`` ((P, 2) column indices of ``Y``, ligand then receptor) and every ordered pair of labels (a, b) the mean of
+        the ligand in a and of the receptor in b, ranked against random reassignments of the labels to the spots on the GPU -
+        ``utils.ligrec.ligand_receptor_test``.  The label sources are those of ``get_neighborhood_enrichment``: ``labels``
+        (``n_labels`` may be passed beside them), ``n_niches`` (which takes the further keywords of ``get_spatial_niches``) or
+        neither - each spot's dominant cell type; giving both is a ``ValueError``.  ``Y``: ``n_spots_`` rows, dense or CSR, ANY gene
+        set, tested as it is passed.  ``random_state``: None is the model's.  ``threshold``, ``n_top`` and ``return_null`` go to
+        ``ligand_receptor_test``.  Works for both ``output`` kinds of ``fit``: labels stay on the device where they are."""
+        self._weights_for(Y, "proportions", None)              # fitted, and Y has the fit's spots as rows
+        if labels is not None and n_niches is not None:
+            raise ValueError("at most one of labels and n_niches may be given")
+        from ..utils._device import check_count
+        from ..utils.ligrec import check_request, ligand_receptor_test
+        from ..utils.neighborhoods import _check_flag
+        from ..utils.spatial_genes import _check_n_top
+        check_count("n_permutations", n_permutations)
+        return_null = _check_flag("return_null", kw.pop("return_null", False))
+        threshold, n_top = kw.pop("threshold", 0.01), _check_n_top(kw.pop("n_top", None))
+        n_labels = kw.pop("n_labels", None)
+        # the pairs and the threshold fail here, before the k-means (the labels proper are checked with their source)
+        check_request(tuple(Y.shape), pairs, np.zeros(int(Y.shape[0]), dtype=np.int32), None, n_permutations, 0, 0, threshold)
+        labels, n_labels = self._spot_labels(labels, n_niches, n_labels, kw, "the ligand-receptor test")
+        return ligand_receptor_test(Y, labels, pairs, n_labels=n_labels, n_permutations=n_permutations,
+                                    random_state=self.random_state if random_state is None else random_state, threshold=threshold,
+                                    n_top=n_top, return_null=return_null)
 
     def get_dominant_cell_type(self):
         self._require_fitted()

@@ -60,6 +60,7 @@
 
 #include "fdx_graph.h"
 #include "fdx_internal.h"
+#include "gene_gather.h"
 #include "gene_pass.h"
 #include "gene_walk.h"
 #include "perm_device.h"
@@ -81,37 +82,7 @@ constexpr int GP_TARGET_GROUPS = 2048;                                    // wor
 template <typename T, int TG>
 struct alignas(sizeof(T) * TG) GpVec { T v[TG]; };
 
-// Yt[tile][p][g] (tiles t0 .. t0 + nt - 1 of this stripe) = Y[perm[p], genes[tile * TG + g]], 0 past S; a thread per element
-template <typename T, int TG>
-__global__ __launch_bounds__(256) void gp_gather_dense_kernel(const T* __restrict__ Y, long long ldy, const int* __restrict__ perm,
-                                                              long long n, const int* __restrict__ genes, int S, int s0, int width,
-                                                              T* __restrict__ Yt) {
-    const long long total = n * width;                          // width = nt * TG slots
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        const long long p = e / width;
-        const int k = (int)(e - p * width), s = s0 + k;
-        const long long row = perm ? perm[p] : p;
-        Yt[((size_t)(k / TG) * n + p) * TG + (k % TG)] = s < S ? Y[row * ldy + genes[s]] : (T)0;
-    }
-}
-
-// Yt (zeroed) takes the stored entries of the stripe's columns: a wave per position, a lane per stored entry of its row
-template <typename T, int TG>
-__global__ __launch_bounds__(256) void gp_gather_csr_kernel(const long long* __restrict__ indptr, const int* __restrict__ indices,
-                                                            const T* __restrict__ values, const int* __restrict__ perm, long long n,
-                                                            int G, const int* __restrict__ slot_of, int s0, int width,
-                                                            T* __restrict__ Yt) {
-    const int lane = threadIdx.x & 63;
-    for (long long p = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); p < n; p += (long long)gridDim.x * 4) {
-        const long long row = perm ? perm[p] : p;
-        const long long e1 = indptr[row + 1];
-        for (long long e = indptr[row] + lane; e < e1; e += 64) {
-            const int c = indices[e];
-            const int k = ((unsigned)c < (unsigned)G ? slot_of[c] : -1) - s0;
-            if (k >= 0 && k < width) Yt[((size_t)(k / TG) * n + p) * TG + (k % TG)] = values[e];
-        }
-    }
-}
+// (gene_gather.h: the gather kernels, shared with the label gene sums)
 
 __global__ __launch_bounds__(256) void gp_inverse_kernel(const int* __restrict__ perm, int n, int* __restrict__ inv) {
     const int p = blockIdx.x * 256 + threadIdx.x;
@@ -392,19 +363,7 @@ int gp_launch_null(const GpPlan& plan, const T* Yt, const int* tables, const Gra
 template <typename T, int TG>
 int gp_gather_as(const GraphTables& t, const GeneMatrix& y, const T* data, const int* genes_dev, const int* slot_dev, int S, int s0,
                  int tiles, T* Yt, hipStream_t st) {
-    const long long n = t.n;
-    const int width = tiles * TG;
-    if (y.sparse) {
-        FDX_HIP(hipMemsetAsync(Yt, 0, (size_t)n * width * sizeof(T), st));
-        hipLaunchKernelGGL((gp_gather_csr_kernel<T, TG>), dim3((unsigned)std::min<long long>(ceil_div(n, 4), 1 << 16)), dim3(256), 0, st,
-                           (const long long*)y.csr->indptr, y.csr->indices, data, t.perm, n, y.G, slot_dev, s0, width, Yt);
-    } else {
-        const long long blocks = std::min<long long>((n * width + 255) / 256, 1 << 20);
-        hipLaunchKernelGGL((gp_gather_dense_kernel<T, TG>), dim3((unsigned)blocks), dim3(256), 0, st, data, y.ldy, t.perm, n, genes_dev, S,
-                           s0, width, Yt);
-    }
-    FDX_CHECK_LAUNCH();
-    return 0;
+    return gather_gene_tiles<T, TG>(t.perm, t.n, y, data, genes_dev, slot_dev, S, s0, tiles, Yt, st);
 }
 
 template <typename T>

@@ -29,6 +29,7 @@
 #include "fdx_graph.h"
 #include "fdx_internal.h"
 #include "gene_pass.h"
+#include "label_stage.h"
 #include "perm_device.h"
 
 #include <algorithm>
@@ -36,79 +37,10 @@
 
 namespace fdx {
 
-constexpr int LP_MAX_LABELS = 64;
-constexpr unsigned LP_NONE = 0xffu;      // the byte of a spot that is not counted (labels are below 64: bit 7 marks it)
 constexpr int LP_MAX_GROUPS = 64;        // groups of B permutations per launch chain (a grid dimension)
 constexpr int LP_TARGET_WAVES = 8192;    // waves of a count launch over all its groups: the chip's 256 CUs x 32
 
-struct LpPermArgs {
-    PermKeys keys;
-    int batch;                           // permutations of this launch (the last group may be ragged)
-};
-
-// codes[i] = the byte of label i; *flag |= 1 where a label is outside [-1, C); label_counts[a] = n_a; deg_sums = {sum deg, sum deg^2}
-__global__ __launch_bounds__(256) void lp_prepare_kernel(const int* __restrict__ labels, const int* __restrict__ deg, int n, int C,
-                                                         unsigned char* __restrict__ codes,
-                                                         unsigned long long* __restrict__ label_counts,
-                                                         unsigned long long* __restrict__ deg_sums, int* __restrict__ flag) {
-    __shared__ unsigned hist[LP_MAX_LABELS];
-    __shared__ unsigned long long red[4][2];
-    if (threadIdx.x < LP_MAX_LABELS) hist[threadIdx.x] = 0u;
-    __syncthreads();
-    unsigned long long sd = 0, sd2 = 0;
-    bool bad = false;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const int l = labels[i];
-        bad |= l < -1 || l >= C;
-        const bool counted = l >= 0 && l < C;
-        codes[i] = counted ? (unsigned char)l : (unsigned char)LP_NONE;
-        if (counted) atomicAdd(&hist[l], 1u);
-        const unsigned long long dg = (unsigned long long)deg[i];
-        sd += dg;
-        sd2 += dg * dg;
-    }
-    if (bad) atomicOr(flag, 1);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sd += __shfl_xor(sd, off, 64);
-        sd2 += __shfl_xor(sd2, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = sd; red[threadIdx.x >> 6][1] = sd2; }
-    __syncthreads();
-    if ((int)threadIdx.x < C && hist[threadIdx.x]) atomicAdd(&label_counts[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
-    if (threadIdx.x < 2) {
-        const unsigned long long s = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        if (s) atomicAdd(&deg_sums[threadIdx.x], s);
-    }
-}
-
-// Lr[blockIdx.y][q][j] for q < ld (header).  IDENTITY: permutation 0 of the one group is the identity, the rest LP_NONE.
-template <int B, bool IDENTITY>
-__global__ __launch_bounds__(256) void lp_stage_kernel(const unsigned char* __restrict__ codes, const int* __restrict__ perm, int n,
-                                                       long long ld, unsigned char* __restrict__ Lr, LpPermArgs pa) {
-    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (q >= ld) return;
-    unsigned w[B / 4];
-#pragma unroll
-    for (int k = 0; k < B / 4; ++k) w[k] = 0xffffffffu;
-    if (q < n) {
-        const int row = perm ? perm[q] : (int)q;
-        if constexpr (IDENTITY) {
-            w[0] = 0xffffff00u | codes[row];
-        } else {
-            const int j0 = blockIdx.y * B;
-#pragma unroll
-            for (int j = 0; j < B; ++j)
-                if (j0 + j < pa.batch) {
-                    const unsigned c = codes[ss_permute_index(perm_key_at(pa.keys, j0 + j), row, n, pa.keys.wl, pa.keys.wr)];
-                    w[j / 4] = (w[j / 4] & ~(0xffu << (8 * (j % 4)))) | (c << (8 * (j % 4)));
-                }
-        }
-    }
-    unsigned* out = reinterpret_cast<unsigned*>(Lr + ((size_t)blockIdx.y * ld + q) * B);
-    if constexpr (B == 8) *reinterpret_cast<uint2*>(out) = make_uint2(w[0], w[1]);
-    else *reinterpret_cast<uint4*>(out) = make_uint4(w[0], w[1], w[2], w[3]);
-}
+// (label_stage.h: lp_prepare_kernel - here with deg_sums = {sum deg, sum deg^2} - and lp_stage_kernel, shared with the label gene sums)
 
 template <int B>
 __device__ __forceinline__ void lp_load(const unsigned char* __restrict__ Lr, long long q, unsigned (&w)[B / 4]) {
@@ -270,7 +202,7 @@ static int launch_label_pairs(const LabelPairPlan& p, const fdx_graph* graph, co
     FDX_HIP(hipMemsetAsync(out, 0, p.words * sizeof(long long), st));
     FDX_HIP(hipMemsetAsync(acc, 0, (size_t)p.groups * B * p.CC * sizeof(long long), st));
     long long* obs = out;
-    hipLaunchKernelGGL(lp_prepare_kernel, dim3(std::min(1024, ceil_div(n, 256))), dim3(256), 0, st, labels, g.deg, n, C, codes,
+    hipLaunchKernelGGL(lp_prepare_kernel<true>, dim3(std::min(1024, ceil_div(n, 256))), dim3(256), 0, st, labels, g.deg, n, C, codes,
                        reinterpret_cast<unsigned long long*>(out + p.o_counts), reinterpret_cast<unsigned long long*>(out + p.o_deg),
                        reinterpret_cast<int*>(out + p.o_flag));
     FDX_CHECK_LAUNCH();

@@ -8,7 +8,8 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
                layer_st=None, layer_ref=None, spatial_key="spatial", key_added="flashdeconv", random_state=0, copy=False,
                spot_diagnostics=False, spatial_stats=False, n_niches=None, spatial_permutations=0, local_stats=False,
                correlogram=False, celltype_expression=False, spatial_genes=False, gene_pairs=None,
-               gene_modules=False, niche_genes=False, gene_permutations=0, nhood_enrichment=False):
+               gene_modules=False, niche_genes=False, gene_permutations=0, nhood_enrichment=False, ligrec_pairs=None,
+               ligrec_permutations=999):
     """Writes ``.obsm[key_added]`` (proportions DataFrame), ``.obs[key_added + '_dominant']`` and
     ``.uns[key_added + '_params']``; returns the modified copy when ``copy=True``, else ``None``.  ``spot_diagnostics=True``
     (additive) also writes ``.obs[key_added + '_residual']`` (relative sketch residual per spot) and
@@ -67,7 +68,16 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
     neighbour of the column's over the fit's graph), ``zscore`` (the count against ``spatial_permutations`` random reassignments of
     the labels to the spots on the GPU, 999 when that is 0, seeded by ``random_state``) and ``pvalue`` (two-sided)
     (``FlashDeconv.get_neighborhood_enrichment``) - and ``.uns[key_added + '_params']['nhood_enrichment']``, the number of
-    permutations."""
+    permutations.
+    ``ligrec_pairs`` (additive): a non-empty sequence of ``(ligand, receptor)`` names, resolved as ``gene_pairs`` resolves them (an
+    unknown name or a bad ``ligrec_permutations`` - an int >= 0 - is a ``ValueError`` before the fit), also writes
+    ``.uns[key_added + '_ligrec']``, a dict of three DataFrames with one row per pair, named ``ligand_receptor``, and a
+    (``source``, ``target``) MultiIndex of columns over the niche indices when ``n_niches`` is given, else over the cell types
+    (each spot labelled by its dominant one): ``means`` (the mean of the ligand in the source's spots and of the receptor in the
+    target's, halved), ``pvalues`` (one-sided, against ``ligrec_permutations`` random reassignments of the labels to the spots on
+    the GPU, seeded by ``random_state``; NaN where a group is empty or expresses its gene in under 1 % of its spots) and
+    ``qvalues`` (Benjamini-Hochberg over all of them) (``FlashDeconv.get_ligand_receptor``) - and
+    ``.uns[key_added + '_params']['ligrec']``, the number of permutations."""
     from ..core.deconv import FlashDeconv
     from ..io import prepare_data, result_to_anndata
     from ..utils.correlogram import correlogram_request
@@ -93,10 +103,11 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
         raise ValueError(f"nhood_enrichment must be True or False, got {nhood_enrichment!r}")
     if niche_genes and n_niches is None:
         raise ValueError("niche_genes=True needs n_niches: the niches whose marker genes are asked for")
-    if gene_pairs is not None:
-        gene_pairs = [tuple(pair) for pair in gene_pairs]
-        if not gene_pairs or any(len(pair) != 2 for pair in gene_pairs):
-            raise ValueError(f"gene_pairs must be a non-empty sequence of (name_a, name_b), got {gene_pairs!r}")
+    gene_pairs = _pair_names("gene_pairs", gene_pairs, "(name_a, name_b)")
+    ligrec_pairs = _pair_names("ligrec_pairs", ligrec_pairs, "(ligand, receptor)")
+    if ligrec_pairs is not None:
+        from ..utils._device import check_count
+        check_count("ligrec_permutations", ligrec_permutations)
 
     adata = adata_st.copy() if copy else adata_st
     Y, X, coords, names, genes = prepare_data(adata, adata_ref, cell_type_key=cell_type_key, layer_st=layer_st,
@@ -113,13 +124,19 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
         if isinstance(n_niches, (int, np.integer)) and n_niches > MAX_GROUPS:
             raise ValueError(f"niche_genes is built for at most {MAX_GROUPS} niches, got n_niches = {n_niches}")
     if gene_pairs is not None:
-        from ..utils.gene_pairs import check_request as check_gene_pairs
-        column = {str(name): j for j, name in enumerate(genes)}
-        for pair in gene_pairs:
-            for name in pair:
-                if str(name) not in column:
-                    raise ValueError(f"gene_pairs names the gene {name!r}, which is not among the genes common to both objects")
-        pair_idx = check_gene_pairs(tuple(Y.shape), np.array([[column[str(a)], column[str(b)]] for a, b in gene_pairs], dtype=np.int64))
+        pair_idx = _pair_columns("gene_pairs", gene_pairs, genes, Y)
+    if ligrec_pairs is not None:
+        from ..utils.ligrec import check_request as check_ligrec
+        ligrec_idx = _pair_columns("ligrec_pairs", ligrec_pairs, genes, Y)
+        if n_niches is None:
+            if len(names) > 64:
+                raise ValueError(f"ligrec_pairs is built for at most 64 labels, got {len(names)} cell types: give n_niches")
+            n_groups = len(names)
+        else:
+            from ..utils.niches import _check_n_niches
+            n_groups = _check_n_niches(n_niches, int(Y.shape[0]))
+        # the pairs, the caps (distinct genes, pairs x groups^2) and the permutation count: the labels themselves come with the fit
+        check_ligrec(tuple(Y.shape), ligrec_idx, np.zeros(int(Y.shape[0]), dtype=np.int32), n_groups, ligrec_permutations)
     # like the reference, max_iter / tol / verbose are not exposed here (tl/_deconvolve.py:132-144)
     model = FlashDeconv(sketch_dim=sketch_dim, lambda_spatial=lambda_spatial, rho_sparsity=rho_sparsity, n_hvg=n_hvg,
                         n_markers_per_type=n_markers_per_type, spatial_method=spatial_method, k_neighbors=k_neighbors,
@@ -194,6 +211,22 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
             "zscore": pd.DataFrame(ne["z_sim"], index=index, columns=index),
             "pvalue": pd.DataFrame(ne["p_value"], index=index, columns=index)}
         adata.uns[f"{key_added}_params"]["nhood_enrichment"] = n_perm
+    if ligrec_pairs is not None:
+        import pandas as pd
+        if n_niches is not None:
+            lr = model.get_ligand_receptor(Y, ligrec_idx, labels=niches["labels"], n_labels=int(n_niches),
+                                           n_permutations=int(ligrec_permutations), random_state=random_state)
+            index = list(range(int(n_niches)))
+        else:
+            lr = model.get_ligand_receptor(Y, ligrec_idx, n_permutations=int(ligrec_permutations), random_state=random_state)
+            index = [str(t) for t in names]
+        rows = pd.Index([f"{a}_{b}" for a, b in ligrec_pairs], name="ligand_receptor")
+        columns = pd.MultiIndex.from_product([index, index], names=["source", "target"])
+        nan = np.full(lr["means"].shape, np.nan)
+        adata.uns[f"{key_added}_ligrec"] = {
+            name: pd.DataFrame(np.asarray(lr.get(key, nan)).reshape(len(ligrec_pairs), -1), index=rows, columns=columns)
+            for name, key in (("means", "means"), ("pvalues", "p_greater"), ("qvalues", "q_value"))}
+        adata.uns[f"{key_added}_params"]["ligrec"] = int(ligrec_permutations)
     if local_stats:
         import pandas as pd
         local = model.get_local_spatial_statistics(n_permutations=spatial_permutations)
@@ -268,6 +301,28 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
 
 def _host(x):
     return x.cpu().numpy() if hasattr(x, "cpu") else x
+
+
+def _pair_names(what, pairs, form):
+    """``pairs`` of the argument ``what`` as a list of 2-tuples (None stays None); ``ValueError`` for anything but a non-empty
+    sequence of pairs."""
+    if pairs is None:
+        return None
+    pairs = [tuple(pair) for pair in pairs]
+    if not pairs or any(len(pair) != 2 for pair in pairs):
+        raise ValueError(f"{what} must be a non-empty sequence of {form}, got {pairs!r}")
+    return pairs
+
+
+def _pair_columns(what, pairs, genes, Y):
+    """The (P, 2) int32 columns of ``Y`` that the named ``pairs`` stand for; ``ValueError`` for a name that is not among ``genes``."""
+    from ..utils.gene_pairs import check_request as check_gene_pairs
+    column = {str(name): j for j, name in enumerate(genes)}
+    for pair in pairs:
+        for name in pair:
+            if str(name) not in column:
+                raise ValueError(f"{what} names the gene {name!r}, which is not among the genes common to both objects")
+    return check_gene_pairs(tuple(Y.shape), np.array([[column[str(a)], column[str(b)]] for a, b in pairs], dtype=np.int64))
 
 
 def _library_scale(Y):

@@ -198,7 +198,9 @@ def _labels_on_device(labels, C, device):
         if hi >= MAX_LABELS:
             raise ValueError(f"at most {MAX_LABELS} labels, got labels up to {hi}")
         C = max(hi + 1, 1)
-    if lab.dtype != torch.int32:
+    if lab.dtype == torch.uint8:                      # (every value fits; a negative bound cannot clamp an unsigned dtype)
+        lab = lab.to(torch.int32)
+    elif lab.dtype != torch.int32:
         lab = lab.clamp(-2, MAX_LABELS).to(torch.int32)
     return lab.contiguous(), C
 

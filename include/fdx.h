@@ -635,6 +635,39 @@ int fdx_label_pair_counts_dev(const fdx_graph* g, const int32_t* labels_dev, int
                               int64_t n_perm, int32_t max_batch, int64_t* null_dev, int64_t* label_counts_out, int64_t* pair_out,
                               int64_t* counts_out, int64_t* count_ge_out, int64_t* count_le_out, double* sum_d_out,
                               double* sumsq_d_out, int32_t* batch_out, void* stream);
+/* Ligand-receptor test between spot groups: per-label gene sums and their label-permutation null (additive, not in the reference;
+ * no graph).  Y (n, G) as for fdx_gene_group_sums_dev (dense FDX_F32 / FDX_F64 with row stride ldy on the DEVICE, or a CSR view with
+ * rows in any order); labels_dev: n int32 on the DEVICE in [-1, C), -1 = not counted, 1 <= C <= 64; 1 <= n <= 2^24.  HOST inputs:
+ * `genes`, S <= 4096 ascending distinct columns of Y, and `pairs` (P, 2) int32 columns (ligand, receptor), every one listed in
+ * `genes`, P >= 1 and P * C^2 <= 2^22.  In float64 on the value converted from storage, to HOST memory:
+ *   u_out (C, S) = u[c, s] = sum_{i : l_i = c} y[i, genes[s]]      nnz_out (C, S) = #{i : l_i = c, y != 0}      label_counts_out[c] = n_c
+ * Then permutations first_perm .. first_perm + n_perm - 1 of `seed` (pi_r as for fdx_spatial_perm_dev; n_perm = 0: the observed
+ * part only): the labels l^r_i = l[pi_r(i)] - a spot labelled -1 is shuffled like any other and never counted, so every n_c stays -
+ * give u^r, and per (p, a, b) with T^r = (u^r[a, lig_p] / n_a + u^r[b, rec_p] / n_b) * 0.5 (one IEEE division per mean, one
+ * addition, one multiplication) and T the same expression of u, to HOST memory, (P, C, C) row-major each:
+ *   count_ge_out / count_le_out = how many of the call's permutations have T^r >= T / T^r <= T
+ *   sum_d_out / sumsq_d_out     = the float64 sums over them of d = T^r - T and of d * d (the square rounded, then added: no fma),
+ *                                 added in permutation order
+ * all four 0 where n_a < 1 or n_b < 1.  null_dev (may be NULL): (n_perm, C, S) float64 DEVICE array that receives every u^r.
+ * Permutations run in batches of B per launch chain (groups of 16, as many as a scratch budget of 1 GiB holds, at most 64 groups
+ * and at most max_batch permutations when that is positive; *batch_out, may be NULL, reports B); the gathered copy of the columns
+ * goes in stripes of whole tiles of 16 genes above max_gather_bytes (0: 1 GiB).  Order: a spot's value is added to the cell of its
+ * label by a thread that owns the cell, the spots of a segment of 2,048 in ascending order, the segments in ascending order; an
+ * exact zero is skipped, which changes no bit.  So u^r depends only on the labels, the column and the permutation - not on B,
+ * max_batch, the stripe, the other genes or pairs, first_perm or the call it ran in; split calls add their counts exactly; no
+ * floating-point atomics, two calls return the same bits, one host synchronisation.  Refused with a message: null pointers, a bad
+ * view / ldy < G / dtype, n, C, S, P out of range, genes not ascending or outside [0, G), a pair's column missing from genes,
+ * negative counts, and - checked on the device, reported after the call - a label outside [-1, C). */
+int fdx_label_gene_sums_dev(const void* Y_dev, int32_t dtype, int64_t n, int32_t G, int64_t ldy, const int32_t* labels_dev, int32_t C,
+                            const int32_t* genes, int32_t S, const int32_t* pairs, int32_t P, uint64_t seed, int64_t first_perm,
+                            int64_t n_perm, int32_t max_batch, int64_t max_gather_bytes, double* null_dev, double* u_out, int64_t* nnz_out,
+                            int64_t* label_counts_out, int64_t* count_ge_out, int64_t* count_le_out, double* sum_d_out, double* sumsq_d_out,
+                            int32_t* batch_out, void* stream);
+int fdx_label_gene_sums_csr_dev(const fdx_csr_view* Y, const int32_t* labels_dev, int32_t C, const int32_t* genes, int32_t S,
+                                const int32_t* pairs, int32_t P, uint64_t seed, int64_t first_perm, int64_t n_perm, int32_t max_batch,
+                                int64_t max_gather_bytes, double* null_dev, double* u_out, int64_t* nnz_out, int64_t* label_counts_out,
+                                int64_t* count_ge_out, int64_t* count_le_out, double* sum_d_out, double* sumsq_d_out, int32_t* batch_out,
+                                void* stream);
 /* Local indicators of spatial association over a whole graph (additive, not in the reference): per spot and column the observed
  * neighbour sum and its conditional-permutation null.  V_dev as for fdx_spatial_autocorr_dev.  DEVICE outputs, rows in the
  * caller's spot order, overwritten:
