@@ -357,7 +357,7 @@ def require_gpu():
 
 
 def host_cpu_budget():
-    """CPUs this process may keep busy: its affinity mask cut to the control group's CPU bandwidth quota (csrc/kdtree_order.cpp has
+    """CPUs this process may keep busy: its affinity mask cut to the control group's CPU bandwidth quota (csrc/host_threads.cpp has
     the same rule: threads beyond the quota only get the whole process throttled)."""
     cpus = float(len(os.sched_getaffinity(0))) if hasattr(os, "sched_getaffinity") else float(os.cpu_count() or 1)
     try:

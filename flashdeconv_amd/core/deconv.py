@@ -212,7 +212,7 @@ class FlashDeconv:
         # additive (not in the reference): how exactly equidistant candidates for the k-th neighbour are taken (regular lattices
         # tie on every spot).  "auto" (default): the device build's graph when it met no tie - every tie-free input, at no cost -
         # and otherwise the fit is repeated on the reference's own choice (cKDTree's traversal order, restated on the host:
-        # csrc/kdtree_order.cpp), so the result is the reference's on lattices too; "ckdtree": the same, decided before the
+        # csrc/kdtree_host.cpp), so the result is the reference's on lattices too; "ckdtree": the same, decided before the
         # first solve (one fit, but the graph build is waited for); "index": ascending spot index, the device rule, always
         # (fastest on lattices; a warning reports the ties, proportions a few 1e-4 from the reference's)
         if knn_ties not in ("auto", "index", "ckdtree"):
@@ -406,7 +406,7 @@ class FlashDeconv:
             if self.spatial_method == "knn" and self.knn_ties == "ckdtree" and not big_k:
                 # the reference's tie order, on request: only when the device build met ties (this question waits for the
                 # build, which otherwise completes behind the sketch) the lists come from the host restatement of scipy's
-                # tree (csrc/kdtree_order.cpp) and the graph is rebuilt from the reference's own adjacency
+                # tree (csrc/kdtree_host.cpp) and the graph is rebuilt from the reference's own adjacency
                 n_ties = self._graph.knn_ties()
                 if n_ties:
                     self._graph.close()

@@ -33,7 +33,8 @@ int graph_plan_set_lists(fdx_graph_plan* plan, const long long* ids_host, const 
 int graph_plan_set_lists_device(fdx_graph_plan* plan, const long long* ids_dev, const long long* rows_host, long long n_rows, int* nbr,
                                 int* cnt, hipStream_t st);
 // kdtree_order.cpp: the reference's k-nearest lists (scipy cKDTree's tie order) for rows_host (NULL: all points) into ids_dev
-// (n_rows x kk int64, caller ids, nearest first, self included, -1 padded); tree on the host, queries on the device
+// (n_rows x kk int64, caller ids, nearest first, self included, -1 padded); tree on the device (kdtree_build_dev.cpp) or on the
+// host (kdtree_host.cpp), queries on the device (kdtree_query_dev.cpp) or, where it cannot serve, on the host
 int ckdtree_lists_device(const double* coords_host, const double* coords_dev, long long n, int dim, int kk, const long long* rows_host,
                          long long n_rows, long long* ids_dev, hipStream_t st);
 int graph_plan_order(const fdx_graph_plan* plan, int* d_perm_out, int* d_rank_out, hipStream_t st);   // device copies of perm / rank (either may be NULL)

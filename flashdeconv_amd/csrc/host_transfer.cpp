@@ -17,10 +17,7 @@
 #include <vector>
 
 #include "fdx_internal.h"
-
-namespace fdx {
-unsigned host_cpu_budget();          // kdtree_order.cpp: hardware threads cut to the control group's CPU quota
-}
+#include "host_threads.h"
 
 namespace {
 

@@ -1,4 +1,4 @@
-// The restated cKDTree (kdtree_order.cpp: scipy.spatial.cKDTree's build, utils/graph.py:60) BUILT ON THE DEVICE for 1-3 coordinates.
+// The restated cKDTree (kdtree_host.cpp: scipy.spatial.cKDTree's build, utils/graph.py:60) BUILT ON THE DEVICE for 1-3 coordinates.
 //
 // What has to come out is scipy's index array and node structure exactly, i.e. libstdc++'s introselect replayed swap for swap at
 // every node (the order of equidistant neighbours hangs on it).  The host build does that with a pool of threads in 9-11 ms per
@@ -8,7 +8,7 @@
 //                the side holding nth, until three elements are left (insertion sort, one thread); the depth budget of 2 log2(n)
 //                partitions is kept, and a node that would exhaust it (libstdc++ then switches to heap select) raises a flag: the
 //                caller builds on the host instead
-//   partition    in the list form of kdtree_order.cpp (team_unguarded_partition): the serial scan's k-th swap is (k-th position
+//   partition    in the list form of kdtree_host.cpp (team_unguarded_partition): the serial scan's k-th swap is (k-th position
 //                from the left whose key stops the left pointer, k-th from the right whose key stops the right pointer) while the
 //                former lies left of the latter.  Every thread lists the stops of its contiguous chunk, two scans give the ranks,
 //                the number of swaps K is counted in parallel (a left stop at position x with rank k is swapped iff more than k

@@ -308,7 +308,7 @@ class ShardedFlashDeconv:
                                   radius=radius, max_iter=max_iter, tol=tol, preprocess=preprocess, random_state=random_state)
         self.n_markers_per_type = n_markers_per_type
         # exactly tied k-th neighbour distances (regular lattices): "auto" / "ckdtree" - the graph is then the reference's own
-        # (cKDTree's choice, restated on the host, csrc/kdtree_order.cpp; every rank builds it from the replicated coordinates and
+        # (cKDTree's choice, restated on the host, csrc/kdtree_host.cpp; every rank builds it from the replicated coordinates and
         # cuts its own rows out, shards in the CALLER's spot order) as in FlashDeconv; "index" - the device rule, with a warning
         if knn_ties not in ("auto", "index", "ckdtree"):
             raise ValueError(f"knn_ties must be 'auto', 'index' or 'ckdtree', got {knn_ties}")
@@ -705,8 +705,8 @@ class ShardedFlashDeconv:
                 and coords.shape[1] <= 3 and not os.environ.get("FDX_TIES_FULL_GRAPH")):
             # The device builds chose among equidistant neighbours by spot index; the reference takes whichever cKDTree's query
             # meets first.  The shards stay what they are (Morton ranges: own_ids do not change): every rank asks the restated
-            # tree (csrc/kdtree_order.cpp: the tree of all points - O(n log n) on the host - but only the queries of its own rows
-            # and of its band) for the reference's lists, puts them in the place of the device's, and symmetrises / localises as
+            # tree (csrc/kdtree_host.cpp, through the entries of kdtree_order.cpp: the tree of all points - O(n log n) on the
+            # host - but only the queries of its own rows and of its band) for the reference's lists, puts them in the place of the device's, and symmetrises / localises as
             # before - the reference's rows index for index.
             self._ties_remedy_lists(coords)
             self.plan_route_ = "ckdtree-lists"

@@ -79,7 +79,7 @@ def _ckdtree_restatement_matches_scipy():
 
 def ckdtree_knn_lists(coords, k):
     """(n, k + 1) neighbour indices exactly as ``cKDTree(coords).query(coords, k=k+1)`` returns them (utils/graph.py:60-63),
-    ties included: libfdx's host restatement of scipy's tree build and traversal order (csrc/kdtree_order.cpp), checked once
+    ties included: libfdx's host restatement of scipy's tree build and traversal order (csrc/kdtree_host.cpp), checked once
     per process against the installed scipy (``_ckdtree_restatement_matches_scipy``)."""
     _ckdtree_restatement_matches_scipy()
     coords = np.ascontiguousarray(coords, dtype=np.float64)

@@ -482,7 +482,7 @@ def test_tl_deconvolve_anndata_surface():
 @pytest.mark.parametrize("name", ["square_k6", "hex_k6", "square100_k6"])
 def test_lattice_k6_with_the_reference_tie_order_is_exact(name, ties):
     """On lattices where the k-th neighbour is tied (square: every spot) the neighbour lists come from the host restatement of
-    scipy's cKDTree order (csrc/kdtree_order.cpp) - the adjacency is then the reference's index for index and the fit agrees
+    scipy's cKDTree order (csrc/kdtree_host.cpp) - the adjacency is then the reference's index for index and the fit agrees
     at the usual 1e-8 (the device's own tie rule, knn_ties="index", leaves 4.5e-4 / 3.1e-4, see below).  knn_ties="auto" is
     the DEFAULT (the fit is repeated on the reference's choice once the device build has reported ties), "ckdtree" decides
     before the first solve.  No warning in either mode; the tie count stays in info_."""

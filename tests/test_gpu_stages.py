@@ -594,7 +594,7 @@ def test_device_built_ckdtree_has_scipys_index_array(case):
                                   "square_big_rows"])
 def test_device_ckdtree_queries_equal_the_host_restatement(case, monkeypatch):
     """fdx_graph_plan_set_ckdtree_lists_dev (csrc/kdtree_order.cpp): the k-nearest queries of the restated cKDTree answered by a
-    device kernel (one lane per query: the host's node visits, heap operations and comparisons, in its order) against the same
+    device kernel (csrc/kdtree_query_dev.cpp; one lane per query: the host's node visits, heap operations and comparisons, in its order) against the same
     queries on the host's threads (FDX_KDTREE_HOST_QUERIES=1), which tests/test_host.py pins to scipy itself - list for list,
     on lattices (every k-th neighbour tied), rounded and duplicated points, 1 to 3 coordinates, all rows and a subset."""
     import ctypes

@@ -369,7 +369,9 @@ def test_bench_dump_sample_is_fixed_and_within_budget():
 
 def test_schedule_builders_under_address_and_ub_sanitizers():
     """`make -C flashdeconv_amd/csrc asan-host`: the pure-host schedule builders (tile_plan.cpp) compiled with g++
-    -fsanitize=address,undefined and replayed on a range of shapes (GPU AddressSanitizer is not available on the build pool)."""
+    -fsanitize=address,undefined and replayed on a range of shapes (GPU AddressSanitizer is not available on the build pool); the
+    restated cKDTree's host build and queries with their thread pool (kdtree_host.cpp, host_threads.cpp) also under
+    -fsanitize=thread."""
     import shutil
     import subprocess
     if not shutil.which("g++") or not shutil.which("make"):
@@ -441,7 +443,7 @@ def test_ckdtree_order_restatement_on_heavily_duplicated_coordinates():
 
 def test_ckdtree_builds_from_several_threads_share_the_pool():
     """Thread ranks of one process each build the restated tree of their coordinates at the same time: the builds cut their work
-    into tasks of ONE pool (csrc/kdtree_order.cpp: KdPool) and run each other's tasks while they wait.  Every tree against scipy."""
+    into tasks of ONE pool (csrc/host_threads.h: KdPool) and run each other's tasks while they wait.  Every tree against scipy."""
     import threading
     from scipy.spatial import cKDTree
     from flashdeconv_amd import _lib
@@ -472,7 +474,7 @@ def test_ckdtree_builds_from_several_threads_share_the_pool():
 
 
 def test_ckdtree_thread_pool_survives_a_fork():
-    """The thread pool of the tree build (csrc/kdtree_order.cpp: KdPool) lives in the process that started it: a fork()ed child
+    """The thread pool of the tree build (csrc/host_threads.cpp: KdPool) lives in the process that started it: a fork()ed child
     (multiprocessing's default start method) has the pool's object without its threads - and its mutex / condition variable in
     whatever state the parent's workers, just going to sleep, had them in - and must start anew: same tree.  50000 points: above
     the size from which subtrees become pool tasks; the fork follows the parent's build at once."""
@@ -507,10 +509,38 @@ def test_ckdtree_thread_pool_survives_a_fork():
         assert status == 0, status
 
 
+def test_ckdtree_prebuild_nobody_consumes_is_joined_when_the_process_ends():
+    """fdx_ckdtree_prebuild (csrc/kdtree_order.cpp) builds the tree on a library thread; a process that ends without ever asking
+    for the lists must end cleanly - the pending build's thread is joined with its owner, not destroyed while it can still be
+    joined (std::terminate).  A child process: the end of the process is what is tested.  Host coordinates: no GPU involved.
+    The child leaves only when both builds have reported themselves done (FDX_TRACE_HOST, read from its own stderr): the thread
+    is then finished but not joined, and no longer reads the coordinates or uses the pool, which the interpreter's shutdown
+    and the process's exit take away before the pending build is destroyed."""
+    import subprocess
+    import sys
+    code = ("import os\n"
+            "r, w = os.pipe()\n"
+            "os.dup2(w, 2)\n"
+            "os.close(w)\n"
+            "import numpy as np\n"
+            "from flashdeconv_amd import _lib\n"
+            "lib = _lib.load()\n"
+            "c = np.ascontiguousarray(np.random.RandomState(0).rand(50000, 2))\n"
+            "_lib.check(lib.fdx_ckdtree_prebuild(_lib.ptr_f64(c), None, len(c), 2))\n"
+            "_lib.check(lib.fdx_ckdtree_prebuild(_lib.ptr_f64(c), None, len(c), 2))   # replaces (and joins) the first\n"
+            "seen = b''\n"
+            "while seen.count(b'ckdtree prebuild: tree of') < 2:\n"
+            "    seen += os.read(r, 4096)\n"
+            "print('both built')\n")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, FDX_TRACE_HOST="1"))
+    assert r.returncode == 0 and "both built" in r.stdout, (r.returncode, r.stdout[-2000:])
+
+
 @pytest.mark.parametrize("case", ["square", "square_scaled", "hex", "cube3d", "random2d", "random3d", "line", "duplicates",
                                   "square_shuffled", "rect_large", "square_big", "random_big", "square_huge"])
 def test_ckdtree_order_restatement_matches_scipy(case, monkeypatch):
-    """fdx_ckdtree_knn (csrc/kdtree_order.cpp) is a host restatement of scipy.spatial.cKDTree's build and k-nearest query
+    """fdx_ckdtree_knn (csrc/kdtree_host.cpp) is a host restatement of scipy.spatial.cKDTree's build and k-nearest query
     ORDER - what decides the reference's neighbour graph when distances tie exactly (flashdeconv/utils/graph.py:60-63).
     Against scipy itself: the tree's index array and the query result, index for index and in the same order, on lattices
     (every k-th neighbour tied), duplicated points, shuffled spot order and tie-free clouds.  Pure host code: no GPU."""

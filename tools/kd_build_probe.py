@@ -1,4 +1,4 @@
-"""Host time of the restated cKDTree's build (csrc/kdtree_order.cpp) on a square lattice, by thread share, by the node size from which
+"""Host time of the restated cKDTree's build (csrc/kdtree_host.cpp) on a square lattice, by thread share, by the node size from which
 a node's passes are cut into pool tasks, and by the size up to which subtrees are built on a contiguous copy.
 python tools/kd_build_probe.py [side]"""
 import sys
