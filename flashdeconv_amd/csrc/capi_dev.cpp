@@ -310,12 +310,23 @@ int fdx_prepare_csr_dev(const fdx_csr_view* Y, const int32_t* gene_idx, int32_t 
                         const int32_t* bucket, const double* weight_y, const double* weight_x, int32_t d, int32_t mode_y,
                         int32_t mode_x, double* H_out_dev, int64_t ldh, double* XtX_out_dev, double* XtX_out_host,
                         double* YtY_partial_out, void* stream) {
+    return fdx_prepare_csr_ex_dev(Y, gene_idx, G, X, K, bucket, weight_y, weight_x, d, mode_y, mode_x, H_out_dev, ldh, XtX_out_dev,
+                                  XtX_out_host, YtY_partial_out, nullptr, Y ? Y->n : 0, stream);
+}
+
+// ... for n_rows rows of the matrix in the order of row_map_dev (NULL: rows 0..n_rows-1), as a fit passes the graph's solver order
+// and a shard a subset; the values of the map are the caller's responsibility, as for fdx_prepare_dev
+int fdx_prepare_csr_ex_dev(const fdx_csr_view* Y, const int32_t* gene_idx, int32_t G, const double* X, int32_t K,
+                           const int32_t* bucket, const double* weight_y, const double* weight_x, int32_t d, int32_t mode_y,
+                           int32_t mode_x, double* H_out_dev, int64_t ldh, double* XtX_out_dev, double* XtX_out_host,
+                           double* YtY_partial_out, const int32_t* row_map_dev, int64_t n_rows, void* stream) {
     FDX_REQUIRE(Y != nullptr && Y->n >= 0 && Y->G > 0, "fdx_prepare_csr_dev: bad matrix");
     FDX_REQUIRE(Y->dtype == FDX_F32 || Y->dtype == FDX_F64, "fdx_prepare_csr_dev: dtype must be FDX_F32 or FDX_F64");
     FDX_REQUIRE(G > 0 && K > 0 && d > 0 && (gene_idx || G == Y->G), "fdx_prepare_csr_dev: bad shape");
     FDX_REQUIRE(X && bucket && weight_y && weight_x && H_out_dev && XtX_out_dev, "fdx_prepare_csr_dev: null array");
     FDX_REQUIRE(mode_y == FDX_PRE_RAW || mode_y == FDX_PRE_LOG_CPM_SPARSE, "fdx_prepare_csr_dev: mode_y must be FDX_PRE_RAW or FDX_PRE_LOG_CPM_SPARSE");
-    const long long n = Y->n;
+    const long long n = n_rows;
+    FDX_REQUIRE(n >= 0 && (row_map_dev || n <= Y->n), "fdx_prepare_csr_dev: bad number of rows");
     FDX_REQUIRE(ldh >= n, "fdx_prepare_csr_dev: leading dimension too small");
     hipStream_t st = (hipStream_t)stream;
     PoolStream pool_stream(st);
@@ -332,7 +343,7 @@ int fdx_prepare_csr_dev(const fdx_csr_view* Y, const int32_t* gene_idx, int32_t 
     double yty = 0.0;
     if (n > 0) {
         FDX_TRY(dSum.alloc(sizeof(double)));
-        FDX_TRY(queue_rows_to_h(ysrc, tables, n, G, d, K, mode_y, nullptr, x.Xs(), H_out_dev, ldh, false, &rows, st));
+        FDX_TRY(queue_rows_to_h(ysrc, tables, n, G, d, K, mode_y, row_map_dev, x.Xs(), H_out_dev, ldh, false, &rows, st));
         FDX_TRY(queue_yty(rows.dRowSq.as<double>(), n, dSum.as<double>(), &yty, nullptr, st, st));
     }
     if (XtX_out_host)

@@ -172,15 +172,26 @@ __global__ __launch_bounds__(256) void sketch_csr_kernel(const long long* __rest
     }
 }
 
+// waves (= rows in flight) per workgroup, the most workgroups of a launch and the LDS of sketch_csr_kernel: every wave has d
+// accumulators and a log1p table, the workgroup the selection bitmap
+CsrScatterCfg csr_scatter_cfg(int d, int sel_words) {
+    CsrScatterCfg c;
+    c.waves = 4;
+    while (c.waves > 1 && ((size_t)d + 64) * 8 * c.waves > 64 * 1024) c.waves >>= 1;
+    c.max_blocks = 256 * 16;
+    c.lds = ((size_t)d + 64) * 8 * c.waves + (size_t)sel_words * 4;
+    return c;
+}
+
 template <typename T>
 static int launch_sketch_csr_t(const long long* indptr, const int* indices, const T* data, const int* row_map, long long row0,
                                long long n, int d, int mode, const void* table, const unsigned* sel_bits, int sel_words,
                                double* Ys, long long ldys, double* row_sumsq, hipStream_t st) {
-    int waves = 4;
-    while (waves > 1 && ((size_t)d + 64) * 8 * waves > 64 * 1024) waves >>= 1;
-    const size_t lds = ((size_t)d + 64) * 8 * waves + (size_t)sel_words * 4;
+    const CsrScatterCfg cfg = csr_scatter_cfg(d, sel_words);
+    const int waves = cfg.waves;
+    const size_t lds = cfg.lds;
     if (lds > 160 * 1024) return fail(FDX_ERR_UNSUPPORTED, "sketch (CSR): sketch_dim and the gene bitmap do not fit in LDS");
-    const int blocks = (int)std::min<long long>((n + waves - 1) / waves, 256LL * 16);
+    const int blocks = (int)std::min<long long>((n + waves - 1) / waves, cfg.max_blocks);
     auto launch = [&](auto kern) -> int {
         if (lds > 64 * 1024)
             FDX_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -509,30 +520,50 @@ static size_t csr_contract_lds(int d, int TT, int sel_words) {
 
 // shapes the fused kernel takes: the A operands of a wave (NB x TT x 4 doubles) must fit beside the row's registers, and the keep
 // buffers need room for a wave's worth of entries at least
-bool csr_contract_ok(int d, int K, int sel_words) {
+// (ranks among the selected genes are 16-bit in the keep buffers and the bucket table: 65536 selected genes or more go the other way)
+bool csr_contract_ok(int d, int K, int sel_words, int n_sel) {
     if (d <= 0 || K <= 0 || K > 64 || d % 4 != 0) return false;
+    if (n_sel >= 65536) return false;
     const int NB = (d + 255) / 256, TT = (K + 15) / 16;
     if (NB * TT > 4) return false;
     return csr_contract_lds(d, TT, sel_words) + 16 * 64 * 10 <= 160 * 1024;
+}
+
+// rows in registers: 24 x 64 float32 entries (48 registers) beside two type tiles, 16 x 64 otherwise; of those, the slots of the
+// next row that are fetched ahead of the contraction
+constexpr int csr_row_slots(size_t elem, int TT) { return (elem == 4 && TT <= 2) ? 24 : 16; }
+constexpr int csr_row_slots_ahead(size_t elem, int TT) { return TT <= 2 ? (elem == 4 ? 12 : 6) : 8; }
+
+// what a launch of the fused kernel uses for a shape csr_contract_ok accepts (elem: bytes of a stored value)
+CsrContractCfg csr_contract_cfg(size_t elem, int d, int K, int sel_words, int n_sel) {
+    CsrContractCfg c;
+    c.NB = (d + 255) / 256;
+    c.TT = (K + 15) / 16;
+    c.NE = csr_row_slots(elem, c.TT);
+    c.NE1 = csr_row_slots_ahead(elem, c.TT);
+    const size_t base = csr_contract_lds(d, c.TT, sel_words);
+    const size_t tables = (size_t)n_sel * (sizeof(double) + sizeof(unsigned short)) + 16;
+    const size_t per_entry = 16 * (elem + sizeof(unsigned short));                // one keep-buffer entry of every wave
+    // weight / bucket by rank in LDS when that leaves the keep buffers 256 entries per wave; else read by rank from global memory
+    // (a few KB: cache-resident)
+    c.sel_in_lds = (n_sel < 65536 && base + tables + 256 * per_entry <= 160 * 1024) ? 1 : 0;
+    const size_t used = base + (c.sel_in_lds ? tables : 16);
+    c.cap = (int)std::min<size_t>(((160 * 1024 - used) / per_entry) & ~(size_t)63, 4096);
+    if (const char* e = env("FDX_CSR_KEEP_CAP")) c.cap = std::min(c.cap, std::max(64, atoi(e) & ~63));   // tests: rows that overflow the buffer
+    c.lds = used + (size_t)c.cap * per_entry;
+    c.max_grid = 256;
+    return c;
 }
 
 template <typename T, int MODE>
 static int launch_csr_contract_m(const long long* indptr, const int* indices, const T* data, const int* row_map, long long n, int d,
                                  const CsrSelection& sel, const double* Xs, int K, double* H, long long ldh, double* row_sumsq,
                                  hipStream_t st) {
-    const int NB = (d + 255) / 256, TT = (K + 15) / 16;
-    const size_t base = csr_contract_lds(d, TT, sel.sel_words);
-    const size_t tables = (size_t)sel.n_sel * (sizeof(double) + sizeof(unsigned short)) + 16;
-    const size_t per_entry = 16 * (sizeof(T) + sizeof(unsigned short));          // one keep-buffer entry of every wave
-    // weight / bucket by rank in LDS when that leaves the keep buffers 256 entries per wave; else read by rank from global memory
-    // (a few KB: cache-resident)
-    const int sel_in_lds = (sel.n_sel < 65536 && base + tables + 256 * per_entry <= 160 * 1024) ? 1 : 0;
     FDX_REQUIRE(sel.n_sel < 65536, "sketch (CSR, fused): more than 65535 selected genes");
-    const size_t used = base + (sel_in_lds ? tables : 16);
-    int cap = (int)std::min<size_t>(((160 * 1024 - used) / per_entry) & ~(size_t)63, 4096);
-    if (const char* e = env("FDX_CSR_KEEP_CAP")) cap = std::min(cap, std::max(64, atoi(e) & ~63));   // tests: rows that overflow the buffer
-    const size_t lds = used + (size_t)cap * per_entry;
-    const int grid = (int)std::min<long long>((n + 15) / 16, 256);
+    const CsrContractCfg cfg = csr_contract_cfg(sizeof(T), d, K, sel.sel_words, sel.n_sel);
+    const int NB = cfg.NB, TT = cfg.TT, sel_in_lds = cfg.sel_in_lds, cap = cfg.cap;
+    const size_t lds = cfg.lds;
+    const int grid = (int)std::min<long long>((n + 15) / 16, cfg.max_grid);
     const int no_table = fdx::env("FDX_NO_LOG_TABLE") ? 1 : 0;
     auto launch = [&](auto kern) -> int {
         if (lds > 64 * 1024)
@@ -543,17 +574,18 @@ static int launch_csr_contract_m(const long long* indptr, const int* indices, co
         FDX_CHECK_LAUNCH();
         return 0;
     };
-    // rows in registers: 24 x 64 float32 entries (48 registers) beside two type tiles, 16 x 64 otherwise
-    constexpr int NV2 = sizeof(T) == 4 ? 24 : 16;
-    constexpr int NV1 = sizeof(T) == 4 ? 12 : 6;
-    if (NB == 1 && TT == 1) return launch(sketch_csr_contract_kernel<T, MODE, 1, 1, NV2, NV1>);
-    if (NB == 1 && TT == 2) return launch(sketch_csr_contract_kernel<T, MODE, 1, 2, NV2, NV1>);
-    if (NB == 1 && TT == 3) return launch(sketch_csr_contract_kernel<T, MODE, 1, 3, 16, 8>);
-    if (NB == 1 && TT == 4) return launch(sketch_csr_contract_kernel<T, MODE, 1, 4, 16, 8>);
-    if (NB == 2 && TT == 1) return launch(sketch_csr_contract_kernel<T, MODE, 2, 1, NV2, NV1>);
-    if (NB == 2 && TT == 2) return launch(sketch_csr_contract_kernel<T, MODE, 2, 2, NV2, NV1>);
-    if (NB == 3 && TT == 1) return launch(sketch_csr_contract_kernel<T, MODE, 3, 1, NV2, NV1>);
-    if (NB == 4 && TT == 1) return launch(sketch_csr_contract_kernel<T, MODE, 4, 1, NV2, NV1>);
+#define FDX_CSR_CONTRACT(B, TILES)                                                                                                  \
+    if (NB == B && TT == TILES)                                                                                                    \
+        return launch(sketch_csr_contract_kernel<T, MODE, B, TILES, csr_row_slots(sizeof(T), TILES), csr_row_slots_ahead(sizeof(T), TILES)>)
+    FDX_CSR_CONTRACT(1, 1);
+    FDX_CSR_CONTRACT(1, 2);
+    FDX_CSR_CONTRACT(1, 3);
+    FDX_CSR_CONTRACT(1, 4);
+    FDX_CSR_CONTRACT(2, 1);
+    FDX_CSR_CONTRACT(2, 2);
+    FDX_CSR_CONTRACT(3, 1);
+    FDX_CSR_CONTRACT(4, 1);
+#undef FDX_CSR_CONTRACT
     return fail(FDX_ERR_UNSUPPORTED, "sketch (CSR, fused): shape not instantiated");
 }
 
@@ -579,6 +611,34 @@ int launch_sketch_csr_contract(const long long* indptr, const int* indices, cons
     }
     return fail(FDX_ERR_INVALID, "sketch (CSR, fused): dtype must be FDX_F32 or FDX_F64");
 }
+
+}  // namespace fdx
+
+// include/fdx.h: what YTables::build and queue_rows_to_h (prepare.cpp) choose for a CSR matrix, through the functions they and the
+// two launches call themselves - csr_contract_ok, then csr_contract_cfg or csr_scatter_cfg.
+extern "C" int fdx_sketch_csr_path(int32_t dtype, int32_t G_all, int32_t n_sel, int32_t d, int32_t K, int32_t mode, int32_t* path_out,
+                                   int32_t* dims_out) {
+    using namespace fdx;
+    FDX_REQUIRE(path_out && dims_out, "fdx_sketch_csr_path: null argument");
+    FDX_REQUIRE(dtype == FDX_F32 || dtype == FDX_F64, "fdx_sketch_csr_path: dtype must be FDX_F32 or FDX_F64");
+    FDX_REQUIRE(G_all > 0 && n_sel > 0 && n_sel <= G_all && d > 0 && K > 0, "fdx_sketch_csr_path: bad shape");
+    FDX_REQUIRE(mode == FDX_PRE_RAW || mode == FDX_PRE_LOG_CPM_SPARSE, "fdx_sketch_csr_path: mode must be FDX_PRE_RAW or FDX_PRE_LOG_CPM_SPARSE");
+    const int sel_words = (G_all + 31) / 32;
+    std::fill(dims_out, dims_out + 8, 0);
+    if (csr_contract_ok(d, K, sel_words, n_sel)) {
+        const CsrContractCfg c = csr_contract_cfg(dtype == FDX_F32 ? 4 : 8, d, K, sel_words, n_sel);
+        *path_out = 1;
+        dims_out[0] = c.NB; dims_out[1] = c.TT; dims_out[2] = c.NE; dims_out[3] = c.NE1;
+        dims_out[4] = c.cap; dims_out[5] = c.sel_in_lds; dims_out[6] = 16 * c.max_grid; dims_out[7] = (int32_t)c.lds;
+    } else {
+        const CsrScatterCfg c = csr_scatter_cfg(d, sel_words);
+        *path_out = 0;
+        dims_out[0] = c.waves; dims_out[1] = c.waves * c.max_blocks; dims_out[2] = (int32_t)SKETCH_CHUNK_ROWS; dims_out[3] = (int32_t)c.lds;
+    }
+    return 0;
+}
+
+namespace fdx {
 
 // ------------------------------------------------------------------------------------------------ gene statistics
 // z = log1p(y * 1e4 / max(lib, 1)) for every stored entry, then per gene sum z, sum z^2 (and sum y for "pearson").

@@ -218,8 +218,22 @@ namespace fdx {
 int launch_sketch_csr(const long long* indptr, const int* indices, const void* data, int dtype, const int* row_map,
                       long long row0, long long n, int d, int mode, const void* table, const unsigned* sel_bits,
                       int sel_words, double* Ys, long long ldys, double* row_sumsq, hipStream_t st);
+// Y_sketch is produced and consumed in chunks of this many rows (queue_rows_to_h, prepare.cpp)
+constexpr long long SKETCH_CHUNK_ROWS = 1LL << 18;
+// the launch shape of sketch_csr_kernel, for the launch and for fdx_sketch_csr_path
+struct CsrScatterCfg {
+    int waves = 0, max_blocks = 0;
+    size_t lds = 0;
+};
+CsrScatterCfg csr_scatter_cfg(int d, int sel_words);
 // fused form (csr_kernels.cpp): CSR rows -> LDS accumulators -> MFMA contraction -> H, no Y_sketch
-bool csr_contract_ok(int d, int K, int sel_words);
+bool csr_contract_ok(int d, int K, int sel_words, int n_sel);
+// instantiation, keep buffer and launch shape of the fused kernel, for the launch and for fdx_sketch_csr_path
+struct CsrContractCfg {
+    int NB = 0, TT = 0, NE = 0, NE1 = 0, cap = 0, sel_in_lds = 0, max_grid = 0;
+    size_t lds = 0;
+};
+CsrContractCfg csr_contract_cfg(size_t elem, int d, int K, int sel_words, int n_sel);
 struct CsrSelection;
 int launch_sketch_csr_contract(const long long* indptr, const int* indices, const void* data, int dtype, const int* row_map,
                                long long n, int d, int mode, const CsrSelection& sel, const double* Xs, int K, double* H,

@@ -14,7 +14,7 @@ namespace fdx {
 int YTables::build(const YSource& y, int G, int d, int K, const int32_t* bucket, const double* weight_y, hipStream_t xs,
                    const char* who) {
     if (!y.csr) return sketch_plan_cached(bucket, weight_y, G, d, xs, &plan);
-    csr_fused = csr_contract_ok(d, K, (y.csr->G + 31) / 32);
+    csr_fused = csr_contract_ok(d, K, (y.csr->G + 31) / 32, G);
     return sel.build(y.gene_idx, G, y.csr->G, bucket, weight_y, d, csr_fused, xs, who);
 }
 
@@ -106,8 +106,7 @@ int queue_rows_to_h(const YSource& y, const YTables& t, long long n, int G, int 
     }
     // Y_sketch is produced and consumed in chunks of 256k rows (1 GB at d = 512): measured on MI355X, smaller chunks
     // (down to Infinity-Cache size) under-fill the chip and are slower, larger ones gain nothing.
-    const long long chunk_rows = 1LL << 18;
-    const long long chunk = std::min<long long>(n, chunk_rows);
+    const long long chunk = std::min<long long>(n, SKETCH_CHUNK_ROWS);
     FDX_TRY(out->dYs.alloc((size_t)chunk * d * sizeof(double)));
     double* Ys = out->dYs.as<double>();
     const int n_chunks = (int)((n + chunk - 1) / chunk);

@@ -401,6 +401,67 @@ __global__ __launch_bounds__(512, 4) void sketch_rows_scatter_kernel(const T* __
     }
 }
 
+// Rows too long for LDS (neither the per-gene {weight, bucket} table of the scatter kernel nor a staged row fits: above about
+// 15000 genes for the table, 20000 float64 genes for the row): the same walk, one wave per row, with weight and bucket of a gene
+// read from global memory (cache-resident: every row reads the same two arrays) and only the d accumulators and the log1p table
+// in LDS.  It serves the signature side of a CSR fit with that many selected genes (K rows), where speed does not matter.
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void sketch_rows_stream_kernel(const T* __restrict__ Y, long long ldy, const int* __restrict__ row_map,
+                                                                 long long n, int G, int d, const double* __restrict__ gene_w,
+                                                                 const int* __restrict__ gene_bucket, double* __restrict__ Ys,
+                                                                 long long ldys, double* __restrict__ row_sumsq, int no_table) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int waves_per_blk = blockDim.x >> 6;
+    double* acc = reinterpret_cast<double*>(smem) + (size_t)wib * (d + 64);          // [waves][d + 64]
+    double* tab = acc + d;                                                            // this wave's log1p table (64)
+    const long long wave0 = (long long)blockIdx.x * waves_per_blk + wib;
+    const long long stride = (long long)gridDim.x * waves_per_blk;
+    for (long long p = wave0; p < n; p += stride) {
+        const long long row = row_map ? (long long)row_map[p] : p;
+        const T* yrow = Y + (size_t)row * ldy;
+        for (int c = lane; c < d; c += 64) acc[c] = 0.0;
+        double scale = 1.0;
+        bool use_tab = false;
+        if (MODE != FDX_PRE_RAW) {
+            double part = 0.0;
+            T mx = (T)0;
+            for (int g = lane; g < G; g += 64) { part += (double)yrow[g]; mx = yrow[g] > mx ? yrow[g] : mx; }
+            double sum = wave_sum(part);
+            use_tab = !no_table && wave_max((double)mx) < 64.0;
+            if (MODE == FDX_PRE_LOG_CPM) {
+                scale = (1.0 / (sum + 1e-10)) * 1e4;           // y / (rowsum + 1e-10) * 1e4   (deconv.py:190)
+            } else {
+                if (sum == 0.0) sum = 1.0;                     // lib_size[lib_size == 0] = 1  (deconv.py:183-185)
+                scale = 1e4 / sum;
+            }
+            if (use_tab) log1p_table_fill(tab, scale, lane);
+        }
+        __builtin_amdgcn_s_waitcnt(0xc07f);                    // zeroing (and the table) done before the adds
+        for (int g = lane; g < G; g += 64) {
+            const int b = gene_bucket[g];
+            if (b < 0) continue;                               // gene has no entry in Omega
+            double y = (double)yrow[g];
+            if (MODE != FDX_PRE_RAW) y = log1p_scaled(y, scale, tab, use_tab);
+            __hip_atomic_fetch_add(acc + b, gene_w[g] * y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        double* dst = Ys + (size_t)p * ldys;
+        double sq = 0.0;
+        for (int c = lane; c < d; c += 64) {
+            const double v = acc[c];
+            dst[c] = v;
+            sq = fma(v, v, sq);
+        }
+        if (row_sumsq) {
+            sq = wave_sum(sq);
+            if (lane == 0) row_sumsq[p] = sq;
+        }
+        __builtin_amdgcn_s_waitcnt(0xc07f);                    // reads of acc done before the next row zeroes it
+    }
+}
+
 template <typename T, int MODE, bool VEC>
 static const void* pick_reg_kernel(int total_len) {
     if (total_len <= 16) return (const void*)sketch_rows_reg_kernel<T, MODE, VEC, 16>;
@@ -458,7 +519,22 @@ static int launch_sketch_mode(const T* Y, long long ldy, const int* row_map, lon
     int waves = 4;
     while (waves > 1 && per_wave * waves > 64 * 1024) waves >>= 1;   // keep >= 2 blocks per CU where possible
     const size_t lds = per_wave * waves;
-    if (lds > 160 * 1024) return fail(FDX_ERR_UNSUPPORTED, "sketch: one gene row does not fit in LDS (G too large)");
+    if (lds > 160 * 1024) {
+        // a row does not fit in LDS: a CountSketch is streamed (sketch_rows_stream_kernel), a general Omega has no kernel for it
+        int ws = 4;
+        while (ws > 1 && ((size_t)d + 64) * 8 * ws > 64 * 1024) ws >>= 1;
+        const size_t lds_w = ((size_t)d + 64) * 8 * ws;
+        if (!plan.scatter_ok || lds_w > 160 * 1024)
+            return fail(FDX_ERR_UNSUPPORTED, "sketch: one gene row does not fit in LDS (G too large)");
+        auto kw = sketch_rows_stream_kernel<T, MODE>;
+        if (lds_w > 64 * 1024)
+            FDX_HIP(hipFuncSetAttribute((const void*)kw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w));
+        const int blocks_w = (int)std::min<long long>((n + ws - 1) / ws, 256LL * 8);
+        hipLaunchKernelGGL(kw, dim3(blocks_w), dim3(ws * 64), lds_w, st, Y, ldy, row_map, n, G, d, plan.gene_w, plan.gene_bucket, Ys,
+                           ldys, row_sumsq, fdx::env("FDX_NO_LOG_TABLE") ? 1 : 0);
+        FDX_CHECK_LAUNCH();
+        return 0;
+    }
     const bool vec = (ldy % (16 / (long long)sizeof(T)) == 0) && ((reinterpret_cast<uintptr_t>(Y) & 15) == 0);
     const long long want_blocks = (n + waves - 1) / waves;
     const int blocks = (int)std::min<long long>(want_blocks, 256LL * 8);

@@ -122,6 +122,14 @@ int fdx_tile_schedule(const int32_t* gene_bucket, const double* gene_w, int32_t 
  * it builds and caches that plan; no kernel is launched.  Tests state the path they mean to cover with it. */
 int fdx_sketch_path(int32_t y_dtype, const void* Y_dev, int64_t ldy, int32_t G, int32_t d, int32_t K, int32_t mode_y,
                     const int32_t* bucket, const double* weight_y, int32_t* path_out, int32_t* dims_out);
+/* The same question for a CSR matrix (fdx_prepare_csr_dev / fdx_fit_dev with sparse rows) of G_all columns, n_sel of them selected,
+ * values of `dtype`, mode FDX_PRE_RAW or FDX_PRE_LOG_CPM_SPARSE: *path_out = 0 the scatter kernel (rows -> Y_sketch) and the
+ * contraction, 1 the fused kernel.  dims_out[8]: path 1 {blocks of 256 buckets, type tiles, 64-entry register slots of a row, slots
+ * fetched ahead of the contraction, keep-buffer entries per wave (follows FDX_CSR_KEEP_CAP), weight / bucket by rank in LDS?, spots
+ * of one trip of the whole grid, LDS bytes}; path 0 {rows (waves) per workgroup, rows of one trip of the whole grid, rows per
+ * Y_sketch chunk, LDS bytes, 0...}.  Answered by the functions the dispatch and the launches call; no device is needed. */
+int fdx_sketch_csr_path(int32_t dtype, int32_t G_all, int32_t n_sel, int32_t d, int32_t K, int32_t mode, int32_t* path_out,
+                        int32_t* dims_out);
 /* out[i] = log1p(y[i] * scale) exactly as the fused sketch kernel evaluates the log-CPM transform (core/deconv.py:190-191)
  * for FLOAT32 rows with every argument in [0, 32000): float32-class (the reference computes this step in float32 for
  * float32 input, numpy dtype rules), v_log_f32 plus a first-order correction of the rounding of 1 + x.  Host arrays;
@@ -550,6 +558,13 @@ int fdx_prepare_csr_dev(const fdx_csr_view* Y, const int32_t* gene_idx, int32_t 
                         const int32_t* bucket, const double* weight_y, const double* weight_x, int32_t d, int32_t mode_y,
                         int32_t mode_x, double* H_out_dev, int64_t ldh, double* XtX_out_dev, double* XtX_out_host,
                         double* YtY_partial_out, void* stream);
+/* fdx_prepare_csr_dev for n_rows rows of the matrix: column p of H (ldh >= n_rows) is row row_map_dev[p] (int32, device; a fit passes
+ * the graph's solver order, a shard a subset).  NULL = rows 0..n_rows-1, n_rows <= Y->n.  The values of the map are the caller's
+ * responsibility, as for fdx_prepare_dev.  With (NULL, Y->n) it is fdx_prepare_csr_dev. */
+int fdx_prepare_csr_ex_dev(const fdx_csr_view* Y, const int32_t* gene_idx, int32_t G, const double* X, int32_t K,
+                           const int32_t* bucket, const double* weight_y, const double* weight_x, int32_t d, int32_t mode_y,
+                           int32_t mode_x, double* H_out_dev, int64_t ldh, double* XtX_out_dev, double* XtX_out_host,
+                           double* YtY_partial_out, const int32_t* row_map_dev, int64_t n_rows, void* stream);
 /* beta[k*ld + i] = 1/K for i < n_fill, 0 beyond (core/solver.py:372 plus the zero pad row). */
 int fdx_init_beta_dev(double* beta_dev, int64_t ld, int64_t n_fill, int32_t K, void* stream);
 /* One BCD sweep of the own spots of `g` (core/solver.py:104-184).  stats_dev: (max_iter, 128) uint64 slots zeroed by

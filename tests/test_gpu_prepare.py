@@ -2,7 +2,8 @@
 X_sketch -> H, XtX, YtY) against a plain float64 numpy evaluation of the same formulas, PER ELEMENT, on every kernel path
 the dispatch can take.  Every dense case first asks fdx_sketch_path which kernels the library will run (0 = two-kernel path,
 1 = narrow, 2 = wide tile form) and asserts the answer it was written for; every tile-path case runs once more under
-FDX_NO_FUSED=1 (the two-kernel path) against the same reference.
+FDX_NO_FUSED=1 (the two-kernel path) against the same reference.  The CSR cases at the end ask fdx_sketch_csr_path in the same
+way; the CSR kernels' own file is test_gpu_prepare_csr.py.
 
 The bound.  With T = f(Y) (the mode's rule), S = T Omega, H = S_x S_y^T and M = (|f(X)| |Omega_x|) (|f(Y)| |Omega_y|)^T:
 
@@ -34,11 +35,12 @@ its own c that any case used:
     tile wide, float64 chain               5.861      79 .. 3455      0.044  |    3.786        80 .. 12640    0.012
     tile narrow, float32-class             0.798      6               0.133  |    0.649        12             0.054
     tile wide, float32-class               0.712      6               0.119  |    0.644        12             0.054
-    two-kernel path                        9.995      15 .. 8020      0.052  |    3.786        65 .. 12900    0.038
+    two-kernel path                        9.995      15 .. 83513     0.052  |    3.786        65 .. 83550    0.038
     CSR, fused kernel                      5.119      273 .. 2295     0.018  |    1.355        475 .. 2495    0.002
     CSR, scatter + contraction             4.175      273 .. 1539     0.008  |    1.199        473 .. 1739    0.002
-    XtX (every case)                      11.567      15 .. 8020      0.044
-The file takes 5 s on that machine (263 cases).
+    XtX (every case)                      11.567      15 .. 83513     0.044
+(the c above 80000: the rows of 41003 genes that are streamed, whose row sum has that many addends.)
+The file takes 5 s on that machine (273 cases).
 """
 import ctypes
 
@@ -108,11 +110,14 @@ def c_transform(mode, addends):
 
 
 def bounds(ref, n, G, d, mode_y, mode_x, f32_class):
-    """(c64 of H, c64 of XtX, c64 of YtY, relative float32-class term of H, of YtY)"""
-    ty, tx = c_transform(mode_y, G), c_transform(mode_x, G)      # (float32-class rows too: their row sum is a float64 one)
-    c_h = ref["occ"] + ref["occ"] + d + ty + tx + 4 + 1
+    """(c64 of H, c64 of XtX, c64 of YtY, relative float32-class term of H, of YtY).  A reference over stored entries
+    (prepare_csr_ref.py) states the spot side's two data terms itself: occ_y, the most stored selected entries of one row in one
+    bucket, and addends_y, the longest selected row; without them both are the dense ones (bucket occupancy, G)."""
+    occ_y = ref.get("occ_y", ref["occ"])
+    ty, tx = c_transform(mode_y, ref.get("addends_y", G)), c_transform(mode_x, G)   # (float32-class rows too: their row sum is a float64 one)
+    c_h = occ_y + ref["occ"] + d + ty + tx + 4 + 1
     c_xx = 2 * (ref["occ"] + tx) + d + 4 + 1
-    c_yy = 2 * (ref["occ"] + ty) + d + n + 4 + 1
+    c_yy = 2 * (occ_y + ty) + d + n + 4 + 1
     e32 = C32 * E32 if f32_class else 0.0
     return c_h, c_xx, c_yy, e32, (1.0 + e32) ** 2 - 1.0
 
@@ -154,6 +159,16 @@ def sketch_path(dtype, ptr, ldy, G, d, K, mode, bucket, wy, flags=0):
     _lib.check(_lib.load().fdx_sketch_path(_lib.dtype_code(np.dtype(dtype)), ptr, ldy, G, d, K, _codes()[mode] | flags, _lib.ptr_i32(bucket),
                                            _lib.ptr_f64(wy), ctypes.byref(path), _lib.ptr_i32(dims)))
     return path.value, dict(zip(("NWC", "NWL", "JW", "TT", "GB", "NBLK"), (int(v) for v in dims)))
+
+
+def csr_sketch_path(dtype, G_all, n_sel, d, K, mode):
+    """(path, the eight dims) of fdx_sketch_csr_path: 0 = scatter kernel + contraction, 1 = the fused kernel; no device needed"""
+    from flashdeconv_amd import _lib
+    path = ctypes.c_int32(-1)
+    dims = np.zeros(8, dtype=np.int32)
+    _lib.check(_lib.load().fdx_sketch_csr_path(_lib.dtype_code(np.dtype(dtype)), G_all, n_sel, d, K, _codes().get(mode, mode),
+                                               ctypes.byref(path), _lib.ptr_i32(dims)))
+    return path.value, [int(v) for v in dims]
 
 
 def run_dense(Ybuf, n, G, X, bucket, wy, wx, d, mode_y, mode_x, row_map=None, ldh=None, flags=0, offset=0, query=True):
@@ -430,6 +445,18 @@ def test_an_omega_the_tile_schedule_refuses(mode, dtype, d, monkeypatch):
     check_case(monkeypatch, Y, X, bucket, wy, wx, d, mode, 0)
 
 
+@pytest.mark.parametrize("dtype,G", [(np.float64, 21001), (np.float32, 41003)])
+@pytest.mark.parametrize("mode", MODES)
+def test_rows_that_do_not_fit_in_lds_are_streamed(mode, dtype, G, monkeypatch):
+    """More genes than LDS holds as a staged row (160 KB: 20480 float64 or 40960 float32 values) or as the scatter kernel's
+    table: sketch_rows_stream_kernel reads weight and bucket per gene from global memory.  The signatures are float64, so the
+    X side takes it for both shapes; under FDX_NO_FUSED the spot side does too (10 workgroups of 4 rows, the last with one).
+    Not covered: a wave's second row, which takes more than 8192 rows of 168 KB each."""
+    Y, X, bucket, wy, wx = problem(37, G, 5, 64, mode, dtype, seed=2450 + G % 100)
+    monkeypatch.setenv("FDX_NO_FUSED", "1")
+    check_case(monkeypatch, Y, X, bucket, wy, wx, 64, mode, 0)
+
+
 # ---------------------------------------------------------------------------------------------- row contents
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("mode", LOG_MODES)
@@ -503,22 +530,27 @@ def test_layout_does_not_change_a_bit(mode, K, d, dtype, fused, monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------- the CSR seam
-def run_csr(Ycsr, gene_idx, G, X, bucket, wy, wx, d, mode, ldh):
+def run_csr(Ycsr, gene_idx, G, X, bucket, wy, wx, d, mode, ldh, ex=None, sort=True):
+    """fdx_prepare_csr_dev, or with ex = (row_map or None, n_rows) fdx_prepare_csr_ex_dev; sort=False uploads the rows as stored"""
     from flashdeconv_amd import _lib
     lib = _lib.load()
     _lib.require_gpu()
     K, n = X.shape[0], Ycsr.shape[0]
     H = np.full((K, ldh), SENTINEL)
     XtX, XtX_h, yty = np.zeros((K, K)), np.zeros((K, K)), ctypes.c_double(0.0)
-    csr = _lib.CsrOnDevice.from_scipy(Ycsr)
+    csr = _lib.CsrOnDevice.from_scipy(Ycsr, sort=sort)
     try:
         assert csr.view.dtype == _lib.dtype_code(Ycsr.data)
         with _DeviceArrays() as dev:
             dH, dG = dev.put(H), dev.put(XtX)
             gi = _lib.ptr_i32(gene_idx) if gene_idx is not None else None
-            _lib.check(lib.fdx_prepare_csr_dev(ctypes.byref(csr.view), gi, G, _lib.ptr_f64(X), K, _lib.ptr_i32(bucket), _lib.ptr_f64(wy),
-                                               _lib.ptr_f64(wx), d, _codes()[mode], _codes()[mode], dH, ldh, dG, _lib.ptr_f64(XtX_h),
-                                               ctypes.byref(yty), None))
+            args = (ctypes.byref(csr.view), gi, G, _lib.ptr_f64(X), K, _lib.ptr_i32(bucket), _lib.ptr_f64(wy), _lib.ptr_f64(wx), d,
+                    _codes().get(mode, mode), _codes().get(mode, mode), dH, ldh, dG, _lib.ptr_f64(XtX_h), ctypes.byref(yty))
+            if ex is None:
+                _lib.check(lib.fdx_prepare_csr_dev(*args, None))
+            else:
+                dmap = dev.put(np.ascontiguousarray(ex[0], dtype=np.int32)) if ex[0] is not None else None
+                _lib.check(lib.fdx_prepare_csr_ex_dev(*args, dmap, ex[1], None))
             _lib.download_bytes(H, dH)
             _lib.download_bytes(XtX, dG)
     finally:
@@ -547,6 +579,8 @@ def csr_problem(n, G_all, G, K, d, dtype, seed, dense_rows=0.5):
 
 def check_csr(Y, gene_idx, X, bucket, wy, d, mode, family):
     n, G = Y.shape[0], X.shape[1]
+    path, _ = csr_sketch_path(Y.dtype, Y.shape[1], G, d, X.shape[0], mode)
+    assert path == {"CSR fused": 1, "CSR two-kernel": 0}[family], (family, path)
     rows = Y if gene_idx is None else Y[:, gene_idx]           # the subset first, then the library size over it
     ref = reference(rows, X, bucket, wy, wy, d, mode, mode)
     got = run_csr(sparse.csr_matrix(Y), gene_idx, G, X, bucket, wy, wy, d, mode, n + 5)
@@ -559,8 +593,8 @@ def check_csr(Y, gene_idx, X, bucket, wy, d, mode, family):
 @pytest.mark.parametrize("mode", ["raw", "log_cpm_sparse"])
 def test_csr_rows(mode, dtype, subset, monkeypatch):
     """fdx_prepare_csr_dev, shapes the fused CSR kernel takes (csr_contract_ok: d % 4 == 0, blocks of 256 buckets x type tiles
-    <= 4): all columns or a selected subset, empty rows, a row with nothing selected.  No path query exists for CSR input; what
-    is stated is the rule."""
+    <= 4): all columns or a selected subset, empty rows, a row with nothing selected.  check_csr asserts the path by
+    fdx_sketch_csr_path."""
     Y, gene_idx, X, bucket, wy = csr_problem(300, 900, 500 if subset else 900, 8, 256, dtype, seed=3000 + subset)
     check_csr(Y, gene_idx, X, bucket, wy, 256, mode, "CSR fused")
 
