@@ -156,6 +156,9 @@ SIGNATURES = {
     "fdx_permutation_indices_dev": (c_int, [ctypes.c_uint64, c_i64, c_i64, c_void_p, c_void_p]),
     "fdx_label_pair_counts_dev": (c_int, [c_void_p, c_void_p, c_i32, ctypes.c_uint64, c_i64, c_i64, c_i32, c_void_p, p_i64, p_i64, p_i64,
                                           p_i64, p_i64, p_double, p_double, p_i32, c_void_p]),
+    "fdx_label_cooccurrence_dev": (c_int, [c_void_p, c_i64, c_i32, c_void_p, c_i32, p_double, c_i32, ctypes.c_uint64, c_i64, c_i64, c_i32,
+                                           c_i32, c_i32, c_i64, c_void_p, c_void_p, p_i64, p_i64, p_i64, p_i64, p_i64, p_double,
+                                           p_double, p_i32, p_i32, p_i64, c_void_p]),
     "fdx_label_gene_sums_dev": (c_int, [c_void_p, c_i32, c_i64, c_i32, c_i64, c_void_p, c_i32, p_i32, c_i32, p_i32, c_i32, ctypes.c_uint64,
                                         c_i64, c_i64, c_i32, c_i64, c_void_p, p_double, p_i64, p_i64, p_i64, p_i64, p_double, p_double,
                                         p_i32, c_void_p]),

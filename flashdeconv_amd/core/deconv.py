@@ -830,6 +830,42 @@ class FlashDeconv:
                                        random_state=self.random_state if random_state is None else random_state,
                                        return_null=return_null)
 
+    def get_co_occurrence(self, coords, labels=None, n_niches=None, radii=None, n_bands=10, n_permutations=999, random_state=None,
+                          **kw):
+        """At which distances niches or cell types occur together more often than chance, and where the association stops
+        (additive, not in the reference): the join counts of spot labels in every distance band of ``radii`` (None: ``n_bands``
+        multiples of the grid radius) with their exact moments, the analytic z score, the co-occurrence ratio and a permutation
+        test on the GPU - ``utils.cooccurrence.label_cooccurrence``.  The label sources are those of
+        ``get_neighborhood_enrichment``: ``labels`` (``n_labels`` may be passed beside them), ``n_niches`` (which takes the further
+        keywords of ``get_spatial_niches``) or neither - each spot's dominant cell type; giving both is a ``ValueError``.  The
+        model does not keep the coordinates: pass the ones the fit was given (``n_spots_`` rows).  ``random_state``: None is the
+        model's.  ``mode`` (``"band"`` or ``"cumulative"``), ``max_candidates`` and ``return_null`` go to ``label_cooccurrence``.
+        Works for both ``output`` kinds of ``fit``: labels stay on the device where they are."""
+        self._require_fitted()
+        if labels is not None and n_niches is not None:
+            raise ValueError("at most one of labels and n_niches may be given")
+        from ..utils._device import check_count
+        from ..utils.cooccurrence import _check_mode, label_cooccurrence
+        from ..utils.correlogram import _check_coords, _check_n_bands, _check_radii
+        from ..utils.neighborhoods import _check_flag
+        check_count("n_permutations", n_permutations)
+        return_null = _check_flag("return_null", kw.pop("return_null", False))
+        mode, max_candidates = _check_mode(kw.pop("mode", "band")), kw.pop("max_candidates", None)
+        n_labels = kw.pop("n_labels", None)
+        # the coordinates and the bands fail here, before the k-means (the labels proper are checked with their source)
+        shape = tuple(coords.shape) if hasattr(coords, "shape") else np.shape(coords)
+        if len(shape) == 2 and shape[0] != self.n_spots_:
+            raise ValueError(f"coords must have the {self.n_spots_} spots of the fit as rows, got shape {shape}")
+        _check_coords(coords, self.n_spots_)
+        if radii is None:
+            _check_n_bands(n_bands)
+        else:
+            _check_radii(radii)
+        labels, n_labels = self._spot_labels(labels, n_niches, n_labels, kw, "the co-occurrence")
+        return label_cooccurrence(labels, coords, radii=radii, n_bands=n_bands, n_labels=n_labels, n_permutations=n_permutations,
+                                  random_state=self.random_state if random_state is None else random_state, mode=mode,
+                                  max_candidates=max_candidates, return_null=return_null)
+
     def _spot_labels(self, labels, n_niches, n_labels, niche_kw, what):
         """``(labels, n_labels)`` of the one label source of a fitted model that the entries on spot labels share (``what`` names
         the entry in the messages): ``labels`` as given (checked, with the fit's spots), the ``labels`` of

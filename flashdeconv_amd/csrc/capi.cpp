@@ -34,7 +34,7 @@ using namespace fdx;
 
 extern "C" {
 
-int fdx_version(void) { return 211; }  // 0.2.11: fdx_label_gene_sums_dev / _csr_dev added (nothing else changed)
+int fdx_version(void) { return 212; }  // 0.2.12: fdx_label_cooccurrence_dev added (nothing else changed)
 
 const char* fdx_last_error(void) { return g_last_error.c_str(); }
 

@@ -18,36 +18,20 @@
 // candidates again - in a wave of their own (blockIdx.y), so that a small slide still fills the device.  No atomics; every sum
 // is formed in candidate order (cells of the block in z, y, x order, positions ascending), which depends on neither the grid,
 // nor KC, nor the chunk of bands.
+#include "band_walk.h"
 #include "gene_pass.h"
-#include "graph_internal.h"
 
 #include <vector>
 
 namespace fdx {
 
-constexpr int CG_MAX_BANDS = 32;
 constexpr int CG_MAX_KC = 16;                       // columns per walk at the most (the staging tile is sized by it)
 // LDS for the band accumulators of a wave.  The kernel waits on LDS round trips, so resident waves count for more than columns
 // per walk: 1M spots x 30 columns x 6 bands took 54.7 ms with 32 KB (3 waves per CU, 2 walks), 43.3 with 16 KB (7 waves, 4 walks),
 // 40.8 with 8 KB (8 walks) - but 8 KB leaves one column per walk at ten bands.
 constexpr size_t CG_ACC_BYTES = 16 * 1024;
 constexpr int CG_WALK_CAP_BLOCKS = 4096;            // waves of the band-lag kernel at the most
-constexpr int CG_COUNT_BLOCKS = 1024;
-constexpr int CG_SHELLS = 1;                        // shells of cells around a point's own that hold its pairs (CG_CELL_MARGIN)
-constexpr double CG_CELL_MARGIN = 1.0 + 1.0 / 65536.0;   // cell edge = r_B times this: two points within r_B are never two cells apart,
-                                                         // whatever the rounding of cell_coord does at a cell border
-
-struct CgRadii {
-    double r[CG_MAX_BANDS];      // the chunk's upper radii, ascending
-    double lo;                   // the radius below the chunk's first band; < 0: none (d = 0 belongs to band 1)
-    double d2_lo, d2_hi;         // squared distances surely outside the chunk: d2 < d2_lo or d2 > d2_hi (a sqrt saved, no decision made)
-    int nb;
-};
-
-__device__ __forceinline__ void cg_handoff() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
+// (band_walk.h: the cell edge, CgRadii and the wave hand-off, shared with the label walk of label_band_kernels.cpp)
 
 // acc[c * 64] += z[c * 64] for N columns: every read issued before the first add (the two LDS regions never overlap, which the
 // compiler cannot know; one column at a time is a chain of N read - read - add - write round trips)
@@ -60,12 +44,13 @@ __device__ __forceinline__ void cg_add_columns(double* __restrict__ acc, const d
     for (int c = 0; c < N; ++c) acc[c * 64] = a[c] + v[c];
 }
 
-// partials[block] = the block's share of sum over occupied cells of count(cell) * count(the 3^dim block of cells around it)
+// partials[2 * block] = the block's share of sum over occupied cells of count(cell) * count(the 3^dim block of cells around it),
+// partials[2 * block + 1] = the largest block count among its occupied cells
 __global__ __launch_bounds__(256) void cg_candidates_kernel(const int* __restrict__ cstart, const int* __restrict__ cend, GridParams gp,
                                                             long long* __restrict__ partials) {
-    __shared__ long long red[256];
+    __shared__ long long red[256], red_max[256];
     const long long n_cells = (long long)gp.nc[0] * gp.nc[1] * gp.nc[2];
-    long long s = 0;
+    long long s = 0, widest = 0;
     for (long long id = blockIdx.x * 256LL + threadIdx.x; id < n_cells; id += (long long)gridDim.x * 256) {
         const long long own = cend[id] - cstart[id];
         if (own <= 0) continue;
@@ -80,14 +65,47 @@ __global__ __launch_bounds__(256) void cg_candidates_kernel(const int* __restric
                     around += cend[cell] - cstart[cell];
                 }
         s += own * around;
+        widest = max(widest, around);
     }
     red[threadIdx.x] = s;
+    red_max[threadIdx.x] = widest;
     __syncthreads();
     for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+        if ((int)threadIdx.x < off) {
+            red[threadIdx.x] += red[threadIdx.x + off];
+            red_max[threadIdx.x] = max(red_max[threadIdx.x], red_max[threadIdx.x + off]);
+        }
         __syncthreads();
     }
-    if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+    if (threadIdx.x == 0) {
+        partials[2 * blockIdx.x] = red[0];
+        partials[2 * blockIdx.x + 1] = red_max[0];
+    }
+}
+
+int cg_guard(const char* who, const BinnedPoints& bins, long long max_candidates, long long* candidates, long long* max_around,
+             hipStream_t st) {
+    const long long n_cells = (long long)bins.gp.nc[0] * bins.gp.nc[1] * bins.gp.nc[2];
+    const int blocks = (int)std::max<long long>(1, std::min<long long>(CG_COUNT_BLOCKS, ceil_div(n_cells, 256)));
+    DevBuf part;
+    FDX_TRY(part.alloc((size_t)blocks * 2 * sizeof(long long)));
+    hipLaunchKernelGGL(cg_candidates_kernel, dim3(blocks), dim3(256), 0, st, bins.cstart.as<int>(), bins.cend_p, bins.gp,
+                       part.as<long long>());
+    FDX_CHECK_LAUNCH();
+    std::vector<long long> host((size_t)blocks * 2);
+    FDX_TRY(copy_d2h(host.data(), part.p, host.size() * sizeof(long long), st));
+    long long total = 0, widest = 0;
+    for (int b = 0; b < blocks; ++b) {
+        total += host[2 * (size_t)b];
+        widest = std::max(widest, host[2 * (size_t)b + 1]);
+    }
+    *candidates = total;
+    if (max_around) *max_around = widest;
+    if (total > max_candidates)
+        return fail(FDX_ERR_INVALID, std::string(who) + ": the largest radius makes the walk examine " + std::to_string(total) +
+                                         " candidate pairs, more than max_candidates = " + std::to_string(max_candidates) +
+                                         " (smaller radii, or raise max_candidates)");
+    return 0;
 }
 
 // lag[(b * K + k) * ld + p] = sum over the candidates q of position p with band(p, q) = b of Z[k][q], for the rc.nb bands of the
@@ -281,7 +299,7 @@ extern "C" int fdx_spatial_correlogram_dev(const double* coords_dev, int64_t n, 
         max_candidates = FDX_CORRELOGRAM_MAX_CANDIDATE_WALKS / ((long long)ceil_div(K, plan.kc) * ceil_div(B, plan.bands_per_pass));
     DevBuf scratch, out;
     FDX_TRY(scratch.alloc(plan.scratch_doubles * sizeof(double)));
-    const size_t out_doubles = 3 * (size_t)K + (size_t)B * KK + 2 * (size_t)B + 1;
+    const size_t out_doubles = 3 * (size_t)K + (size_t)B * KK + 2 * (size_t)B;
     FDX_TRY(out.alloc(out_doubles * sizeof(double)));
     const long long plane = (long long)K * plan.s.ld;
     double* Zp = scratch.as<double>();
@@ -291,31 +309,17 @@ extern "C" int fdx_spatial_correlogram_dev(const double* coords_dev, int64_t n, 
     double* d_m2 = d_mean + K;
     double* d_m4 = d_m2 + K;
     double* d_C = d_m4 + K;
-    long long* d_counts = reinterpret_cast<long long*>(d_C + (size_t)B * KK);   // (B, 2), then the candidate count
+    long long* d_counts = reinterpret_cast<long long*>(d_C + (size_t)B * KK);   // (B, 2)
 
     // the guard: what the walk would examine, known before it starts
-    const long long n_cells = (long long)bins.gp.nc[0] * bins.gp.nc[1] * bins.gp.nc[2];
-    const int count_blocks = (int)std::max<long long>(1, std::min<long long>(CG_COUNT_BLOCKS, ceil_div(n_cells, 256)));
-    hipLaunchKernelGGL(cg_candidates_kernel, dim3(count_blocks), dim3(256), 0, st, bins.cstart.as<int>(), bins.cend_p, bins.gp,
-                       reinterpret_cast<long long*>(part));
-    FDX_CHECK_LAUNCH();
-    FDX_TRY(launch_reduce_i64(reinterpret_cast<long long*>(part), count_blocks, 1, d_counts + 2 * (size_t)B, st));
     long long candidates = 0;
-    FDX_TRY(copy_d2h(&candidates, d_counts + 2 * (size_t)B, sizeof(long long), st));
+    const int guarded = cg_guard("fdx_spatial_correlogram_dev", bins, max_candidates, &candidates, nullptr, st);
     if (candidates_out) *candidates_out = candidates;
-    if (candidates > max_candidates)
-        return fail(FDX_ERR_INVALID, "fdx_spatial_correlogram_dev: the largest radius makes the walk examine " +
-                                         std::to_string(candidates) + " candidate pairs, more than max_candidates = " +
-                                         std::to_string(max_candidates) + " (smaller radii, or raise max_candidates)");
+    FDX_TRY(guarded);
 
     FDX_TRY(launch_spatial_moments(plan.s, V_dev, ldv, (int)n, K, bins.perm.as<int>(), Zp, part, d_mean, d_m2, d_m4, st));
     for (int b0 = 0; b0 < B; b0 += plan.bands_per_pass) {
-        CgRadii rc;
-        rc.nb = std::min(plan.bands_per_pass, B - b0);
-        for (int i = 0; i < CG_MAX_BANDS; ++i) rc.r[i] = i < rc.nb ? radii[b0 + i] : 0.0;
-        rc.lo = b0 > 0 ? radii[b0 - 1] : -1.0;
-        rc.d2_lo = b0 > 0 ? rc.lo * rc.lo * (1.0 - 1e-9) : -1.0;
-        rc.d2_hi = rc.r[rc.nb - 1] * rc.r[rc.nb - 1] * (1.0 + 1e-9);        // (an overflow to infinity filters nothing)
+        const CgRadii rc = cg_chunk_radii(radii, b0, std::min(plan.bands_per_pass, B - b0));
         hipLaunchKernelGGL(cg_band_lag_kernel, dim3(plan.walk_blocks, ceil_div(K, plan.kc)), dim3(64), plan.lds_bytes, st, bins.sc.as<double>(),
                            bins.cstart.as<int>(), bins.cend_p, bins.gp, (int)n, plan.s.n_slices, Zp, plan.s.ld, K, plan.kc, rc, lag,
                            bins.perm.as<int>(), degree_dev, (int)B, b0, reinterpret_cast<long long*>(part));

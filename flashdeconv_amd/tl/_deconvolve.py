@@ -9,7 +9,7 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
                spot_diagnostics=False, spatial_stats=False, n_niches=None, spatial_permutations=0, local_stats=False,
                correlogram=False, celltype_expression=False, spatial_genes=False, gene_pairs=None,
                gene_modules=False, niche_genes=False, gene_permutations=0, nhood_enrichment=False, ligrec_pairs=None,
-               ligrec_permutations=999):
+               ligrec_permutations=999, co_occurrence=False):
     """Writes ``.obsm[key_added]`` (proportions DataFrame), ``.obs[key_added + '_dominant']`` and
     ``.uns[key_added + '_params']``; returns the modified copy when ``copy=True``, else ``None``.  ``spot_diagnostics=True``
     (additive) also writes ``.obs[key_added + '_residual']`` (relative sketch residual per spot) and
@@ -77,11 +77,22 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
     target's, halved), ``pvalues`` (one-sided, against ``ligrec_permutations`` random reassignments of the labels to the spots on
     the GPU, seeded by ``random_state``; NaN where a group is empty or expresses its gene in under 1 % of its spots) and
     ``qvalues`` (Benjamini-Hochberg over all of them) (``FlashDeconv.get_ligand_receptor``) - and
-    ``.uns[key_added + '_params']['ligrec']``, the number of permutations."""
+    ``.uns[key_added + '_params']['ligrec']``, the number of permutations.
+    ``co_occurrence`` (additive): ``True`` (ten bands of the grid radius), an int (that many bands) or a sequence (the radii) -
+    anything else is a ``ValueError`` before the fit - also writes ``.uns[key_added + '_co_occurrence']``, a dict of ``radii``,
+    ``labels`` (the niche indices when ``n_niches`` is given, else the cell types: each spot labelled by its dominant one) and the
+    (band, label, label) arrays ``count`` (how often a spot of the first label has one of the second at a distance in the band),
+    ``ratio`` (the co-occurrence ratio: the share of the first label's band neighbours that carry the second, over the second's share
+    of all the band's pair ends), ``z_score`` (analytic, under random reassignment) and ``p_value`` (two-sided, against as many
+    random reassignments of the labels to the spots on the GPU as ``nhood_enrichment`` uses: ``spatial_permutations``, 999 when that
+    is 0; seeded by ``random_state``) (``FlashDeconv.get_co_occurrence``) - and ``.uns[key_added + '_params']['co_occurrence']``,
+    the request."""
     from ..core.deconv import FlashDeconv
     from ..io import prepare_data, result_to_anndata
     from ..utils.correlogram import correlogram_request
     correlogram_kw = correlogram_request(correlogram)          # a bad request fails here, not behind the fit
+    from ..utils.cooccurrence import cooccurrence_request
+    co_occurrence_kw = cooccurrence_request(co_occurrence)
     if not isinstance(celltype_expression, (bool, np.bool_)):
         raise ValueError(f"celltype_expression must be True or False, got {celltype_expression!r}")
     if not isinstance(spatial_genes, (bool, np.bool_)):
@@ -211,6 +222,19 @@ def deconvolve(adata_st, adata_ref, cell_type_key="cell_type", *, sketch_dim=512
             "zscore": pd.DataFrame(ne["z_sim"], index=index, columns=index),
             "pvalue": pd.DataFrame(ne["p_value"], index=index, columns=index)}
         adata.uns[f"{key_added}_params"]["nhood_enrichment"] = n_perm
+    if co_occurrence_kw is not None:
+        n_perm = int(spatial_permutations) if spatial_permutations else 999
+        if n_niches is not None:
+            co = model.get_co_occurrence(coords, labels=niches["labels"], n_labels=int(n_niches), n_permutations=n_perm,
+                                         random_state=random_state, **co_occurrence_kw)
+            index = list(range(int(n_niches)))
+        else:
+            co = model.get_co_occurrence(coords, n_permutations=n_perm, random_state=random_state, **co_occurrence_kw)
+            index = [str(t) for t in names]
+        adata.uns[f"{key_added}_co_occurrence"] = {"radii": co["radii"], "labels": index, "count": co["count"], "ratio": co["ratio"],
+                                                   "z_score": co["z_score"], "p_value": co["p_value"]}
+        adata.uns[f"{key_added}_params"]["co_occurrence"] = (True if not co_occurrence_kw else
+                                                              co_occurrence_kw.get("n_bands", co_occurrence_kw.get("radii")))
     if ligrec_pairs is not None:
         import pandas as pd
         if n_niches is not None:

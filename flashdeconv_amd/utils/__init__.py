@@ -7,7 +7,8 @@
 ``assemble_coexpression`` (``utils.gene_modules``) and ``spatial_gene_permutation_test`` / ``gene_permutation_sums`` /
 ``assemble_gene_permutation`` (``utils.gene_permutations``) and ``rank_genes_groups`` / ``gene_group_sums`` / ``assemble_group_tests``
 (``utils.group_genes``) and ``neighborhood_enrichment`` / ``label_pair_counts`` / ``join_count_moments`` / ``assemble_enrichment``
-(``utils.neighborhoods``) and ``ligand_receptor_test`` / ``label_gene_sums`` / ``assemble_ligrec`` (``utils.ligrec``) are additive."""
+(``utils.neighborhoods``) and ``label_cooccurrence`` / ``label_band_counts`` / ``assemble_cooccurrence`` (``utils.cooccurrence``) and
+``ligand_receptor_test`` / ``label_gene_sums`` / ``assemble_ligrec`` (``utils.ligrec``) are additive."""
 from .genes import select_hvg, select_markers, compute_leverage_scores  # noqa: F401
 from .graph import build_knn_graph, build_radius_graph, coords_to_adjacency  # noqa: F401
 from .random import check_random_state  # noqa: F401
@@ -23,6 +24,7 @@ from .gene_modules import spatial_gene_modules, spatial_coexpression, gene_coexp
 from .gene_permutations import spatial_gene_permutation_test, gene_permutation_sums, assemble_gene_permutation  # noqa: F401
 from .group_genes import rank_genes_groups, gene_group_sums, assemble_group_tests  # noqa: F401
 from .neighborhoods import neighborhood_enrichment, label_pair_counts, join_count_moments, assemble_enrichment  # noqa: F401
+from .cooccurrence import label_cooccurrence, label_band_counts, assemble_cooccurrence  # noqa: F401
 from .ligrec import ligand_receptor_test, label_gene_sums, assemble_ligrec  # noqa: F401
 
 __all__ = ["select_hvg", "select_markers", "compute_leverage_scores", "build_knn_graph", "build_radius_graph",
@@ -33,6 +35,7 @@ __all__ = ["select_hvg", "select_markers", "compute_leverage_scores", "build_knn
            "gene_spatial_sums", "assemble_genes", "rank_genes_groups", "gene_group_sums", "assemble_group_tests",
            "spatial_gene_permutation_test", "gene_permutation_sums", "assemble_gene_permutation",
            "neighborhood_enrichment", "label_pair_counts", "join_count_moments", "assemble_enrichment",
+           "label_cooccurrence", "label_band_counts", "assemble_cooccurrence",
            "ligand_receptor_test", "label_gene_sums", "assemble_ligrec",
            "spatial_gene_pairs", "gene_pair_sums", "assemble_pairs",
            "spatial_gene_modules", "spatial_coexpression", "gene_coexpression_sums", "assemble_coexpression"]

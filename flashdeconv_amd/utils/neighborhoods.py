@@ -37,8 +37,11 @@ count is an exact integer and does not depend on the batching or on how a range 
     p_greater   = (1 + #{r : N^r >= N}) / (R + 1)              p_less likewise with <=        p_value = min(1, 2 min(p_greater, p_less))
     null_mean   = N + mean_r d      null_std = std_r d (ddof = 0)      z_sim = (N - null_mean) / null_std      NaN where null_std = 0
 
-**Out of scope.**  Per-spot neighbour label counts (``spatial_sums`` on a one-hot matrix gives them); distance bands; sharded
-graphs (refused); conditional shuffles that keep the ``-1`` spots fixed.
+**Distance bands.**  The same counts, moments and null in every distance band of a set of radii, with no graph built, are
+``utils.cooccurrence.label_cooccurrence``.
+
+**Out of scope.**  Per-spot neighbour label counts (``spatial_sums`` on a one-hot matrix gives them); sharded graphs (refused);
+conditional shuffles that keep the ``-1`` spots fixed.
 """
 import ctypes
 

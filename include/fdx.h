@@ -725,6 +725,39 @@ int fdx_spatial_correlogram_dev(const double* coords_dev, int64_t n, int32_t dim
                                 const double* radii, int32_t B, int32_t max_bands_per_pass, int64_t max_candidates, double* mean,
                                 double* m2, double* m4, double* C, int64_t* W, int64_t* sum_deg_sq, int32_t* degree_dev,
                                 int32_t* bands_per_pass_out, int64_t* candidates_out, void* stream);
+/* Label co-occurrence by distance band (additive, not in the reference): the join counts of fdx_label_pair_counts_dev in every
+ * distance band of fdx_spatial_correlogram_dev, with their label-permutation null, in walks over the pairs within the largest radius
+ * and with no graph built.  coords_dev: (n, dim) row-major DEVICE, 1 <= dim <= 3; labels_dev: n int32 on the DEVICE in the order of
+ * coords_dev, each in [-1, C), -1 = not counted (and still a spot: it counts in n and in the degrees); 1 <= C <= 64; radii: B HOST
+ * values, 0 < r_1 < ... < r_B finite, 1 <= B <= 32.  Distances and bands are the correlogram's, bit for bit: band 1 holds
+ * d_ij <= r_1 (d = 0 among them), band b holds r_{b-1} < d_ij <= r_b, ordered pairs i != j.  To HOST memory:
+ *   label_counts_out[a] = n_a           pair_out (B, C, C) row-major = N_b[a][c] = #{(i, j) in band b : l_i = a, l_j = c}
+ *   deg_sums_out (3, B) = W_b = sum_i deg_{b,i} | sum_i deg_{b,i}^2 | sum_i (sum_{b' <= b} deg_{b',i})^2 (the radius graph of r_b)
+ * degree_dev (may be NULL): (n, B) int32 DEVICE, deg_{b,i} in the caller's spot order.  Then permutations
+ * first_perm .. first_perm + n_perm - 1 of `seed` (pi_r and l^r_i = l[pi_r(i)] as for fdx_label_pair_counts_dev: the same
+ * (seed, r) is the same relabelling) give N^r_b and the running sums Ncum^r_b = sum_{b' <= b} N^r_{b'}; to HOST memory, each
+ * (2, B, C, C) row-major with [0] the bands and [1] the running sums, against N_b and Ncum_b:
+ *   count_ge_out / count_le_out = how many of the call's permutations have N^r >= N / N^r <= N
+ *   sum_d_out / sumsq_d_out     = the float64 sums over them of d = N^r - N and of d^2, added in permutation order
+ * null_dev (may be NULL): (n_perm, B, C, C) int64 DEVICE array that receives every N^r_b.  Groups of 8 (C > 32) or 16 permutations
+ * share one distance computation per pair; *bands_per_pass_out bands (what 128 KiB of 32-bit bins in LDS hold, at most
+ * max_bands_per_pass when that is positive) are counted per walk, *batch_out permutations (what a scratch budget of 1 GiB holds,
+ * at most 64 groups, at most max_batch when positive) per launch chain, in at most max_blocks workgroups a group when that is
+ * positive (more where the 32-bit bins of a workgroup need them); either pointer may be NULL.  Every count is an exact integer:
+ * no output depends on any of the three caps, on first_perm or on the call a permutation ran in, split calls add up exactly, no
+ * floating-point atomics, two calls return the same bits.  The guard is the correlogram's: the candidate pairs of a walk are
+ * computed first, returned in *candidates_out (may be NULL), and a call where they exceed max_candidates fails with
+ * FDX_ERR_INVALID before any pair is walked; max_candidates = 0 stands for FDX_CORRELOGRAM_MAX_CANDIDATE_WALKS / walks with
+ * walks = ceil(B / bands per pass) * (1 + ceil(n_perm / batch)).  n <= 1: zeros (count_ge = count_le = n_perm), nothing walked.
+ * Refused with a message: null pointers, n >= 2^31 - 128, dim, C, B or the radii out of range, negative counts, a spot with 2^26
+ * candidates or more, and - checked on the device, reported after the call - a label outside [-1, C).  Host synchronisations
+ * behind the binning's: the candidate count and the results. */
+int fdx_label_cooccurrence_dev(const double* coords_dev, int64_t n, int32_t dim, const int32_t* labels_dev, int32_t C,
+                               const double* radii, int32_t B, uint64_t seed, int64_t first_perm, int64_t n_perm, int32_t max_batch,
+                               int32_t max_bands_per_pass, int32_t max_blocks, int64_t max_candidates, int32_t* degree_dev,
+                               int64_t* null_dev, int64_t* label_counts_out, int64_t* pair_out, int64_t* deg_sums_out,
+                               int64_t* count_ge_out, int64_t* count_le_out, double* sum_d_out, double* sumsq_d_out,
+                               int32_t* batch_out, int32_t* bands_per_pass_out, int64_t* candidates_out, void* stream);
 /* out_dev[t] (count int32, DEVICE) = the t-th spot conditional permutation r of `seed` draws for `spot` among n, by the device
  * function the kernel of fdx_local_stats_dev uses; 0 <= spot < n, 0 <= count <= n - 1.  Asynchronous on `stream`. */
 int fdx_conditional_indices_dev(uint64_t seed, int64_t r, int64_t spot, int64_t n, int64_t count, int32_t* out_dev, void* stream);
